@@ -100,13 +100,38 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--measure-clock", action="store_true", help="count attempts in the timed frames too, so that the shader clock of the "
                     "overlapped launches can be read afterwards (two timestamp reads per wave; the counters cost an atomic per tile)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure as well: roofline blocks, secondary figures, "
+                    "program build timing, CPU baseline (--no-secondary / --no-cpu-baseline / --no-build-timing switch parts off).  Without it "
+                    "a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps write the frame the last one rendered to DIR "
+                    "as float32 .npy (see dump_outputs)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_secondary = args.no_cpu_baseline = args.no_build_timing = True
     if args.config in OTHER_CONFIGS:
         c = OTHER_CONFIGS[args.config]
         args.metric, (args.width, args.height), args.camera, args.redshift = c["metric"], c["size"], ",".join(str(x) for x in c["camera"]), c["features"].get("redshift", 0)
     if args.fused_shading == 1:   # a build option of the programs (part of their cache key)
         os.environ["GR_EXTRA_FLAGS"] = (os.environ.get("GR_EXTRA_FLAGS", "") + " -DGR_TILE_SHADING").strip()
     return args
+
+
+DUMP_PIXELS = 1 << 21   # a frame of more pixels is dumped as this many of them: 32 MiB of RGBA + 16 MiB of indices
+
+
+def dump_outputs(directory, frame):
+    """--dump-outputs: the [H, W, 4] float32 frame a timed step hands its caller.  Up to DUMP_PIXELS pixels it is written whole
+    (frame.npy); a larger one (a 4K frame is 127 MiB) as a fixed sample of its pixels, drawn with a fixed seed so that every run of the
+    same size samples the same ones: frame_pixels.npy [n, 4] and frame_pixel_index.npy [n] (flat index y * W + x, float64)"""
+    os.makedirs(directory, exist_ok=True)
+    px = np.ascontiguousarray(frame, dtype=np.float32)
+    h, w = px.shape[:2]
+    if h * w <= DUMP_PIXELS:
+        np.save(os.path.join(directory, "frame.npy"), px)
+        return
+    index = np.sort(np.random.default_rng(0).choice(h * w, DUMP_PIXELS, replace=False))
+    np.save(os.path.join(directory, "frame_pixels.npy"), px.reshape(h * w, -1)[index])
+    np.save(os.path.join(directory, "frame_pixel_index.npy"), index.astype(np.float64))
 
 
 def cpu_baseline(metric_name, cfg_values, features_kw, target_seconds, prefer="port"):
@@ -332,15 +357,17 @@ def single_process(args):
             st.trace_log(reset=True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        frame()
+        j = frame()
     sync()
     elapsed = time.perf_counter() - t0
     logged = [st.trace_log(reset=True) for row in states for st in row]
     launches = sum(c for _, c in logged)
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[j].cpu().numpy())
     # participant 0's share on its own, one launch at a time: the kernel's duration the roofline divides by
     stage = {}
-    for i in range(4):
+    for i in range(4 if args.full else 0):
         count[0] = 0
         o = gra.frame_options(mode=gra.MODE_FUSED, time_kernels=1, count_attempts=1, inline_prepass=0)
         parts[0].render(states[0][0], programs[devices[0]], metric, camera, outs[0].data_ptr(), (skies[devices[0]].data_ptr(), 4096, 2048, levels),
@@ -375,6 +402,9 @@ def single_process(args):
         "stage_ms_sequential_frame": {key: round(v, 4) for key, v in stage.items()},
         "first_frame_check": "the assembled frame equals device 0's own whole frame bit for bit",
     }
+    if not args.full:   # the launches one at a time were not run
+        line["roofline"] = None
+        del line["stage_ms_sequential_frame"]
     if rehearsal:
         line["rehearsal"] = f"GR_BENCH_ONE_DEVICE: {n} participants on ONE GPU, one process, peer-copy transport - a run of the single-process N-device path, not a measurement"
     for p in parts:
@@ -680,9 +710,11 @@ def main():
     logged = [slot.state.trace_log(reset=True) for slot in ring]
     launches = sum(n for _, n in logged)
     avg_launch_s = sum(ms for ms, _ in logged) / max(launches, 1) * 1e-3
+    if args.dump_outputs and rank == 0:   # (before any later frame renders into the ring's outputs)
+        dump_outputs(args.dump_outputs, ring[(frame_index[0] - 1) % in_flight].out[:H].cpu().numpy())
 
     without_transfer_s = None
-    if multi:
+    if multi and args.full:
         # the same frames with every rank rendering its (rotating) share and nothing sent - what the exchange costs on
         # the critical path is the difference
         barrier()
@@ -824,20 +856,23 @@ def main():
     if args.config in OTHER_CONFIGS:
         tag = OTHER_CONFIGS[args.config]["tag"]
     tag = tag or f"{args.metric}_{W}x{H}"
-    roofline, valu, stages = roofline_blocks(program, cfg_values, tag, elapsed / args.steps, avg_launch_s, launches)
-    if world > 1:   # every rank's trace launch: as timed in the overlapped region, and on its own
+    roofline = None
+    if args.full:
+        roofline, valu, stages = roofline_blocks(program, cfg_values, tag, elapsed / args.steps, avg_launch_s, launches)
+    if world > 1 and args.full:   # every rank's trace launch: as timed in the overlapped region, and on its own
         mine = torch.tensor([avg_launch_s * 1e3, stages.get("trace", 0.0), stages.get("prepass", 0.0)], dtype=torch.float64, device=coll_device)
         everyone = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(everyone, mine)
         extra["per_rank_trace_launch_ms"] = {"overlapped": [round(float(t[0]), 4) for t in everyone],
                                              "one_at_a_time": [round(float(t[1]), 4) for t in everyone],
                                              "prepass_one_at_a_time": [round(float(t[2]), 4) for t in everyone]}
-    extra["valu_roofline"] = valu
-    extra["stage_ms_sequential_frame"] = {k: round(v, 4) for k, v in stages.items()}
+    if args.full:
+        extra["valu_roofline"] = valu
+        extra["stage_ms_sequential_frame"] = {k: round(v, 4) for k, v in stages.items()}
     if multi:
         # per-rank view of the split (rank 0's): what the SCALE run needs to tell imbalance from communication
         extra["rank0_rows"] = sum(b - a for a, b in plan.blocks_of(rank))
-    if not multi:
+    if not multi and args.full:
         rd = np.empty(W * H, dtype=gra.pipeline.RENDER_DATA_DTYPE)
         gra.check(gra.lib.gr_device_download(local_rank, rd.ctypes.data_as(ctypes.c_void_p), state.buffer(gra.BUF_RENDER_DATA), rd.nbytes))
         skipped = int((rd["terminated"] == 2).sum())

@@ -426,9 +426,12 @@ def test_bench_gpus_n_means_n_gpus_however_it_is_started():
 def test_bench_plain_invocation_without_the_gpus_exits_non_zero(n):
     import subprocess
     import sys
-    # (asked inside the test, not in a skipif at import: a torch.cuda call while pytest COLLECTS initialises torch's HIP runtime in the
-    # process before the library's own first device call, and on the GPU box that first call then found no device - round 6)
-    if torch.cuda.is_available():
+    # (asked inside the test and through the library's own HIP runtime: a torch.cuda call initialises torch's HIP runtime in the
+    # process before the library's own first device call, and the GPU tests of the same process then found no device - round 6)
+    import ctypes
+    import geodesic_raytracing_amd as gra
+    devices = ctypes.c_int(0)
+    if gra.lib.gr_device_count(ctypes.byref(devices)) == 0 and devices.value > 0:
         pytest.skip("the refusal of a box without GPUs")
     _, root = _bench_module()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}

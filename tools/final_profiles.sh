@@ -11,6 +11,7 @@
 TAG=${1:-r03}
 WORKLOADS=${2:-"a045 a09 dk alc"}
 OUT=$GRAFT_REPO_ROOT/gpurun_out
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for W in $WORKLOADS; do
   case $W in
@@ -23,7 +24,7 @@ for W in $WORKLOADS; do
     refseqdyn) SEL="--mode reference --program dynamic"; STEPS=10;;      # ... and the reference-shaped sequence through it
     *) echo "unknown workload $W"; continue;;
   esac
-  ARGS="$SEL --steps $STEPS --warmup 3 --no-cpu-baseline --no-secondary"
+  ARGS="$SEL --steps $STEPS --warmup 3 --full --no-cpu-baseline --no-secondary"
   timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_${W}_stats -o bench -- python $GRAFT_REPO_ROOT/bench.py $ARGS > $OUT/${TAG}_${W}_stats.log 2>&1
   timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_${W}_exclusive_stats -o bench -- python $GRAFT_REPO_ROOT/bench.py $ARGS --frames-in-flight 1 --no-lookahead --inline-prepass 0 > $OUT/${TAG}_${W}_exclusive_stats.log 2>&1
   tail -1 $OUT/${TAG}_${W}_stats.log | cut -c1-160
@@ -35,7 +36,7 @@ for W in $WORKLOADS; do
     i=$((i+1))
     # counters serialise kernels: frames in flight 1 keeps the launches comparable with the sequential trace time
     timeout 300 rocprofv3 --kernel-trace --pmc $C -d $OUT/${TAG}_${W}_pmc$i -o pmc --output-format csv -- \
-        python $GRAFT_REPO_ROOT/bench.py $SEL --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --frames-in-flight 1 --no-lookahead --inline-prepass 0 > $OUT/${TAG}_${W}_pmc$i.log 2>&1
+        python $ROOT/bench.py $SEL --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary --frames-in-flight 1 --no-lookahead --inline-prepass 0 > $OUT/${TAG}_${W}_pmc$i.log 2>&1
     echo "$W pass $i ($C): rc=$? $(ls $OUT/${TAG}_${W}_pmc$i 2>/dev/null | tr '\n' ' ')"
   done
 done

@@ -3,7 +3,7 @@
 tag=${1:-quick}
 mkdir -p gpurun_out
 for cfg in "" "--config 3" "--config 4"; do
-  python bench.py --no-secondary --no-cpu-baseline $cfg 2>/dev/null | python -c "
+  python bench.py --full --no-secondary --no-cpu-baseline $cfg 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']; v=d.get('valu_roofline',{})

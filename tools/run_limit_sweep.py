@@ -33,7 +33,7 @@ else:
     for l in VARIANTS:
         row = {"run_limit": l}
         for tag, mode in [("pipelined", []), ("alone", ["--frames-in-flight", "1", "--no-lookahead"])]:
-            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary", "--steps", "40", "--warmup", "5"] + mode + extra,
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary", "--steps", "40", "--warmup", "5"] + mode + extra,
                                  env=env_of(l), capture_output=True, text=True)
             try:
                 j = json.loads(out.stdout.strip().splitlines()[-1])
