@@ -167,6 +167,47 @@ bool accelerations_without_trig(const std::vector<std::string>& opts) {
     return any;
 }
 
+// May a wave whose live rays are all inside the precision radius skip the outer boundary test (-DGR_RADIUS_EXITS_ORDERED, kernels/integrator.hip)?
+// Only when both hold for the program as it is built:
+//   * the distance the precision radius is compared with IS the polar radius the boundary tests compare, one float: DISTANCE_FUNC is the
+//     variable v2 itself and, where the generator's composed form stands in for it (GR_DISTANCE_OF_GENERIC), that and TO_COORD2 are both
+//     the bare variable v2 - the chart's own radius (Boyer-Lindquist, Schwarzschild ...), so nothing rests on the compiler evaluating two
+//     copies of one expression to the same bits.  Decided on the expressions, never by sampling.  Macro strings are compared: a string
+//     that writes the same thing another way, or does not say it, merely loses the shortcut.  Two holes' distance is not the chart radius;
+//   * SINGULAR_TERMINATOR < max_precision_radius < universe_size, as the floats the kernel compares with - which a substituted program
+//     (-DKERNEL_IS_STATIC, -DFEATURE_*) knows and a program whose features arrive at run time does not.
+// Then "inside the radius" excludes "at the outer boundary".  (The lower bound is the issue's condition for the pair of shortcuts; the
+// terminator-side one - no terminator test in a wave with nobody inside - is not built, the kernel tests the terminator in every wave, so
+// here the lower bound only withholds the shortcut.)  Anything else: the outer boundary is tested in every wave.
+bool radius_exits_ordered(const std::vector<std::string>& opts) {
+    bool is_static = false, singular = false;
+    std::string radius, universe, terminator, distance, composed, polar_radius;
+    for (auto& o : opts) {
+        if (o == "-DKERNEL_IS_STATIC") is_static = true;
+        else if (o.rfind("-DDISTANCE_FUNC=", 0) == 0) distance = o.substr(o.find('=') + 1);
+        else if (o.rfind("-DGR_DISTANCE_OF_GENERIC=", 0) == 0) composed = o.substr(o.find('=') + 1);
+        else if (o.rfind("-DTO_COORD2=", 0) == 0) polar_radius = o.substr(o.find('=') + 1);
+        else if (o == "-DSINGULAR") singular = true;
+        else if (o.rfind("-DFEATURE_max_precision_radius=", 0) == 0) radius = o.substr(o.find('=') + 1);
+        else if (o.rfind("-DFEATURE_universe_size=", 0) == 0) universe = o.substr(o.find('=') + 1);
+        else if (o.rfind("-DSINGULAR_TERMINATOR=", 0) == 0) terminator = o.substr(o.find('=') + 1);
+    }
+    // a float literal as the generator writes it (float_literal: "10.0f"); anything else - an expression, a hex float - is not understood
+    auto literal = [](const std::string& text, float& value) {
+        if (text.empty()) return false;
+        char* end = nullptr;
+        value = strtof(text.c_str(), &end);
+        if (end == text.c_str()) return false;
+        if (*end == 'f' || *end == 'F') end++;
+        return *end == '\0' && std::isfinite(value);
+    };
+    const bool distance_is_radius = distance == "v2" && !polar_radius.empty() && (composed.empty() || (composed == "v2" && polar_radius == "v2"));
+    float r = 0, u = 0, t = 0;
+    if (!is_static || !distance_is_radius || !literal(radius, r) || !literal(universe, u)) return false;
+    if (singular && !literal(terminator, t)) return false;
+    return (!singular || t < r) && r < u;
+}
+
 // VGPRs and scratch bytes per lane of one kernel, read from the code object's metadata note (msgpack: the kernel's map holds
 // ".name", later ".private_segment_fixed_size" and ".vgpr_count" - keys are sorted).  false when the note is not understood.
 bool kernel_resources(const std::string& code, const char* kernel, int& vgprs, int& scratch_bytes, int* sgprs = nullptr) {
@@ -312,6 +353,7 @@ int compile_code_object(const std::string& argument_string, std::string& code, s
     }
     if (pair_kernel_applies(opts)) opts.push_back("-DGR_TWO_RAYS_PER_LANE");
     if (accelerations_without_trig(opts)) opts.push_back("-DGR_ACCEL_WITHOUT_TRIG");
+    if (radius_exits_ordered(opts)) opts.push_back("-DGR_RADIUS_EXITS_ORDERED");
     if (const char* extra = getenv("GR_EXTRA_FLAGS"))
         for (auto& tok : split_arguments(extra)) opts.push_back(tok);
     opts.push_back(part == PART_FRAME ? "-DGR_BUILD_FRAME_PATH" : "-DGR_BUILD_REST");
@@ -857,6 +899,14 @@ int gr_argument_string_accelerations_call_trig(const char* argument_string) {
     for (auto& tok : split_arguments(argument_string))
         if (tok.rfind("-D", 0) == 0) opts.push_back(tok);
     return accelerations_without_trig(opts) ? 0 : 1;
+}
+
+int gr_argument_string_radius_exits_ordered(const char* argument_string) {
+    if (!argument_string) return -1;
+    std::vector<std::string> opts;
+    for (auto& tok : split_arguments(argument_string))
+        if (tok.rfind("-D", 0) == 0) opts.push_back(tok);
+    return radius_exits_ordered(opts) ? 1 : 0;
 }
 
 int gr_program_precompile(const char* argument_string) {

@@ -21,6 +21,27 @@ __device__ __forceinline__ float acceleration_to_precision(float4 acc, float max
 
 enum { DS_NONE = 0, DS_SKIP = 1, DS_RETURN = 2 };
 
+// The one-ray loop's paths for a wave whose live rays are all inside the precision radius (integrate_pingpong: the step selection, the
+// far step and the outer boundary test are skipped there - the same values, fewer instructions).  -DGR_NO_UNIFORM_WAVE_PATHS compiles
+// them out: the build tests/test_gpu_uniform_wave_paths.py holds the default one to, bit for bit.  That arm is a second copy of the
+// loop top and of the carried step's update, kept for the test alone: nothing keeps the two in step but the hand that edits them.
+#ifdef GR_NO_UNIFORM_WAVE_PATHS
+#define GR_UNIFORM_WAVE_PATHS 0
+#else
+#define GR_UNIFORM_WAVE_PATHS 1
+#endif
+// GR_OUTER_BOUNDARY_NEEDS_A_RAY_OUTSIDE: the radius the outer boundary test compares IS the distance the precision radius is compared
+// with, and SINGULAR_TERMINATOR < max_precision_radius < universe_size.  The host decides both when it builds a substituted program
+// (capi.cpp radius_exits_ordered: the first symbolically, on the generated expressions of the macro string - never by sampling -
+// the second on the feature values) and passes -DGR_RADIUS_EXITS_ORDERED.  A wave whose live rays are all inside the precision radius
+// then has none at the outer boundary and does not make that compare.  Every other program (features set at run time, a distance that
+// is not the chart radius - two holes -, a chart whose loop compares squares, a radius outside the two bounds) makes it in every wave.
+#if GR_UNIFORM_WAVE_PATHS && defined(GR_RADIUS_EXITS_ORDERED) && !defined(GR_POLAR_R_SQUARED) && !(defined(GR_DISTANCE_SQUARED_OF_GENERIC) && defined(ADAPTIVE_PRECISION))
+#define GR_OUTER_BOUNDARY_NEEDS_A_RAY_OUTSIDE 1
+#else
+#define GR_OUTER_BOUNDARY_NEEDS_A_RAY_OUTSIDE 0
+#endif
+
 struct ray_state {
     float4 position, velocity, acceleration;
     float next_ds;
@@ -199,6 +220,41 @@ __device__ __forceinline__ int integrate_pingpong(ray_state& s, cfg_t cfg, dfg_t
     };
 #endif
     const float far_offset = ambient_precision - 0.1f * new_max;
+#if GR_UNIFORM_WAVE_PATHS
+    // Lanes that MAY have to leave at the top of an attempt, as lane masks - a superset of the lanes stop_lost | stop_terminated is true
+    // on, one ballot per compare, joined as scalars: |r| >= universe_size ...
+    auto outer_boundary_candidates = [&](float4 pos, float4 polar) {
+#ifdef GR_POLAR_R_SQUARED
+        (void)polar;
+        return __builtin_amdgcn_ballot_w64(gm::polar_radius_squared(pos, cfg) >= universe2);
+#else
+        (void)pos;
+        return __builtin_amdgcn_ballot_w64(__builtin_fabsf(polar.y) >= universe);
+#endif
+    };
+    // ... and what every wave tests
+    auto loop_top_candidates = [&](float4 pos, float4 vel, float4 polar, float run) {
+        unsigned long long lanes = 0;
+#ifdef HAS_CYLINDRICAL_SINGULARITY
+        lanes |= __builtin_amdgcn_ballot_w64(pos.y < CYLINDRICAL_TERMINATOR);
+#endif
+#ifndef UNCONDITIONALLY_NONSINGULAR
+        lanes |= __builtin_amdgcn_ballot_w64(__builtin_fabsf(vel.x / run) > 1000 + f_in_x);   // the first condition of the runaway test
+#endif
+#ifdef SINGULAR
+#ifdef GR_POLAR_R_SQUARED
+        lanes |= __builtin_amdgcn_ballot_w64(gm::polar_radius_squared(pos, cfg) < (float)(SINGULAR_TERMINATOR) * (float)(SINGULAR_TERMINATOR));
+#else
+        lanes |= __builtin_amdgcn_ballot_w64(__builtin_fabsf(polar.y) < SINGULAR_TERMINATOR);
+#endif
+#endif
+#if !GR_OUTER_BOUNDARY_NEEDS_A_RAY_OUTSIDE
+        lanes |= outer_boundary_candidates(pos, polar);
+#endif
+        (void)pos; (void)vel; (void)polar; (void)run;
+        return lanes;
+    };
+#endif
     // One Verlet attempt from (p, v, a): the state the next attempt starts from goes to (po, vo, ao) - the new state, or the old
     // one again after a rejection.  Returns true when the loop is to be left: the ray is done and (p, v, a) is its final state
     // (what the loop carries - step suggestion, budget - is then that of the abandoned attempt); or pause_wave was raised
@@ -220,30 +276,61 @@ __device__ __forceinline__ int integrate_pingpong(ray_state& s, cfg_t cfg, dfg_t
         // the far step reads it - is taken in a wave that has a ray outside (a v_sqrt_f32 is four multiplies' issue time)
         const float ar2 = gm::distance_squared_from(position, cfg);
         const bool inside = ar2 < new_max * new_max;
-        const unsigned long long inside_lanes = __builtin_amdgcn_ballot_w64(inside);
-        const bool wave_inside = inside_lanes != 0;
-        const float near_ds = next_ds;
-        float far_ds = near_ds;
-        if (inside_lanes != __builtin_amdgcn_ballot_w64(true)) {
-            asm volatile("; a ray outside the precision radius: the far step");   // (keeps the root from being hoisted out of the branch)
-            far_ds = __builtin_fmaf(0.1f, __builtin_sqrtf(ar2), far_offset);
-        }
 #else
         const float ar = __builtin_fabsf(gm::distance_to_object_from(position, polar, cfg));
         const bool inside = ar < new_max;
-        const bool wave_inside = __builtin_amdgcn_ballot_w64(inside) != 0;   // (taken here, where the compare is: one scalar instruction)
+#endif
+        const unsigned long long inside_lanes = __builtin_amdgcn_ballot_w64(inside);   // (taken here, where the compare is: one scalar instruction)
+        const bool wave_inside = inside_lanes != 0;
         (void)wave_inside;
 #ifdef ADAPTIVE_PRECISION
         const float near_ds = next_ds;   // carried clamped (above, and every update below)
 #else
         const float near_ds = min_f32_uniform(ambient_precision, mixf(ambient_precision, subambient_precision, (clampf(ar, new_min, new_max) - new_min) / (new_max - new_min)));
 #endif
+#if GR_UNIFORM_WAVE_PATHS
+        // Every live ray of the wave inside the precision radius - nearly every attempt of the headline camera: the step is the near
+        // step (a select whose condition holds on every live lane is its first operand), the far step is not computed, and no ray can
+        // stand at the outer boundary.  Three wave-uniform branches per attempt in all (this block, the one behind `leaving`, and
+        // the carried step's update below), each around a small block - the attempt is not duplicated; the ballots are taken where the
+        // compares are (a lane mask that crosses a branch as a bool comes back through a 0/1 register), and a lane leaves only in the
+        // block behind `leaving`, which redoes the reference's tests in the reference's own terms.
+        const bool wave_all_inside = inside_lanes == __builtin_amdgcn_ballot_w64(true);
+        unsigned long long leaving = loop_top_candidates(position, velocity, polar, running);
+        float ds = near_ds;
+        if (!wave_all_inside) {
+            asm volatile("; a ray outside the precision radius: the far step, the outer boundary");   // (keeps the block from being turned into selects)
+#if defined(GR_DISTANCE_SQUARED_OF_GENERIC) && defined(ADAPTIVE_PRECISION)
+            const float far_ds = __builtin_fmaf(0.1f, __builtin_sqrtf(ar2), far_offset);
+#else
+            const float far_ds = __builtin_fmaf(0.1f, ar, far_offset);   // 0.1 (|r| - max_precision_radius) + ambient
+#endif
+            ds = inside ? near_ds : far_ds;
+#if GR_OUTER_BOUNDARY_NEEDS_A_RAY_OUTSIDE
+            leaving |= outer_boundary_candidates(position, polar);
+#endif
+        }
+        ds_used = ds;
+        running_before = running;
+        if (__builtin_expect(leaving != 0, 0)) {
+            asm volatile("; a ray at a loop-top exit");
+            if (stop_lost(position, velocity, acceleration, running) | stop_terminated(position, polar)) return true;
+        }
+#else
+#if defined(GR_DISTANCE_SQUARED_OF_GENERIC) && defined(ADAPTIVE_PRECISION)
+        float far_ds = near_ds;
+        if (inside_lanes != __builtin_amdgcn_ballot_w64(true)) {
+            asm volatile("; a ray outside the precision radius: the far step");   // (keeps the root from being hoisted out of the branch)
+            far_ds = __builtin_fmaf(0.1f, __builtin_sqrtf(ar2), far_offset);
+        }
+#else
         const float far_ds = __builtin_fmaf(0.1f, ar, far_offset);   // 0.1 (|r| - max_precision_radius) + ambient
 #endif
         const float ds = inside ? near_ds : far_ds;
         ds_used = ds;
         running_before = running;
         if (stop_lost(position, velocity, acceleration, running) | stop_terminated(position, polar)) return true;
+#endif
         GR_PROBE_EXTRA_INSTRUCTIONS(ds)
         // velocity Verlet (step_verlet, cl.cl:3273-3346) in the reference's operation order.  (Through the half-kicked velocity
         // h = v + a ds/2 - x' = x + h ds, v~ = h + a ds/2, v' = h + a' ds/2 - it is 16 fmas instead of 20 operations and the same
@@ -307,7 +394,16 @@ __device__ __forceinline__ int integrate_pingpong(ray_state& s, cfg_t cfg, dfg_t
                 const float poison = (next_velocity.x + next_velocity.y) + (next_velocity.z + next_velocity.w);
                 rare_lanes |= __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(poison) <= 3.402823466e+38f));
             }
-            next_ds = inside ? clamped : near_ds;   // also on an attempt that is then rejected (cl.cl:3443 comes before the returns)
+            // also on an attempt that is then rejected (cl.cl:3443 comes before the returns)
+#if GR_UNIFORM_WAVE_PATHS
+            next_ds = clamped;
+            if (!wave_all_inside) {
+                asm volatile("; a ray outside the precision radius keeps its carried step");
+                next_ds = inside ? clamped : near_ds;
+            }
+#else
+            next_ds = inside ? clamped : near_ds;
+#endif
         } else {
             // no ray of the wave inside the radius: nothing of the controller applies; a non-finite velocity (their sum) is handed to
             // the rare block as a NaN "error"

@@ -352,6 +352,10 @@ int gr_render_state_tile_history(gr_render_state* s, unsigned long long* frames_
  * 0 no, -1 no string.  A program whose accelerations call neither is built with -DGR_ACCEL_WITHOUT_TRIG: its loop has no range-limited
  * polynomial whose NaN it would have to tell from the metric's own (kernels/integrator.hip). */
 int gr_argument_string_accelerations_call_trig(const char* argument_string);
+/* Is a program built from this string built with -DGR_RADIUS_EXITS_ORDERED (kernels/integrator.hip: a wave whose live rays are all inside the
+ * precision radius skips the outer boundary test)?  1 when the string is a substituted program's, its distance function is the polar radius
+ * (DISTANCE_FUNC is v2; GR_DISTANCE_OF_GENERIC absent, or it and TO_COORD2 the bare v2) and SINGULAR_TERMINATOR < max_precision_radius < universe_size; 0 otherwise; -1 no string. */
+int gr_argument_string_radius_exits_ordered(const char* argument_string);
 /* How many frames of this render state took the previous frame's camera set-up and prepass (gr_frame_tuning.reuse_still_camera). */
 int gr_render_state_prepass_reused(gr_render_state* s, unsigned long long* frames);
 /* The two estimates tile_history works with (host arithmetic, no device).  gr_camera_origin_on_screen: the pixel at which the
