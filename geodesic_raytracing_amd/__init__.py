@@ -232,6 +232,10 @@ _SIGNATURES = {
     "gr_frame_options_default": (None, [ctypes.POINTER(FrameOptions)]),
     "gr_frame_tuning_default": (None, [ctypes.POINTER(FrameTuning)]),
     "gr_render_state_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "gr_render_state_create_supersampled": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "gr_render_state_supersample": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "gr_render_state_resolve_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
+    "gr_resolve_supersampled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "gr_render_state_destroy": (None, [c_void_p]),
     "gr_render_frame": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
                                 ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
@@ -305,5 +309,5 @@ def check(rc):
         raise GeodesicError(f"libgeodesic_hip error {rc}: {msg.decode(errors='replace') if msg else ''}")
 
 
-from .pipeline import (GeodesicCamera, Metric, Program, RenderState, TiledFrame, default_camera, default_features, frame_options,  # noqa: E402,F401
-                       synthetic_background, pack_background)
+from .pipeline import (GeodesicCamera, Metric, Program, RenderState, TiledFrame, box_resolve, default_camera, default_features,  # noqa: E402,F401
+                       frame_options, synthetic_background, pack_background)

@@ -96,17 +96,18 @@ const char* const KERNEL_NAMES[] = {
     "gr_cart_to_generic", "gr_init_basis_vectors", "gr_clear_termination_buffer", "gr_init_rays_generic",
     "gr_do_generic_rays", "gr_calculate_singularities", "gr_calculate_render_data",
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
-    "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic"};
+    "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_COUNT
 };
 
-// the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic
+// the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
+// filter of a supersampled frame (kernels/resolve.hip), which wants the same arithmetic and no part in the ray kernels' compilation
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
-           k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC;
+           k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED;
 }
 
 std::vector<std::string> split_arguments(const std::string& s) {
@@ -556,7 +557,7 @@ int compile_code_object(const std::string& argument_string, std::string& code, s
 // geodesic - from program + probes + metric + setup + camera + geodesic_camera, built with IEEE arithmetic (kernels/camera.hip says
 // why).  Same macro string, a cache file of its own; no pass over the code, no occupancy rule: nothing here is issue-bound.
 int compile_setup_module(const std::string& argument_string, std::string& code, bool cache_only) {
-    static const char* const PARTS[] = {"program.hip", "probes.inc", "metric.hip", "setup.hip", "camera.hip", "geodesic_camera.hip"};
+    static const char* const PARTS[] = {"program.hip", "probes.inc", "metric.hip", "setup.hip", "camera.hip", "geodesic_camera.hip", "resolve.hip"};
     std::string source;
     // GR_SETUP_KERNEL_SOURCE: one file instead of the parts, as GR_KERNEL_SOURCE is for the ray kernels' module.  (GR_KERNEL_SOURCE
     // alone replaces the ray kernels only - the tools that use it patch the trace kernel - and this module is then built from the
@@ -1462,6 +1463,21 @@ int gr_render_seams(gr_program* p, void* stream, const void* rdata, void* out, c
     void* args[] = {&rdata, &rdata_count, &out, &bg1, &bg2, &bg_width, &bg_height, &bg_levels, &width, &height,
                     &max_probes, &cfg, &dfg, &num, &block_pixels, &strip_rank, &strip_count, &compact_out, &seams_only};
     return launch(p, K_RENDER, stream, blocks(num, 256), 1, 256, 1, args);
+}
+
+// the box filter of a supersampled frame (kernels/resolve.hip): one work item per output pixel of this device's rows, a wave on 64
+// consecutive pixels of one row, four rows to a workgroup
+int gr_resolve_supersampled(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int block_rows,
+                            int strip_rank, int strip_count, int compact_out) {
+    GR_NEED("gr_resolve_supersampled", src, dst);
+    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_resolve_supersampled: factor " + std::to_string(factor) + " (1 to 4)");
+    if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
+        return fail(GR_ERROR_INVALID_ARGUMENT, "gr_resolve_supersampled: the frame's size");
+    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = height; }
+    if (block_rows <= 0 || strip_rank < 0 || strip_rank >= strip_count) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_resolve_supersampled: bad strip parameters");
+    int local_rows = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_rows;
+    void* args[] = {&src, &dst, &width, &height, &factor, &block_rows, &strip_rank, &strip_count, &compact_out, &local_rows};
+    return launch(p, K_RESOLVE_SUPERSAMPLED, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
 }
 
 int gr_internal_fail(int code, const char* msg) { return fail((gr_status)code, msg ? msg : ""); }

@@ -77,7 +77,14 @@ struct upload_ring {
 
 struct gr_render_state {
     int device = 0;
-    int width = 0, height = 0;
+    int width = 0, height = 0;      // what every frame of the state is traced and shaded at
+    // gr_render_state_create_supersampled: width x height above are supersample x the caller's frame per axis; a frame is shaded into
+    // traced_frame (float4[width * height], NULL for factor 1) and box-averaged from there into the caller's out (gr_resolve_supersampled)
+    int supersample = 1;
+    int out_width = 0, out_height = 0;
+    void* traced_frame = nullptr;
+    hipEvent_t ev_resolve[2] = {};   // time_kernels = 1: around the resolve launch (gr_render_state_resolve_ms)
+    bool resolve_timed = false;
     upload_ring uploads;
     // small buffers (render_state.hpp:150-170)
     void* camera_pos_cart = nullptr;
@@ -484,13 +491,23 @@ int gr_device_synchronize(int device) {
     return GR_OK;
 }
 
-int gr_render_state_create(int device, int width, int height, gr_render_state** out) {
-    if (!out || width <= 0 || height <= 0) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "bad render state size");
+// a state whose frames are out_width x out_height and are traced at factor x that per axis (1: gr_render_state_create)
+static int create_render_state(int device, int out_width, int out_height, int factor, gr_render_state** out) {
+    if (!out || out_width <= 0 || out_height <= 0) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "bad render state size");
+    if (factor < 1 || factor > 4)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("supersampling factor " + std::to_string(factor) + ": 1, 2, 3 or 4 per axis").c_str());
+    if (factor > 1 && (long long)out_width * factor * out_height * factor > 0x7fffffffll)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("supersampling factor " + std::to_string(factor) + ": " + std::to_string(out_width) + " x " +
+                                                            std::to_string(out_height) + " traced at that factor has more pixels than an int counts").c_str());
+    const int width = out_width * factor, height = out_height * factor;
     HIP_CHECK(hipSetDevice(device));
     gr_render_state* s = new gr_render_state();
     s->device = device;
     s->width = width;
     s->height = height;
+    s->supersample = factor;
+    s->out_width = out_width;
+    s->out_height = out_height;
     auto alloc = [&](void** p, size_t bytes) -> hipError_t {
         hipError_t e = hipMalloc(p, bytes);
         if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
@@ -525,6 +542,11 @@ int gr_render_state_create(int device, int width, int height, gr_render_state** 
         A(&slot.set.tile_order, order_bytes);
         A(&slot.velocity, 16);
     }
+    if (factor > 1) {
+        A(&s->traced_frame, px * 4 * sizeof(float));
+        for (auto& ev : s->ev_resolve)
+            if (e == hipSuccess) e = hipEventCreate(&ev);
+    }
     if (e == hipSuccess) {
         // High priority: the look-ahead prepass is a latency-bound launch of a few hundred waves that must make progress
         // while the trace kernel occupies every CU, and priority streams get hardware queues of their own (with the
@@ -554,6 +576,29 @@ int gr_render_state_create(int device, int width, int height, gr_render_state** 
     return GR_OK;
 }
 
+int gr_render_state_create(int device, int width, int height, gr_render_state** out) { return create_render_state(device, width, height, 1, out); }
+
+int gr_render_state_create_supersampled(int device, int width, int height, int factor, gr_render_state** out) {
+    return create_render_state(device, width, height, factor, out);
+}
+
+int gr_render_state_supersample(const gr_render_state* s, int* factor, int* traced_width, int* traced_height) {
+    if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null render state");
+    if (factor) *factor = s->supersample;
+    if (traced_width) *traced_width = s->width;
+    if (traced_height) *traced_height = s->height;
+    return GR_OK;
+}
+
+int gr_render_state_resolve_ms(gr_render_state* s, float* ms) {
+    if (!s || !ms) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
+    *ms = 0;
+    if (!s->resolve_timed) return GR_OK;
+    HIP_CHECK(hipEventSynchronize(s->ev_resolve[1]));
+    HIP_CHECK(hipEventElapsedTime(ms, s->ev_resolve[0], s->ev_resolve[1]));
+    return GR_OK;
+}
+
 void gr_render_state_destroy(gr_render_state* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -562,7 +607,8 @@ void gr_render_state_destroy(gr_render_state* s) {
     std::vector<void*> ptrs = {s->camera_pos_cart, s->camera_quat, s->camera_pos_generic, s->tetrad[0], s->tetrad[1], s->tetrad[2],
                                s->tetrad[3], s->rays_count_in, s->rays_adaptive_count, s->render_data_count, s->cfg, s->dfg,
                                s->attempts, s->rays_in, s->rays_adaptive, s->render_data, s->termination_buffer, s->tile_order,
-                               s->tile_cost, s->lattice_rays, s->guessed[0], s->guessed[1], s->pending_list, s->block_cost, s->block_cost_before, s->ref_cost[0], s->ref_cost[1], s->ref_order, s->ref_sort_work, s->parking_records, s->parking_words};
+                               s->tile_cost, s->lattice_rays, s->guessed[0], s->guessed[1], s->pending_list, s->block_cost, s->block_cost_before, s->ref_cost[0], s->ref_cost[1], s->ref_order, s->ref_sort_work, s->parking_records, s->parking_words,
+                               s->traced_frame};
     for (auto& slot : s->pre) {
         if (slot.stream) { (void)hipStreamSynchronize(slot.stream); (void)hipStreamDestroy(slot.stream); }
         if (slot.ready) (void)hipEventDestroy(slot.ready);
@@ -571,6 +617,7 @@ void gr_render_state_destroy(gr_render_state* s) {
                                  slot.velocity});
     }
     if (s->main_mark) (void)hipEventDestroy(s->main_mark);
+    for (auto& ev : s->ev_resolve) if (ev) (void)hipEventDestroy(ev);
     if (s->policy.copied) (void)hipEventDestroy(s->policy.copied);
     if (s->policy.host_flags) (void)hipHostFree(s->policy.host_flags);
     for (auto& pr : s->trace_log) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -817,9 +864,11 @@ void* gr_geodesic_camera_buffer(gr_geodesic_camera* g, int which) {
     return nullptr;
 }
 
-int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream_v, const gr_camera* camera,
-                    const gr_features* features_in, const float* cfg_values, int num_cfg_values, const void* bg1,
-                    const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* opt_in) {
+// one frame at the state's traced size: out is float4[s->width * s->height] (gr_render_frame below for a state of factor 1, and what a
+// supersampled state shades into its own traced frame)
+static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream_v, const gr_camera* camera,
+                               const gr_features* features_in, const float* cfg_values, int num_cfg_values, const void* bg1,
+                               const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* opt_in) {
     if (!s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
     // a frame that is to be shaded needs both skies and their shape (the texture pass reads them unchecked: a NULL sky is a device fault,
     // not an error code - tests/test_gpu_lifecycle.py found it); out == NULL stops after the render-data
@@ -1494,6 +1543,36 @@ int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void*
         GR_CHECK(gr_render(p, stream, s->render_data, s->render_data_count, width * height, out, bg1, bg2, bg_width, bg_height,
                            bg_levels, width, height, opt.max_probes, s->cfg, s->dfg));
         GR_CHECK(end(GR_STAGE_RENDER));
+    }
+    return GR_OK;
+}
+
+int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
+                    const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height,
+                    int bg_levels, void* out, const gr_frame_options* options) {
+    if (s) s->resolve_timed = false;
+    // (out == NULL stops after the records: nothing was shaded, nothing to resolve)
+    if (!s || s->supersample == 1 || !out)
+        return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out, options);
+    // A supersampled state: the frame as ever, at the traced size, into the state's own traced frame - a device's share of a split frame
+    // in blocks of factor x as many traced rows, so that they cover the rows its output blocks average - and from there into the
+    // caller's frame, laid out as the caller asked.
+    gr_frame_options opt;
+    gr_frame_options_default(&opt);
+    if (options) opt = *options;
+    const int factor = s->supersample, block_rows = opt.block_rows;
+    if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame: block_rows");
+    opt.block_rows *= factor;
+    GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
+                                 s->traced_frame, &opt));
+    const bool strips = opt.mode == GR_MODE_FUSED && opt.strip_count > 1;   // (as the fused path reads them; the reference-shaped sequence renders whole frames)
+    const bool timed = opt.time_kernels == 1;
+    if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
+    GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, strips ? block_rows : s->out_height,
+                                     strips ? opt.strip_rank : 0, strips ? opt.strip_count : 1, strips ? opt.compact_out : 0));
+    if (timed) {
+        HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
+        s->resolve_timed = true;
     }
     return GR_OK;
 }

@@ -549,6 +549,12 @@ int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const 
                           const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
                           int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation) {
     if (!t || !s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
+    {   // (the staging buffers and the transfers are laid out for rows of the participant's own size: a supersampled state's share would
+        // have to be resolved before it is shipped, which gr_render_frame's strip mode can do and this function does not do yet)
+        int factor = 1;
+        gr_render_state_supersample(s, &factor, nullptr, nullptr);
+        if (factor != 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a supersampled render state (gr_render_state_create_supersampled) cannot render a split frame yet; use gr_render_frame's strip mode, or a state of factor 1");
+    }
     if (t->device < 0) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "this participant was created without a device (schedule tests): nothing to render with");
     {   // (the staging buffers and the blocks' places in the root's frame are those of the participant's frame size)
         int sw = 0, sh = 0;

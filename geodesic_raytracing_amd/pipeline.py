@@ -332,10 +332,19 @@ def download(device, ptr, dtype, count):
 class RenderState:
     """Per-frame device buffers + the frame sequence (render_state.hpp:97-197, main.cpp:2244-2526)."""
 
-    def __init__(self, width, height, device=0):
+    def __init__(self, width, height, device=0, supersample=1):
+        """supersample = f > 1 (gr_render_state_create_supersampled; 2, 3 or 4): frames are still width x height, traced at f x that per
+        axis and box-averaged on the device (box_resolve says what that means).  Everything else about the state - buffer(), the
+        prepass grid, tile history - is of traced_size."""
         self.width, self.height, self.device = width, height, device
         self.handle = c_void_p()
-        check(lib.gr_render_state_create(device, width, height, ctypes.byref(self.handle)))
+        if supersample == 1:
+            check(lib.gr_render_state_create(device, width, height, ctypes.byref(self.handle)))
+        else:
+            check(lib.gr_render_state_create_supersampled(device, width, height, int(supersample), ctypes.byref(self.handle)))
+        f, tw, th = c_int(), c_int(), c_int()
+        check(lib.gr_render_state_supersample(self.handle, ctypes.byref(f), ctypes.byref(tw), ctypes.byref(th)))
+        self.supersample, self.traced_size = f.value, (tw.value, th.value)
 
     def __del__(self):
         if getattr(self, "handle", None):
@@ -385,6 +394,12 @@ class RenderState:
             check(lib.gr_render_state_stage_ms(self.handle, i, ctypes.byref(ms)))
             out[name] = ms.value
         return out
+
+    def resolve_ms(self):
+        """the resolve launch of the last frame rendered with frame_options(time_kernels=1) by a supersampled state (0.0: it launched none)"""
+        ms = c_float()
+        check(lib.gr_render_state_resolve_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
 
     def trace_log(self, reset=True):
         """(sum of durations in ms, number) of the trace launches logged with frame_options(time_kernels=2)"""
@@ -461,6 +476,18 @@ class GeodesicCamera:
         n = self.steps
         get = lambda which, dtype, count: download(self.device, lib.gr_geodesic_camera_buffer(self.handle, which), dtype, count)
         return get(0, np.float32, n * 4).reshape(n, 4), get(1, np.float32, n * 4).reshape(n, 4), get(2, np.float32, n)
+
+
+def box_resolve(frame, factor):
+    """What gr_resolve_supersampled computes, on the host: frame [H*f, W*f, C] -> [H, W, C], every output value the mean of its f x f
+    block of `frame`, taken in float64 and rounded to float32 once.  (The kernel sums the block in fp32 and multiplies by the rounded
+    1 / f^2: it agrees with this to (f^2 + 2) * 2^-24 of the block's mean magnitude, and exactly for f = 1.)"""
+    frame = np.asarray(frame)
+    f = int(factor)
+    if f < 1 or frame.ndim != 3 or frame.shape[0] % f or frame.shape[1] % f:
+        raise ValueError(f"box_resolve: a frame of shape {frame.shape} does not divide into {f} x {f} blocks")
+    h, w, c = frame.shape[0] // f, frame.shape[1] // f, frame.shape[2]
+    return frame.astype(np.float64).reshape(h, f, w, f, c).mean(axis=(1, 3)).astype(np.float32)
 
 
 def synthetic_background(width=1024, height=512, seed=0x5EED, stars=None):

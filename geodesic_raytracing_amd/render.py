@@ -1,6 +1,7 @@
 """Headless renderer: metric script -> PNG (the role of the reference's `-start <metric>` + screenshot key).
 
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 1920x1080 --out kerr.png
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 1920x1080 --supersample 2 --out kerr_ss2.png
     python -m geodesic_raytracing_amd.render --metric alcubierre --redshift --camera 0,0,-6,0.5 --background sky.png --out warp.png
     # camera riding its own timelike geodesic: 24 frames, 0.5 units of proper time apart -> fall_000.png .. fall_023.png
     python -m geodesic_raytracing_amd.render --metric schwarzschild --camera 0,0,-8,0 --geodesic-speed 0,0.3,0 \
@@ -35,15 +36,16 @@ def write_frame_png(path, frame):
 
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
-           parallel_transport=True):
+           parallel_transport=True, supersample=1):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
-    main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path)."""
+    main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
+    at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24)."""
     metric = gra.Metric(metric_name, scripts or os.path.join(HERE, "scripts"))
     feats = metric.features(adaptive_sampling=int(adaptive), redshift=int(redshift), field_of_view=fov, universe_size=universe)
     cfg_values = metric.cfg_values(**(cfg or {}))
     manager = ProgramManager(metric, device, feats, cfg_values)
     program = manager.current(wait=wait_for_static)
-    state = gra.RenderState(width, height, device)
+    state = gra.RenderState(width, height, device, supersample=supersample)
     rgba = background if background is not None else gra.synthetic_background(2048, 1024)
     packed, levels = gra.pack_background(rgba)
     dbg = DeviceBuffer.from_numpy(device, packed)
@@ -89,6 +91,8 @@ def main(argv=None):
     ap.add_argument("--geodesic-dt", type=float, default=0.5, help="proper time between frames")
     ap.add_argument("--frames", type=int, default=1)
     ap.add_argument("--recompute-tetrads", action="store_true", help="rebuild the tetrad at every point instead of parallel transport")
+    ap.add_argument("--supersample", type=int, choices=[1, 2, 3, 4], default=1, help="anti-aliasing: trace N x N rays per pixel of --size and "
+                    "average them on the device (the output keeps the size given by --size)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
@@ -99,7 +103,7 @@ def main(argv=None):
     result = render(a.metric, w, h, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
                     [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, a.adaptive,
                     read_png(a.background) if a.background else None, a.device, a.fov, a.universe, geodesic_speed=speed,
-                    geodesic_times=times, parallel_transport=not a.recompute_tetrads)
+                    geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample)
     if speed is None:
         write_frame_png(a.out, result)
         print(f"wrote {a.out} ({w}x{h})")

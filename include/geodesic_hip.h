@@ -246,10 +246,11 @@ typedef struct gr_frame_options {
 void gr_frame_options_default(gr_frame_options* out);
 
 int gr_render_state_create(int device, int width, int height, gr_render_state** out);
+int gr_render_state_create_supersampled(int device, int width, int height, int factor, gr_render_state** out);   /* frames of this state are traced at factor x per axis (graphics_settings.hpp:23-24) and box-averaged into out */
 void gr_render_state_destroy(gr_render_state* s);
 
-/* Renders one frame into out_rgba_f32 (float4[width*height], device memory; in fused strip mode only
- * rows [row_begin,row_end) are written).  cfg_values = the $cfg parameters (NULL = metric defaults). */
+/* Renders one frame into out_rgba_f32 (device memory, always float4[width*height] of the state's constructor, supersampled or not; in
+ * fused strip mode only this device's rows are written).  cfg_values = the $cfg parameters (NULL = metric defaults). */
 int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features*
                     features, const float* cfg_values, int num_cfg_values, const void* background1, const void* background2, int
                     bg_width, int bg_height, int bg_levels, void* out_rgba_f32, const gr_frame_options* options);

@@ -75,6 +75,13 @@ enum { GR_BUF_RAYS_IN = 0, GR_BUF_RAYS_COUNT = 1, GR_BUF_RENDER_DATA = 2, GR_BUF
  * camera set-up and prepass whatever gr_frame_tuning.reuse_still_camera says.  That holds for the NEXT frame only - a caller that keeps such
  * a pointer and writes through it in later frames renders those with reuse_still_camera = 0. */
 void* gr_render_state_buffer(gr_render_state* s, int which);
+/* A state made by gr_render_state_create_supersampled works at the TRACED size throughout - prepass, adaptive sampling, look-ahead, tile
+ * history, both modes - and gr_render_state_buffer hands out its traced-size buffers (records of traced_width x traced_height pixels).
+ * _supersample: the factor (1 for gr_render_state_create) and that size; any output may be NULL.  _resolve_ms: elapsed milliseconds of
+ * the resolve launch of the last frame rendered with time_kernels = 1 (0 when it launched none); it has an event pair of its own
+ * beside the GR_STAGE_* ones, whose GR_STAGE_RENDER covers the shading of the traced frame. */
+int gr_render_state_supersample(const gr_render_state* s, int* factor, int* traced_width, int* traced_height);
+int gr_render_state_resolve_ms(gr_render_state* s, float* ms);
 
 /* counters of a program manager: out[0] parameter changes taken (gr_program_manager_update), [1] substituted programs swapped in, [2] substituted
  * builds started - never more than one of them is running -, [3] 1 while a build is running whose result nobody wants any more */
@@ -109,6 +116,13 @@ int gr_render_strips(gr_program* p, void* stream, const void* render_data, void*
                      int max_probes, const void* cfg, const void* dfg);
 /* number of row blocks device `strip_rank` owns */
 int gr_strip_local_blocks(int height, int block_rows, int strip_rank, int strip_count);
+/* The box filter of a supersampled frame (kernels/resolve.hip, built into the set-up module: IEEE arithmetic): every float4 of dst
+ * (width x height) is the sum of the factor x factor block of src (width*factor x height*factor) behind it, times 1.0f / factor^2, in
+ * fp32; factor 1..4, 1 copies.  Rows as in gr_render_strips (strip_count <= 1: the whole image): with compact_out BOTH src and dst hold
+ * the device's blocks back to back (a traced block is factor * block_rows rows), without it both are indexed by global row and only
+ * this device's rows are read and written. */
+int gr_resolve_supersampled(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int block_rows,
+                            int strip_rank, int strip_count, int compact_out);
 
 /* ---- fused MI355X path (no reference counterpart) ------------------------------------------- */
 
