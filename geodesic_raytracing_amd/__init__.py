@@ -236,10 +236,15 @@ _SIGNATURES = {
     "gr_render_state_supersample": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "gr_render_state_resolve_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     "gr_resolve_supersampled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "gr_present_rgba8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "gr_srgb8_thresholds": (c_int, [ctypes.POINTER(c_float)]),
     "gr_render_state_destroy": (None, [c_void_p]),
     "gr_render_frame": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
                                 ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                 ctypes.POINTER(FrameOptions)]),
+    "gr_render_frame_rgba8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
+                                      ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                      ctypes.POINTER(FrameOptions)]),
     "gr_geodesic_camera_create": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p)]),
     "gr_geodesic_camera_destroy": (None, [c_void_p]),
     "gr_geodesic_camera_snapshot": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(c_float),
@@ -280,6 +285,9 @@ _SIGNATURES = {
     "gr_device_alloc": (c_int, [c_int, c_size_t, ctypes.POINTER(c_void_p)]),
     "gr_device_free": (c_int, [c_int, c_void_p]),
     "gr_device_synchronize": (c_int, [c_int]),
+    "gr_host_alloc": (c_int, [c_size_t, ctypes.POINTER(c_void_p)]),
+    "gr_host_free": (c_int, [c_void_p]),
+    "gr_device_download_async": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "gr_stream_create": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p)]),
     "gr_stream_synchronize": (c_int, [c_void_p]),
     "gr_stream_destroy": (c_int, [c_void_p]),
@@ -309,5 +317,5 @@ def check(rc):
         raise GeodesicError(f"libgeodesic_hip error {rc}: {msg.decode(errors='replace') if msg else ''}")
 
 
-from .pipeline import (GeodesicCamera, Metric, Program, RenderState, TiledFrame, box_resolve, default_camera, default_features,  # noqa: E402,F401
-                       frame_options, synthetic_background, pack_background)
+from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, default_camera,  # noqa: E402,F401
+                       default_features, encode_srgb8, frame_options, synthetic_background, pack_background)

@@ -14,6 +14,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <algorithm>
 #include <atomic>
@@ -96,18 +97,19 @@ const char* const KERNEL_NAMES[] = {
     "gr_cart_to_generic", "gr_init_basis_vectors", "gr_clear_termination_buffer", "gr_init_rays_generic",
     "gr_do_generic_rays", "gr_calculate_singularities", "gr_calculate_render_data",
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
-    "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled"};
+    "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_COUNT
 };
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
-// filter of a supersampled frame (kernels/resolve.hip), which wants the same arithmetic and no part in the ray kernels' compilation
+// filter of a supersampled frame (kernels/resolve.hip) and its 8-bit sRGB encode (kernels/present.hip), which want the same arithmetic
+// and no part in the ray kernels' compilation
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
-           k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED;
+           k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8;
 }
 
 std::vector<std::string> split_arguments(const std::string& s) {
@@ -556,8 +558,30 @@ int compile_code_object(const std::string& argument_string, std::string& code, s
 // The set-up module of a program: the kernels that run once per frame on one lane - camera coordinates, tetrad, the camera's own
 // geodesic - from program + probes + metric + setup + camera + geodesic_camera, built with IEEE arithmetic (kernels/camera.hip says
 // why).  Same macro string, a cache file of its own; no pass over the code, no occupancy rule: nothing here is issue-bound.
+// The table kernels/present.hip searches, as source text: gr_srgb8_thresholds' T[1 ... 255] (imageio.cpp - the host encode inverted with
+// the host's own powf) as bit patterns, in the breadth-first order of the perfect search tree over them (node i: children 2i and 2i + 1;
+// entry 0 unused).  Part of the set-up module's source, so of its cache key: a host whose libm rounds differently builds its own.
+const std::string& srgb8_tree_source() {
+    static const std::string text = [] {
+        float sorted[256];
+        uint32_t tree[256] = {};
+        (void)gr_srgb8_thresholds(sorted);
+        for (int level = 0; level < 8; level++)   // entry j of level l is the (2 j + 1) 2^(7 - l)-th threshold in sorted order
+            for (int j = 0; j < (1 << level); j++) memcpy(&tree[(1 << level) + j], &sorted[(2 * j + 1) << (7 - level)], sizeof(uint32_t));
+        std::string t = "__device__ const unsigned int GR_SRGB8_TREE_BITS[256] = {";
+        char word[32];
+        for (int i = 0; i < 256; i++) {
+            snprintf(word, sizeof(word), "%s0x%08xu", i ? (i % 8 ? ", " : ",\n    ") : "\n    ", tree[i]);
+            t += word;
+        }
+        return t + "};\n";
+    }();
+    return text;
+}
+
 int compile_setup_module(const std::string& argument_string, std::string& code, bool cache_only) {
-    static const char* const PARTS[] = {"program.hip", "probes.inc", "metric.hip", "setup.hip", "camera.hip", "geodesic_camera.hip", "resolve.hip"};
+    static const char* const PARTS[] = {"program.hip", "probes.inc", "metric.hip", "setup.hip", "camera.hip", "geodesic_camera.hip", "resolve.hip",
+                                        "present.hip"};
     std::string source;
     // GR_SETUP_KERNEL_SOURCE: one file instead of the parts, as GR_KERNEL_SOURCE is for the ray kernels' module.  (GR_KERNEL_SOURCE
     // alone replaces the ray kernels only - the tools that use it patch the trace kernel - and this module is then built from the
@@ -579,6 +603,7 @@ int compile_setup_module(const std::string& argument_string, std::string& code, 
             if (!text.empty() && text.back() != '\n') source += '\n';
         }
     }
+    source = srgb8_tree_source() + source;
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-math-errno", "-fno-slp-vectorize",
                                      "-fhip-fp32-correctly-rounded-divide-sqrt", "-DGR_SETUP_MODULE", "-DGR_LIBM_TRIG", "-DGR_LIBM_TANH"};
     for (auto& tok : split_arguments(argument_string)) {
@@ -1478,6 +1503,20 @@ int gr_resolve_supersampled(gr_program* p, void* stream, const void* src, void* 
     int local_rows = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_rows;
     void* args[] = {&src, &dst, &width, &height, &factor, &block_rows, &strip_rank, &strip_count, &compact_out, &local_rows};
     return launch(p, K_RESOLVE_SUPERSAMPLED, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
+}
+
+// gr_resolve_supersampled fused with the 8-bit sRGB encode (kernels/present.hip): the same grid, the same row dealing, one uint32 a pixel
+int gr_present_rgba8(gr_program* p, void* stream, const void* src, void* dst_rgba8, int width, int height, int factor, int block_rows,
+                     int strip_rank, int strip_count, int compact_out) {
+    GR_NEED("gr_present_rgba8", src, dst_rgba8);
+    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_present_rgba8: factor " + std::to_string(factor) + " (1 to 4)");
+    if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
+        return fail(GR_ERROR_INVALID_ARGUMENT, "gr_present_rgba8: the frame's size");
+    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = height; }
+    if (block_rows <= 0 || strip_rank < 0 || strip_rank >= strip_count) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_present_rgba8: bad strip parameters");
+    int local_rows = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_rows;
+    void* args[] = {&src, &dst_rgba8, &width, &height, &factor, &block_rows, &strip_rank, &strip_count, &compact_out, &local_rows};
+    return launch(p, K_PRESENT_RGBA8, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
 }
 
 int gr_internal_fail(int code, const char* msg) { return fail((gr_status)code, msg ? msg : ""); }

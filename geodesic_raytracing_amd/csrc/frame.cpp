@@ -79,7 +79,8 @@ struct gr_render_state {
     int device = 0;
     int width = 0, height = 0;      // what every frame of the state is traced and shaded at
     // gr_render_state_create_supersampled: width x height above are supersample x the caller's frame per axis; a frame is shaded into
-    // traced_frame (float4[width * height], NULL for factor 1) and box-averaged from there into the caller's out (gr_resolve_supersampled)
+    // traced_frame (float4[width * height], NULL for factor 1) and box-averaged from there into the caller's out (gr_resolve_supersampled).
+    // gr_render_frame_rgba8 shades into it at every factor: a factor-1 state gets one, and the events, with its first 8-bit frame.
     int supersample = 1;
     int out_width = 0, out_height = 0;
     void* traced_frame = nullptr;
@@ -490,6 +491,20 @@ int gr_device_synchronize(int device) {
     HIP_CHECK(hipDeviceSynchronize());
     return GR_OK;
 }
+int gr_host_alloc(size_t bytes, void** out) {
+    if (!out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
+    HIP_CHECK(hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault));
+    return GR_OK;
+}
+int gr_host_free(void* ptr) {
+    if (ptr) HIP_CHECK(hipHostFree(ptr));
+    return GR_OK;
+}
+int gr_device_download_async(void* stream, void* host_dst, const void* device_src, size_t bytes) {
+    if (!host_dst || !device_src) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
+    HIP_CHECK(hipMemcpyAsync(host_dst, device_src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return GR_OK;
+}
 
 // a state whose frames are out_width x out_height and are traced at factor x that per axis (1: gr_render_state_create)
 static int create_render_state(int device, int out_width, int out_height, int factor, gr_render_state** out) {
@@ -866,15 +881,22 @@ void* gr_geodesic_camera_buffer(gr_geodesic_camera* g, int which) {
 
 // one frame at the state's traced size: out is float4[s->width * s->height] (gr_render_frame below for a state of factor 1, and what a
 // supersampled state shades into its own traced frame)
-static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream_v, const gr_camera* camera,
-                               const gr_features* features_in, const float* cfg_values, int num_cfg_values, const void* bg1,
-                               const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* opt_in) {
+// What a frame refuses before any HIP call (render_traced_frame, and gr_render_frame_rgba8 before it allocates for a factor-1 state).
+static int check_frame_arguments(const gr_render_state* s, const gr_program* p, const gr_metric* m, const gr_camera* camera, const float* cfg_values,
+                                 int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height, int bg_levels, const void* out) {
     if (!s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
     // a frame that is to be shaded needs both skies and their shape (the texture pass reads them unchecked: a NULL sky is a device fault,
     // not an error code - tests/test_gpu_lifecycle.py found it); out == NULL stops after the render-data
     if (out && (!bg1 || !bg2 || bg_width <= 0 || bg_height <= 0 || bg_levels <= 0))
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame: an output frame needs both background textures and their width, height and levels");
     if (num_cfg_values < 0 || (num_cfg_values > 0 && !cfg_values)) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame: cfg_values");
+    return GR_OK;
+}
+
+static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream_v, const gr_camera* camera,
+                               const gr_features* features_in, const float* cfg_values, int num_cfg_values, const void* bg1,
+                               const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* opt_in) {
+    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out));
     hipStream_t stream = (hipStream_t)stream_v;
     HIP_CHECK(hipSetDevice(s->device));
     gr_frame_options opt;
@@ -1570,6 +1592,41 @@ int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void*
     if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
     GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, strips ? block_rows : s->out_height,
                                      strips ? opt.strip_rank : 0, strips ? opt.strip_count : 1, strips ? opt.compact_out : 0));
+    if (timed) {
+        HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
+        s->resolve_timed = true;
+    }
+    return GR_OK;
+}
+
+// The frame as gr_render_frame renders it, at the traced size, into the state's own traced frame (at factor 1 too: the encode reads
+// float4 and the caller has only bytes), and one gr_present_rgba8 launch from there into the caller's out_rgba8 - resolve and encode in
+// one pass, no w x h float4 in between.
+int gr_render_frame_rgba8(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
+                          const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height,
+                          int bg_levels, void* out_rgba8, const gr_frame_options* options) {
+    if (!s || !out_rgba8) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_rgba8: null argument");
+    s->resolve_timed = false;
+    gr_frame_options opt;
+    gr_frame_options_default(&opt);
+    if (options) opt = *options;
+    const int factor = s->supersample, block_rows = opt.block_rows;
+    if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_rgba8: block_rows");
+    opt.block_rows *= factor;
+    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out_rgba8));
+    if (!s->traced_frame) {   // a factor-1 state's first 8-bit frame (nothing is allocated for a call that is refused)
+        HIP_CHECK(hipSetDevice(s->device));
+        HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
+        for (auto& ev : s->ev_resolve)
+            if (!ev) HIP_CHECK(hipEventCreate(&ev));
+    }
+    GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
+                                 s->traced_frame, &opt));
+    const bool strips = opt.mode == GR_MODE_FUSED && opt.strip_count > 1;
+    const bool timed = opt.time_kernels == 1;
+    if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
+    GR_CHECK(gr_present_rgba8(p, stream, s->traced_frame, out_rgba8, s->out_width, s->out_height, factor, strips ? block_rows : s->out_height,
+                              strips ? opt.strip_rank : 0, strips ? opt.strip_count : 1, strips ? opt.compact_out : 0));
     if (timed) {
         HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
         s->resolve_timed = true;

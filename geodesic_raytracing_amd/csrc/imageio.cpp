@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/geodesic_hip.h"
+#include "../../include/geodesic_hip_internal.h"
 
 extern "C" int gr_internal_fail(int code, const char* msg);
 
@@ -34,6 +34,15 @@ void chunk(std::vector<uint8_t>& out, const char* type, const std::vector<uint8_
 // lin_to_srgb_single, cl.cl:326-332 (the host applies the same curve, main.cpp:2797)
 float lin_to_srgb(float v) { return v <= 0.0031308f ? v * 12.92f : 1.055f * std::pow(v, 1.0f / 2.4f) - 0.055f; }
 float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
+
+// The 8-bit encode of one value, stated once (main.cpp:2791-2796): clamp, linear -> sRGB, clamp, * 255 truncated.  gr_frame_to_rgba8
+// applies it to a frame; gr_srgb8_thresholds inverts it into the table the device encode (kernels/present.hip) searches.  A NaN passes
+// both clamps and its cast is undefined.
+unsigned char srgb8(float v) {
+    const float c = clamp01(v);
+    const float s = clamp01(lin_to_srgb(c));
+    return (unsigned char)(s * 255.f);
+}
 
 uint32_t get32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
@@ -72,13 +81,32 @@ int gr_write_png_rgba8(const char* path, const unsigned char* rgba, int width, i
     return GR_OK;
 }
 
-// the screenshot conversion of main.cpp:2791-2800: clamp, linear -> sRGB (all four channels), clamp, * 255 truncated
+// the screenshot conversion of main.cpp:2791-2800: clamp, linear -> sRGB (all four channels), clamp, * 255 truncated.  The byte of a
+// NaN is undefined here (the device encode, gr_present_rgba8, writes 0 for it).
 int gr_frame_to_rgba8(const float* frame_rgba_f32, int width, int height, unsigned char* out_rgba8) {
     if (!frame_rgba_f32 || !out_rgba8) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
     size_t n = (size_t)width * height * 4;
-    for (size_t i = 0; i < n; i++) {
-        float v = clamp01(lin_to_srgb(clamp01(frame_rgba_f32[i])));
-        out_rgba8[i] = (unsigned char)(v * 255.f);
+    for (size_t i = 0; i < n; i++) out_rgba8[i] = srgb8(frame_rgba_f32[i]);
+    return GR_OK;
+}
+
+// out[k] = the smallest float of [0, 1] whose byte is >= k (+infinity where none is: 1.055f - 0.055f need not be 1), found by bisection
+// over the bit patterns 0 ... 0x3f800000 with srgb8 itself - which is monotone there (tests/test_present_abi.py checks it against
+// this library's own powf).  byte(c) is then the largest k with out[k] <= c, whatever libm is underneath.
+int gr_srgb8_thresholds(float out[256]) {
+    if (!out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
+    auto of_bits = [](uint32_t bits) { float f; memcpy(&f, &bits, sizeof(f)); return f; };
+    const uint32_t one = 0x3f800000u;
+    const int top = srgb8(of_bits(one));
+    out[0] = 0.f;
+    for (int k = 1; k < 256; k++) {
+        if (k > top) { out[k] = INFINITY; continue; }
+        uint32_t lo = 0, hi = one;   // byte(lo) < k <= byte(hi)
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (srgb8(of_bits(mid)) >= k) hi = mid; else lo = mid;
+        }
+        out[k] = of_bits(hi);
     }
     return GR_OK;
 }

@@ -329,6 +329,39 @@ def download(device, ptr, dtype, count):
     return out
 
 
+class PinnedBuffer:
+    """Page-locked host memory (gr_host_alloc) that a device copy lands in without staging: download_async enqueues the copy on a
+    stream, and view() is valid once that stream has been synchronised."""
+
+    def __init__(self, nbytes):
+        self.nbytes = int(nbytes)
+        self.ptr = c_void_p()
+        check(lib.gr_host_alloc(self.nbytes, ctypes.byref(self.ptr)))
+
+    def view(self, dtype=np.uint8, shape=None):
+        """a numpy array over the buffer (no copy; it must not outlive the buffer)"""
+        arr = np.frombuffer((ctypes.c_ubyte * self.nbytes).from_address(self.ptr.value), dtype=dtype)
+        return arr if shape is None else arr[:int(np.prod(shape))].reshape(shape)
+
+    def download_async(self, stream, device_ptr, nbytes=None):
+        nbytes = self.nbytes if nbytes is None else int(nbytes)
+        if nbytes > self.nbytes:
+            raise ValueError(f"PinnedBuffer: {nbytes} bytes asked for, {self.nbytes} allocated")
+        check(lib.gr_device_download_async(stream, self.ptr, device_ptr, nbytes))
+
+    def free(self):
+        """releases the memory (views of it are dead from here on); raises if the library refuses"""
+        ptr, self.ptr = getattr(self, "ptr", None), None
+        if ptr:
+            check(lib.gr_host_free(ptr))
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:   # (a destructor has nobody to raise to; free() called by hand does raise)
+            pass
+
+
 class RenderState:
     """Per-frame device buffers + the frame sequence (render_state.hpp:97-197, main.cpp:2244-2526)."""
 
@@ -351,7 +384,7 @@ class RenderState:
             lib.gr_render_state_destroy(self.handle)
             self.handle = None
 
-    def render(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None):
+    def render(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None, rgba8=False):
         """Enqueue one frame. `out_ptr`: device pointer to float4[width*height] (or None to stop after render-data);
         `background`: (device_ptr, width, height, levels) or ((ptr1, ptr2), width, height, levels)."""
         arr, n = None, 0
@@ -365,9 +398,14 @@ class RenderState:
             bg1, bg2 = ptrs if isinstance(ptrs, tuple) else (ptrs, ptrs)
         if features is None:
             features = metric.features()
-        check(lib.gr_render_frame(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera),
-                                  ctypes.byref(features), arr, n, bg1, bg2, bw, bh, bl, out_ptr,
-                                  ctypes.byref(options) if options is not None else None))
+        entry = lib.gr_render_frame_rgba8 if rgba8 else lib.gr_render_frame
+        check(entry(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n, bg1, bg2, bw, bh, bl,
+                    out_ptr, ctypes.byref(options) if options is not None else None))
+
+    def render_rgba8(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None):
+        """render(), delivered as 8-bit sRGB (gr_render_frame_rgba8): `out_ptr` is a device pointer to width*height*4 bytes, R G B A, rows
+        laid out as render() lays out its float rows; every byte is encode_srgb8's of the float render() writes (a NaN gives 0)."""
+        self.render(program, metric, camera, out_ptr, background, features, cfg_values, options, stream, rgba8=True)
 
     def prepass_policy(self):
         """(frames rendered with a prepass, frames the policy rendered without, fraction of cells the last inspected prepass marked)"""
@@ -488,6 +526,19 @@ def box_resolve(frame, factor):
         raise ValueError(f"box_resolve: a frame of shape {frame.shape} does not divide into {f} x {f} blocks")
     h, w, c = frame.shape[0] // f, frame.shape[1] // f, frame.shape[2]
     return frame.astype(np.float64).reshape(h, f, w, f, c).mean(axis=(1, 3)).astype(np.float32)
+
+
+def encode_srgb8(frame):
+    """The host statement of the 8-bit encode (gr_frame_to_rgba8, the reference's screenshot loop main.cpp:2791-2796): float [H, W, 4] in
+    linear light -> uint8 [H, W, 4], every value clamped to [0, 1], through lin_to_srgb, clamped, times 255 and truncated.  What
+    gr_present_rgba8 computes on the device (a NaN is undefined here and 0 there)."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.ndim != 3 or frame.shape[2] != 4:
+        raise ValueError(f"encode_srgb8: a frame of shape {frame.shape} is not [H, W, 4]")
+    out = np.empty(frame.shape, dtype=np.uint8)
+    if frame.size:
+        check(lib.gr_frame_to_rgba8(frame.ctypes.data_as(c_void_p), frame.shape[1], frame.shape[0], out.ctypes.data_as(c_void_p)))
+    return out
 
 
 def synthetic_background(width=1024, height=512, seed=0x5EED, stars=None):

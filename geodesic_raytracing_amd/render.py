@@ -2,6 +2,7 @@
 
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 1920x1080 --out kerr.png
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 1920x1080 --supersample 2 --out kerr_ss2.png
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --encode device --out kerr_4k.png
     python -m geodesic_raytracing_amd.render --metric alcubierre --redshift --camera 0,0,-6,0.5 --background sky.png --out warp.png
     # camera riding its own timelike geodesic: 24 frames, 0.5 units of proper time apart -> fall_000.png .. fall_023.png
     python -m geodesic_raytracing_amd.render --metric schwarzschild --camera 0,0,-8,0 --geodesic-speed 0,0.3,0 \
@@ -15,7 +16,7 @@ import sys
 import numpy as np
 
 import geodesic_raytracing_amd as gra
-from geodesic_raytracing_amd.pipeline import DeviceBuffer, ProgramManager
+from geodesic_raytracing_amd.pipeline import DeviceBuffer, PinnedBuffer, ProgramManager
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -34,12 +35,21 @@ def write_frame_png(path, frame):
     gra.check(gra.lib.gr_write_frame_png(path.encode(), frame.ctypes.data_as(ctypes.c_void_p), w, h))
 
 
+def write_rgba8_png(path, pixels):
+    """a frame that is 8-bit sRGB already (render(..., rgba8=True)): written as it is"""
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+    h, w = pixels.shape[:2]
+    gra.check(gra.lib.gr_write_png_rgba8(path.encode(), pixels.ctypes.data_as(ctypes.c_void_p), w, h))
+
+
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
-           parallel_transport=True, supersample=1):
+           parallel_transport=True, supersample=1, rgba8=False):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
-    at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24)."""
+    at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
+    rgba8: the frames are uint8 [H, W, 4] in sRGB instead, encoded on the device (RenderState.render_rgba8) and fetched at 4 bytes a
+    pixel through pinned memory - the bytes pipeline.encode_srgb8 makes of the float frame."""
     metric = gra.Metric(metric_name, scripts or os.path.join(HERE, "scripts"))
     feats = metric.features(adaptive_sampling=int(adaptive), redshift=int(redshift), field_of_view=fov, universe_size=universe)
     cfg_values = metric.cfg_values(**(cfg or {}))
@@ -49,27 +59,42 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     rgba = background if background is not None else gra.synthetic_background(2048, 1024)
     packed, levels = gra.pack_background(rgba)
     dbg = DeviceBuffer.from_numpy(device, packed)
-    out = DeviceBuffer(device, width * height * 16)
+    out = DeviceBuffer(device, width * height * (4 if rgba8 else 16))
+    pinned = PinnedBuffer(width * height * 4) if rgba8 else None
     cam = gra.default_camera(camera_pos, camera_quat)
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
     bg = (dbg.ptr, packed.shape[2], packed.shape[1], levels)
-    if geodesic_speed is None:
-        state.render(program, metric, cam, out.ptr, bg, feats, cfg_values, gra.frame_options(mode=mode))
-        state.synchronize()
-        return out.to_numpy(np.float32, (height, width, 4))
-    gc = gra.GeodesicCamera(device=device)
-    steps, tau = gc.snapshot(program, metric, cam, geodesic_speed, feats, cfg_values)
-    print(f"geodesic snapshot: {steps} samples covering {tau:.3f} of proper time", file=sys.stderr)
-    times = list(geodesic_times or [0.0])
-    frames = []
-    for i, t in enumerate(times):
-        ahead = i + 1 < len(times) and mode == gra.MODE_FUSED
-        opts = gra.frame_options(mode=mode, geodesic=gc.handle.value, geodesic_time=t, parallel_transport_observer=int(parallel_transport),
-                                 next_camera=ctypes.pointer(cam) if ahead else None, next_geodesic_time=times[i + 1] if ahead else 0.0)
-        state.render(program, metric, cam, out.ptr, bg, feats, cfg_values, opts)
-        state.synchronize()
-        frames.append(out.to_numpy(np.float32, (height, width, 4)))
-    return frames
+
+    def one_frame(options):
+        if not rgba8:
+            state.render(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
+            state.synchronize()
+            return out.to_numpy(np.float32, (height, width, 4))
+        state.render_rgba8(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
+        pinned.download_async(None, out.ptr, width * height * 4)   # the frame's stream: copies queue behind its launches
+        gra.check(gra.lib.gr_stream_synchronize(None))
+        return pinned.view(np.uint8, (height, width, 4)).copy()
+
+    def frames_of_the_call():
+        if geodesic_speed is None:
+            return one_frame(gra.frame_options(mode=mode))
+        gc = gra.GeodesicCamera(device=device)
+        steps, tau = gc.snapshot(program, metric, cam, geodesic_speed, feats, cfg_values)
+        print(f"geodesic snapshot: {steps} samples covering {tau:.3f} of proper time", file=sys.stderr)
+        times = list(geodesic_times or [0.0])
+        frames = []
+        for i, t in enumerate(times):
+            ahead = i + 1 < len(times) and mode == gra.MODE_FUSED
+            opts = gra.frame_options(mode=mode, geodesic=gc.handle.value, geodesic_time=t, parallel_transport_observer=int(parallel_transport),
+                                     next_camera=ctypes.pointer(cam) if ahead else None, next_geodesic_time=times[i + 1] if ahead else 0.0)
+            frames.append(one_frame(opts))
+        return frames
+
+    try:
+        return frames_of_the_call()
+    finally:
+        if pinned is not None:   # every frame was copied out of it
+            pinned.free()
 
 
 def main(argv=None):
@@ -93,6 +118,8 @@ def main(argv=None):
     ap.add_argument("--recompute-tetrads", action="store_true", help="rebuild the tetrad at every point instead of parallel transport")
     ap.add_argument("--supersample", type=int, choices=[1, 2, 3, 4], default=1, help="anti-aliasing: trace N x N rays per pixel of --size and "
                     "average them on the device (the output keeps the size given by --size)")
+    ap.add_argument("--encode", choices=["host", "device"], default="host", help="where the frame becomes 8-bit sRGB: host = download float4 and "
+                    "convert there; device = encode on the GPU and download 4 bytes a pixel (the same bytes)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
@@ -103,15 +130,16 @@ def main(argv=None):
     result = render(a.metric, w, h, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
                     [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, a.adaptive,
                     read_png(a.background) if a.background else None, a.device, a.fov, a.universe, geodesic_speed=speed,
-                    geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample)
+                    geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample, rgba8=a.encode == "device")
+    write = write_rgba8_png if a.encode == "device" else write_frame_png
     if speed is None:
-        write_frame_png(a.out, result)
+        write(a.out, result)
         print(f"wrote {a.out} ({w}x{h})")
         return 0
     stem, ext = os.path.splitext(a.out)
     for i, frame in enumerate(result):
         path = a.out if len(result) == 1 else f"{stem}_{i:03d}{ext}"
-        write_frame_png(path, frame)
+        write(path, frame)
         print(f"wrote {path} ({w}x{h}, proper time {times[i]:.3f})")
     return 0
 

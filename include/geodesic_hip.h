@@ -3,10 +3,9 @@
  *   (1) the compile-time macro string: metrics::build_argument_string (metric.hpp:725-959) + dynamic_feature_config::generate_{dynamic,
  *       static}_argument_string (dynamic_feature_config.cpp:122-180), consumed by cl::build_program_with_cache (metric_manager.hpp:88-108);
  *   (2) launches by kernel name: cl::command_queue::exec(name, args, global, local), main.cpp:203, 2311, 2329, 2396 ... 2525.
- * Every entry point replaces one of those and cites it.  Device buffers are plain device pointers owned by the caller (the reference's
- * cl::buffer ownership, render_state.hpp:172-196); kernels never allocate.  `stream` is a hipStream_t passed as void* (NULL = default
- * stream); launches are asynchronous on it, like the reference's in-order queue (main.cpp:1460).  Every function returns 0 on success
- * and a negative gr_status otherwise; gr_last_error() returns a thread-local message.
+ * Every entry point replaces one of those and cites it.  Device buffers are device pointers owned by the caller (cl::buffer ownership,
+ * render_state.hpp:172-196); kernels never allocate.  `stream` is a hipStream_t as void* (NULL = default stream); launches on it are
+ * asynchronous, like the reference's in-order queue (main.cpp:1460).  Returns 0 or a negative gr_status; gr_last_error(): this thread's message.
  * This header is the CONTRACT: layouts, metric -> macro string, program, one launcher per reference kernel, the frame driver, one frame
  * over several GPUs, image helpers.  The fused MI355X launchers, their schedules and every measurement hook: geodesic_hip_internal.h. */
 #ifndef GEODESIC_HIP_H
@@ -44,9 +43,8 @@ typedef struct gr_render_data {
     int sx, sy, terminated, side, pad_;
 } gr_render_data;
 
-/* struct dynamic_feature_config as packed by dynamic_feature_config::alloc_and_write_gpu_buffer
- * (dynamic_feature_config.cpp:182-237): floats in alphabetical order, then bools as int. 48 bytes.
- * Defaults: main.cpp:1123-1158. */
+/* struct dynamic_feature_config as packed by dynamic_feature_config::alloc_and_write_gpu_buffer (dynamic_feature_config.cpp:182-237):
+ * floats in alphabetical order, then bools as int. 48 bytes.  Defaults: main.cpp:1123-1158. */
 typedef struct gr_features {
     float adaptive_sampling_threshold, field_of_view, max_acceleration_change, max_precision_radius, min_step, ray_skip, universe_size;
     int adaptive_sampling, redshift, reparameterisation, use_old_redshift, use_triangle_rendering;
@@ -170,9 +168,8 @@ int gr_handle_adaptive_sampling(gr_program* p, void* stream, const void* rays, c
 int gr_render(gr_program* p, void* stream, const void* render_data, const void* render_data_count, int num_pixels, void*
               out_rgba_f32, const void* background1, const void* background2, int bg_width, int bg_height, int bg_levels, int width,
               int height, int max_probes, const void* cfg, const void* dfg);
-/* ---- camera riding a timelike geodesic (the snapshot sequence of main.cpp:2675-2760 and the
- *      per-frame interpolation of main.cpp:2265-2297).  Path buffers are step-major: element k of observer id is at
- *      [k*count + id].  basis_speed buffers hold float4 per observer (the reference's float3 has the same 16-byte stride). */
+/* ---- camera riding a timelike geodesic (snapshot sequence main.cpp:2675-2760, per-frame interpolation :2265-2297).
+ *      Path buffers are step-major: element k of observer id is at [k*count + id]; basis_speed buffers hold float4 per observer. */
 
 /* boost_tetrad, cl.cl:2441-2481; main.cpp:2700 */
 int gr_boost_tetrad(gr_program* p, void* stream, const void* generic_in, int count, const void* basis_speed, void* e0_io, void*
@@ -215,8 +212,7 @@ enum {
     GR_MODE_FUSED = 1        /* gr_prepass_fused + gr_trace_fused + gr_render */
 };
 
-/* Snapshot of the camera's own timelike geodesic, resident on the device: the buffers of main.cpp:1232-1242
- * (geodesic_trace / vel / ds / count) and the four parallel-transported tetrad legs. */
+/* The camera's own timelike geodesic on the device: the buffers of main.cpp:1232-1242 and the four parallel-transported tetrad legs */
 typedef struct gr_geodesic_camera gr_geodesic_camera;
 
 typedef struct gr_frame_tuning gr_frame_tuning;   /* geodesic_hip_internal.h: which fused kernel, schedule and launch size (defaults are right) */
@@ -254,6 +250,11 @@ void gr_render_state_destroy(gr_render_state* s);
 int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features*
                     features, const float* cfg_values, int num_cfg_values, const void* background1, const void* background2, int
                     bg_width, int bg_height, int bg_levels, void* out_rgba_f32, const gr_frame_options* options);
+/* The same frame as 8-bit sRGB, encoded on the device: rendered as above into a frame the state owns, resolved and encoded by one more
+ * launch.  out_rgba8: device memory, width*height*4 bytes (R G B A), rows as above; gr_frame_to_rgba8's bytes (a NaN channel gives 0). */
+int gr_render_frame_rgba8(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features*
+                          features, const float* cfg_values, int num_cfg_values, const void* background1, const void* background2, int
+                          bg_width, int bg_height, int bg_levels, void* out_rgba8, const gr_frame_options* options);
 
 /* stage timing of a frame rendered with options->time_kernels = 1 (the reference's -bench mode times frames on the host, main.cpp:2864-2871) */
 enum { GR_STAGE_CAMERA = 0, GR_STAGE_PREPASS = 1, GR_STAGE_INIT = 2, GR_STAGE_TRACE = 3, GR_STAGE_RENDER_DATA = 4,
@@ -269,8 +270,7 @@ void gr_geodesic_camera_destroy(gr_geodesic_camera* g);
 int gr_geodesic_camera_snapshot(gr_geodesic_camera* g, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
                                 const float geodesic_basis_speed[3], const gr_features* features, const float* cfg_values, int
                                 num_cfg_values, int* steps_out, float* proper_time_out);
-/* handle_interpolating_geodesic + read-back (the reference's geodesic_q / camera_q async reads, main.cpp:2295-2296):
- * generic camera position, tetrad (4 rows of 4) and 4-velocity at `proper_time`; any output may be NULL */
+/* handle_interpolating_geodesic + read-back (main.cpp:2295-2296): position, tetrad (4 x 4), 4-velocity at `proper_time`; outputs may be NULL */
 int gr_geodesic_camera_interpolate(gr_geodesic_camera* g, gr_program* p, void* stream, float proper_time, int
                                 parallel_transport_observer, float camera_generic_out[4], float tetrad_out[16], float
                                 velocity_out[4]);
@@ -337,7 +337,7 @@ int gr_tiled_look_ahead(gr_tiled* t, int rotations);
 int gr_pack_mipped_background(const unsigned char* rgba, int width, int height, unsigned char* out);
 
 /* ---- host helpers: PNG in/out (the screenshot path main.cpp:2762-2808, the background loader graphics_settings.cpp:214-243) ---- */
-/* clamp -> linear-to-sRGB -> clamp -> 8 bit, as the reference's screenshot loop does (main.cpp:2791-2800) */
+/* clamp -> linear-to-sRGB -> clamp -> 8 bit, the reference's screenshot loop (main.cpp:2791-2800); a NaN: undefined here, 0 on the device */
 int gr_frame_to_rgba8(const float* frame_rgba_f32, int width, int height, unsigned char* out_rgba8);
 int gr_write_frame_png(const char* path, const float* frame_rgba_f32, int width, int height);
 int gr_write_png_rgba8(const char* path, const unsigned char* rgba, int width, int height);

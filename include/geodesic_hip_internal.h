@@ -123,6 +123,21 @@ int gr_strip_local_blocks(int height, int block_rows, int strip_rank, int strip_
  * this device's rows are read and written. */
 int gr_resolve_supersampled(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int block_rows,
                             int strip_rank, int strip_count, int compact_out);
+/* gr_resolve_supersampled fused with the 8-bit sRGB encode (kernels/present.hip, set-up module): dst_rgba8 holds one uint32 a pixel
+ * (width x height; bytes R, G, B, A in memory order), each byte gr_frame_to_rgba8's of the value gr_resolve_supersampled would have
+ * written - identical for every input but a NaN, whose byte is 0 here and undefined there.  Same arguments, same checks (all before
+ * any device call), same row dealing; factor 1 encodes src as it is. */
+int gr_present_rgba8(gr_program* p, void* stream, const void* src, void* dst_rgba8, int width, int height, int factor, int block_rows,
+                     int strip_rank, int strip_count, int compact_out);
+/* What defines that encode: out[k] = the smallest float of [0, 1] whose byte under gr_frame_to_rgba8 is >= k (out[0] = 0; +infinity for a
+ * k no input reaches), found by bisection with the host function itself.  byte(c) = the largest k with out[k] <= c; the device searches
+ * this table, so it agrees with the host's powf by construction.  NaN: the host conversion is undefined, the device writes 0. */
+int gr_srgb8_thresholds(float out[256]);
+/* Pinned host memory and an asynchronous download into it, for Python and tools (a C caller owns its streams and copies for itself):
+ * a frame of gr_render_frame_rgba8 is fetched with _download_async on the frame's stream and a gr_stream_synchronize. */
+int gr_host_alloc(size_t bytes, void** out);
+int gr_host_free(void* ptr);
+int gr_device_download_async(void* stream, void* host_dst, const void* device_src, size_t bytes);
 
 /* ---- fused MI355X path (no reference counterpart) ------------------------------------------- */
 
