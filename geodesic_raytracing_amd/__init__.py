@@ -238,6 +238,8 @@ _SIGNATURES = {
     "gr_resolve_supersampled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "gr_present_rgba8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "gr_srgb8_thresholds": (c_int, [ctypes.POINTER(c_float)]),
+    "gr_mipped_background_scratch_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "gr_build_mipped_background": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t]),
     "gr_render_state_destroy": (None, [c_void_p]),
     "gr_render_frame": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
                                 ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
@@ -317,5 +319,5 @@ def check(rc):
         raise GeodesicError(f"libgeodesic_hip error {rc}: {msg.decode(errors='replace') if msg else ''}")
 
 
-from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, default_camera,  # noqa: E402,F401
-                       default_features, encode_srgb8, frame_options, synthetic_background, pack_background)
+from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, build_background,  # noqa: E402,F401
+                       default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background)

@@ -97,19 +97,21 @@ const char* const KERNEL_NAMES[] = {
     "gr_cart_to_generic", "gr_init_basis_vectors", "gr_clear_termination_buffer", "gr_init_rays_generic",
     "gr_do_generic_rays", "gr_calculate_singularities", "gr_calculate_render_data",
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
-    "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8"};
+    "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
+    "gr_background_reduce", "gr_background_slices"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_COUNT
 };
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
-// filter of a supersampled frame (kernels/resolve.hip) and its 8-bit sRGB encode (kernels/present.hip), which want the same arithmetic
-// and no part in the ray kernels' compilation
+// filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB encode (kernels/present.hip) and the sky's mip slices
+// (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
-           k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8;
+           k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
+           k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES;
 }
 
 std::vector<std::string> split_arguments(const std::string& s) {
@@ -581,7 +583,7 @@ const std::string& srgb8_tree_source() {
 
 int compile_setup_module(const std::string& argument_string, std::string& code, bool cache_only) {
     static const char* const PARTS[] = {"program.hip", "probes.inc", "metric.hip", "setup.hip", "camera.hip", "geodesic_camera.hip", "resolve.hip",
-                                        "present.hip"};
+                                        "present.hip", "background.hip"};
     std::string source;
     // GR_SETUP_KERNEL_SOURCE: one file instead of the parts, as GR_KERNEL_SOURCE is for the ray kernels' module.  (GR_KERNEL_SOURCE
     // alone replaces the ray kernels only - the tools that use it patch the trace kernel - and this module is then built from the
@@ -1517,6 +1519,72 @@ int gr_present_rgba8(gr_program* p, void* stream, const void* src, void* dst_rgb
     int local_rows = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_rows;
     void* args[] = {&src, &dst_rgba8, &width, &height, &factor, &block_rows, &strip_rank, &strip_count, &compact_out, &local_rows};
     return launch(p, K_PRESENT_RGBA8, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
+}
+
+// ---- the sky's mip slices on the device (kernels/background.hip) ------------------------------------
+
+// gr_pack_mipped_background's level count (graphics_settings.cpp:164-168), in integers
+static int background_levels(int width, int height) {
+    int levels = 0;
+    for (int m = std::min(width, height); m > 0 && levels < 10; m >>= 1) levels++;
+    return levels;
+}
+
+// the float4 pyramid of levels 1 ... levels - 1, back to back
+static size_t background_scratch_bytes(int width, int height, int levels) {
+    size_t texels = 0;
+    for (int l = 1; l < levels; l++) texels += (size_t)(width >> l) * (size_t)(height >> l);
+    return texels * 4 * sizeof(float);
+}
+
+// the sizes both entry points refuse: none, or more texels than a slice may index with 31 bits / the slice writer's grid may cover
+static int background_size_check(const char* who, int width, int height) {
+    if (width <= 0 || height <= 0 || (long long)width * height > 0x7fffffffll || (long long)width * height * 10 / 4 > 0xffffff00ll)
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the image's size " + std::to_string(width) + " x " + std::to_string(height));
+    return GR_OK;
+}
+
+int gr_mipped_background_scratch_bytes(int width, int height, size_t* bytes) {
+    if (!bytes) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_mipped_background_scratch_bytes: null argument");
+    int rc = background_size_check("gr_mipped_background_scratch_bytes", width, height);
+    if (rc != GR_OK) return rc;
+    *bytes = background_scratch_bytes(width, height, background_levels(width, height));
+    return GR_OK;
+}
+
+// Everything is refused before the first HIP call.  Then: the float levels in one launch per five levels (gr_background_reduce), the
+// slices in one launch over all of them (gr_background_slices), on `stream` in that order.
+int gr_build_mipped_background(gr_program* p, void* stream, const void* rgba8, int width, int height, void* packed_out, void* scratch,
+                               size_t scratch_bytes) {
+    const char* who = "gr_build_mipped_background";
+    int rc = background_size_check(who, width, height);
+    if (rc != GR_OK) return rc;
+    const int levels = background_levels(width, height);
+    const size_t image_bytes = (size_t)width * height * 4, packed_bytes = image_bytes * levels, need_bytes = background_scratch_bytes(width, height, levels);
+    if (need_bytes) GR_NEED(who, rgba8, packed_out, scratch);
+    else GR_NEED(who, rgba8, packed_out);
+    if (scratch_bytes < need_bytes)
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": scratch of " + std::to_string(scratch_bytes) + " bytes, " + std::to_string(need_bytes) + " needed (gr_mipped_background_scratch_bytes)");
+    const uintptr_t image_at = (uintptr_t)rgba8, packed_at = (uintptr_t)packed_out, scratch_at = (uintptr_t)scratch;
+    if (image_at % 4 || packed_at % 16 || (need_bytes && scratch_at % 16))
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": rgba8 must be aligned to 4 bytes, packed_out and scratch to 16");
+    auto overlap = [](uintptr_t a, size_t an, uintptr_t b, size_t bn) { return an && bn && a < b + bn && b < a + an; };
+    const bool in_place = image_at == packed_at;
+    if ((!in_place && overlap(image_at, image_bytes, packed_at, packed_bytes)) || overlap(scratch_at, need_bytes, packed_at, packed_bytes) ||
+        overlap(scratch_at, need_bytes, image_at, image_bytes))
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": rgba8, packed_out and scratch overlap (rgba8 == packed_out is the one overlap allowed)");
+    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": null program");
+    for (int source_level = 0; source_level < levels - 1; source_level += 5) {
+        int count = std::min(5, levels - 1 - source_level);
+        void* args[] = {&rgba8, &scratch, &width, &height, &source_level, &count};
+        rc = launch(p, K_BACKGROUND_REDUCE, stream, blocks((width >> source_level) >> 1, 16), blocks((height >> source_level) >> 1, 16), 16, 16, args);
+        if (rc != GR_OK) return rc;
+    }
+    if (in_place && levels == 1) return levels;   // slice 0 is the image and is where it should be
+    int levels_arg = levels, in_place_arg = in_place ? 1 : 0;
+    void* args[] = {&rgba8, &scratch, &packed_out, &width, &height, &levels_arg, &in_place_arg};
+    rc = launch(p, K_BACKGROUND_SLICES, stream, blocks(((long long)width * height * levels + 3) / 4, 256), 1, 256, 1, args);
+    return rc != GR_OK ? rc : levels;
 }
 
 int gr_internal_fail(int code, const char* msg) { return fail((gr_status)code, msg ? msg : ""); }

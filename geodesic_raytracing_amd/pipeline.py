@@ -575,3 +575,27 @@ def pack_background(rgba):
     if rc != levels:
         raise GeodesicError("gr_pack_mipped_background failed")
     return out, levels
+
+
+def build_background(program, rgba, device=0, stream=None):
+    """pack_background on the device (gr_build_mipped_background): uploads the RGBA8 image [h, w, 4] into slice 0 of a new packed buffer
+    and builds the other slices in place, on `stream` -> (DeviceBuffer of levels * h * w * 4 bytes, levels), the bytes pack_background
+    makes.  The float pyramid the build needs is freed once the stream has been synchronised, which this function does."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+    if rgba.ndim != 3 or rgba.shape[2] != 4:
+        raise ValueError(f"build_background: an image of shape {rgba.shape} is not [H, W, 4]")
+    h, w = rgba.shape[:2]
+    levels = lib.gr_pack_mipped_background(None, w, h, None)
+    if levels <= 0:
+        raise GeodesicError("gr_pack_mipped_background failed")
+    need = ctypes.c_size_t()
+    check(lib.gr_mipped_background_scratch_bytes(w, h, ctypes.byref(need)))
+    packed = DeviceBuffer(device, levels * rgba.nbytes)
+    scratch = DeviceBuffer(device, need.value) if need.value else None
+    check(lib.gr_device_upload(device, packed.ptr, rgba.ctypes.data_as(c_void_p), rgba.nbytes))
+    rc = lib.gr_build_mipped_background(program.handle, stream, packed.ptr, w, h, packed.ptr, scratch.ptr if scratch else None, need.value)
+    if rc != levels:
+        check(rc)
+        raise GeodesicError(f"gr_build_mipped_background made {rc} levels, gr_pack_mipped_background makes {levels}")
+    check(lib.gr_stream_synchronize(stream))   # (the scratch is freed on return)
+    return packed, levels

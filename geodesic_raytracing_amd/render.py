@@ -3,6 +3,7 @@
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 1920x1080 --out kerr.png
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 1920x1080 --supersample 2 --out kerr_ss2.png
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --encode device --out kerr_4k.png
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --background sky.png --mips device --out kerr_sky.png
     python -m geodesic_raytracing_amd.render --metric alcubierre --redshift --camera 0,0,-6,0.5 --background sky.png --out warp.png
     # camera riding its own timelike geodesic: 24 frames, 0.5 units of proper time apart -> fall_000.png .. fall_023.png
     python -m geodesic_raytracing_amd.render --metric schwarzschild --camera 0,0,-8,0 --geodesic-speed 0,0.3,0 \
@@ -44,12 +45,16 @@ def write_rgba8_png(path, pixels):
 
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
-           parallel_transport=True, supersample=1, rgba8=False):
+           parallel_transport=True, supersample=1, rgba8=False, mips="host"):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
     rgba8: the frames are uint8 [H, W, 4] in sRGB instead, encoded on the device (RenderState.render_rgba8) and fetched at 4 bytes a
-    pixel through pinned memory - the bytes pipeline.encode_srgb8 makes of the float frame."""
+    pixel through pinned memory - the bytes pipeline.encode_srgb8 makes of the float frame.
+    mips: where the sky's mip slices are made - "host" (pack_background, all slices uploaded) or "device" (build_background: the image is
+    uploaded and the slices are built there, the same bytes)."""
+    if mips not in ("host", "device"):
+        raise ValueError(f"render: mips={mips!r} (host or device)")
     metric = gra.Metric(metric_name, scripts or os.path.join(HERE, "scripts"))
     feats = metric.features(adaptive_sampling=int(adaptive), redshift=int(redshift), field_of_view=fov, universe_size=universe)
     cfg_values = metric.cfg_values(**(cfg or {}))
@@ -57,13 +62,16 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     program = manager.current(wait=wait_for_static)
     state = gra.RenderState(width, height, device, supersample=supersample)
     rgba = background if background is not None else gra.synthetic_background(2048, 1024)
-    packed, levels = gra.pack_background(rgba)
-    dbg = DeviceBuffer.from_numpy(device, packed)
+    if mips == "device":
+        dbg, levels = gra.build_background(program, rgba, device)
+    else:
+        packed, levels = gra.pack_background(rgba)
+        dbg = DeviceBuffer.from_numpy(device, packed)
     out = DeviceBuffer(device, width * height * (4 if rgba8 else 16))
     pinned = PinnedBuffer(width * height * 4) if rgba8 else None
     cam = gra.default_camera(camera_pos, camera_quat)
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
-    bg = (dbg.ptr, packed.shape[2], packed.shape[1], levels)
+    bg = (dbg.ptr, rgba.shape[1], rgba.shape[0], levels)
 
     def one_frame(options):
         if not rgba8:
@@ -120,6 +128,8 @@ def main(argv=None):
                     "average them on the device (the output keeps the size given by --size)")
     ap.add_argument("--encode", choices=["host", "device"], default="host", help="where the frame becomes 8-bit sRGB: host = download float4 and "
                     "convert there; device = encode on the GPU and download 4 bytes a pixel (the same bytes)")
+    ap.add_argument("--mips", choices=["host", "device"], default="host", help="where the sky's mip slices are made: host = pack them on the CPU "
+                    "and upload all of them; device = upload the image and build the slices on the GPU (the same bytes)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
@@ -130,7 +140,8 @@ def main(argv=None):
     result = render(a.metric, w, h, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
                     [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, a.adaptive,
                     read_png(a.background) if a.background else None, a.device, a.fov, a.universe, geodesic_speed=speed,
-                    geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample, rgba8=a.encode == "device")
+                    geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample, rgba8=a.encode == "device",
+                    mips=a.mips)
     write = write_rgba8_png if a.encode == "device" else write_frame_png
     if speed is None:
         write(a.out, result)

@@ -74,7 +74,6 @@ int gr_metric_load_script(const char* scripts_dir, const char* name, gr_metric**
 /* A metric that is only what gr_render_frame reads off one (gr_metric_info, the $cfg names and defaults), for a caller that already
  * holds the argument strings (a program cache, a fixture); gr_metric_argument_string fails on it.  var_names may be NULL. */
 int gr_metric_from_info(const gr_metric_info* info, const char* const* var_names, const float* var_defaults, gr_metric** out);
-
 void gr_metric_destroy(gr_metric* m);
 int gr_metric_get_info(const gr_metric* m, gr_metric_info* out);
 const char* gr_metric_dynamic_var_name(const gr_metric* m, int index);
@@ -110,10 +109,8 @@ int gr_program_create(const char* argument_string, int device, gr_program** out)
  * code object that - when it is not in the cache yet - is still being built when gr_program_create returns, and the first launcher that
  * needs one of them waits for it.  gr_program_complete waits now (and reports that build's error, if any). */
 int gr_program_complete(gr_program* p);
-
 /* Compile only (no device needed): fills the on-disk cache; used by the build step. */
 int gr_program_precompile(const char* argument_string);
-
 void gr_program_destroy(gr_program* p);
 
 /* metric_manager (metric_manager.hpp:19-219) as an object.  _create builds the dynamic program of `m` (blocking, as the reference does
@@ -170,7 +167,6 @@ int gr_render(gr_program* p, void* stream, const void* render_data, const void* 
               int height, int max_probes, const void* cfg, const void* dfg);
 /* ---- camera riding a timelike geodesic (snapshot sequence main.cpp:2675-2760, per-frame interpolation :2265-2297).
  *      Path buffers are step-major: element k of observer id is at [k*count + id]; basis_speed buffers hold float4 per observer. */
-
 /* boost_tetrad, cl.cl:2441-2481; main.cpp:2700 */
 int gr_boost_tetrad(gr_program* p, void* stream, const void* generic_in, int count, const void* basis_speed, void* e0_io, void*
                     e1_io, void* e2_io, void* e3_io, const void* cfg);
@@ -271,9 +267,8 @@ int gr_geodesic_camera_snapshot(gr_geodesic_camera* g, gr_program* p, const gr_m
                                 const float geodesic_basis_speed[3], const gr_features* features, const float* cfg_values, int
                                 num_cfg_values, int* steps_out, float* proper_time_out);
 /* handle_interpolating_geodesic + read-back (main.cpp:2295-2296): position, tetrad (4 x 4), 4-velocity at `proper_time`; outputs may be NULL */
-int gr_geodesic_camera_interpolate(gr_geodesic_camera* g, gr_program* p, void* stream, float proper_time, int
-                                parallel_transport_observer, float camera_generic_out[4], float tetrad_out[16], float
-                                velocity_out[4]);
+int gr_geodesic_camera_interpolate(gr_geodesic_camera* g, gr_program* p, void* stream, float proper_time, int parallel_transport_observer,
+                                   float camera_generic_out[4], float tetrad_out[16], float velocity_out[4]);
 
 /* blocking copies for tests and tools */
 int gr_device_download(int device, void* host_dst, const void* device_src, size_t bytes);
@@ -320,9 +315,8 @@ int gr_tiled_create_local(int count, const int* devices, int width, int height, 
 int gr_tiled_create_ipc(int world, int rank, int device, const char* session, int width, int height, int block_rows, gr_tiled** out);
 void gr_tiled_destroy(gr_tiled* t);
 int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
-                          const gr_features* features, const float* cfg_values, int num_cfg_values, const void* background1, const
-                          void* background2, int bg_width, int bg_height, int bg_levels, void* frame_on_root, const
-                          gr_frame_options* options, int rotation);
+                          const gr_features* features, const float* cfg_values, int num_cfg_values, const void* background1, const void* background2,
+                          int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation);
 int gr_tiled_join(gr_tiled* root, void* stream);
 /* the share participant t renders in a frame with this rotation */
 int gr_tiled_share(const gr_tiled* t, int rotation);
@@ -335,6 +329,12 @@ int gr_tiled_look_ahead(gr_tiled* t, int rotations);
 /* load_mipped_image (graphics_settings.cpp:152-212): an RGBA8 image and its box-filtered mip chain in `levels` same-size slices (mip i
  * in the top-left corner of slice i, edge replicated).  Returns the number of levels; out needs levels*width*height*4 bytes (NULL asks). */
 int gr_pack_mipped_background(const unsigned char* rgba, int width, int height, unsigned char* out);
+/* The same bytes made on the device (p: any program; its set-up module holds the kernels): rgba8 (device, width*height*4 bytes) -> packed_out
+ * (device, levels*width*height*4 bytes), asynchronous on `stream`; scratch: _scratch_bytes' answer (0 for a one-level image), device.  rgba8 ==
+ * packed_out is allowed (the image was uploaded into slice 0, which is left as it is).  Refused before any device call: any other overlap of
+ * the three, a NULL, a short scratch, more than 1.7e9 texels, rgba8 not aligned to 4 bytes, packed_out or scratch not to 16.  Returns levels. */
+int gr_mipped_background_scratch_bytes(int width, int height, size_t* bytes);
+int gr_build_mipped_background(gr_program* p, void* stream, const void* rgba8, int width, int height, void* packed_out, void* scratch, size_t scratch_bytes);
 
 /* ---- host helpers: PNG in/out (the screenshot path main.cpp:2762-2808, the background loader graphics_settings.cpp:214-243) ---- */
 /* clamp -> linear-to-sRGB -> clamp -> 8 bit, the reference's screenshot loop (main.cpp:2791-2800); a NaN: undefined here, 0 on the device */
