@@ -109,8 +109,11 @@ __device__ float4 integrate_footprint(const sky_sampler& sky, float2 centre, sky
 }
 
 // colour (cl.cl:326-350, 5366-5413)
-// x^y for x > 0 on v_log_f32 / v_exp_f32: the colour curves take powers of values in (0, 1] with |log2 x| < 9, where the error of this
-// form is below 2e-7 of the result (the library's pow: ~100 instructions, three to six of them a pixel)
+// x^y for x > 0 on v_log_f32 / v_exp_f32: the colour curves take powers of values in (0, 1] with |log2 x| < 9.  The exponent
+// t = y log2 x carries the rounding of the logarithm and of the product, so the error is about (2 |t| ln 2 + 2) 2^-24 of the result:
+// 2e-7 for |t| < 1, 1.9e-6 at |t| = 21.6 (x = 2^-9, y = 2.4; measured 1.4e-6 with correctly rounded log2 / exp2,
+// tests/test_shading_model.py).  The curves below call it above their linear toes only, |t| < 8.5: 8e-7 of a result that is small
+// where |t| is large, a few 1e-7 of the frame's unit in absolute terms (the library's pow: ~100 instructions, three to six of them a pixel)
 __device__ __forceinline__ float colour_pow(float x, float y) { return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x)); }
 __device__ __forceinline__ float srgb_to_linear(float v) { return v < 0.04045f ? v / 12.92f : colour_pow((v + 0.055f) / 1.055f, 2.4f); }
 __device__ __forceinline__ float linear_to_srgb(float v) { return v <= 0.0031308f ? v * 12.92f : 1.055f * colour_pow(v, 1.0f / 2.4f) - 0.055f; }
@@ -234,8 +237,10 @@ extern "C" __global__ void gr_render(const render_data* __restrict__ rdata, cons
     const bool last_column = px == width - 1, last_row = py == height - 1;
     float2 beside = make_float2(0, 0), below = make_float2(0, 0);
     if (self.terminated == 1) {
-        beside = rdata[py * width + px + (last_column ? -1 : 1)].tex_coord;
-        below = rdata[(py + (last_row ? -1 : 1)) * width + px].tex_coord;
+        // a frame one pixel wide (high) has no horizontal (vertical) neighbour: the pixel stands in for it, the difference is zero
+        // and the footprint is the one-texel padding (the reference reads the record before the buffer there)
+        beside = rdata[py * width + px + (last_column ? (width > 1 ? -1 : 0) : 1)].tex_coord;
+        below = rdata[(py + (last_row ? (height > 1 ? -1 : 0) : 1)) * width + px].tex_coord;
     }
     const sky_sampler near_sky{bg1_texels, bg_width, bg_height, bg_levels}, far_sky{bg2_texels, bg_width, bg_height, bg_levels};
     out[out_index] = shade_pixel(self, beside, last_column, below, last_row, near_sky, far_sky, most_probes, dfg);

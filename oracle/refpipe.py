@@ -116,6 +116,21 @@ class OraclePipeline:
             out["pixels"] = pixels
         return out
 
+    def render(self, records, width, height, sky1, sky2, levels, max_probes, features_bytes, nthreads=1, count=None, fill=0.0):
+        """ref_render on records made by hand (tests/shading_model.py): the first `count` records (default: all) shaded over the packed
+        skies [levels][h][w][4] -> pixels [height][width][4], `fill` where no record wrote.  (render reads no $cfg parameter.)"""
+        rdata = np.ascontiguousarray(records, dtype=RENDER_DATA_DTYPE)
+        sky1 = np.ascontiguousarray(sky1, dtype=np.uint8)
+        sky2 = np.ascontiguousarray(sky2, dtype=np.uint8)
+        assert sky1.shape == sky2.shape and sky1.shape[0] == levels and len(rdata) == width * height
+        rcount = np.array([len(rdata) if count is None else count], dtype="<i4")
+        cfg = np.zeros(16, dtype="<f4")
+        dfg = np.frombuffer(features_bytes, dtype=np.uint8).copy()
+        pixels = np.full((height, width, 4), fill, dtype="<f4")
+        self.lib.ref_render(_p(rdata), _p(rcount), len(rdata), _p(pixels), _p(sky1), _p(sky2), sky1.shape[2], sky1.shape[1], levels,
+                            width, height, max_probes, _p(cfg), _p(dfg), nthreads)
+        return pixels
+
     def attempts_per_ray(self, rays_init, cfg_values, features_bytes, nthreads=8):
         """Verlet attempts of every initial ray (restatement back end only; see ref_attempts_per_ray)"""
         cfg = np.array(list(cfg_values) if len(cfg_values) else [0.0], dtype="<f4")

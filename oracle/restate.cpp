@@ -920,8 +920,10 @@ void shade_pixel(const render_data* rdata, int id, float* out, const image& bg1,
     float sxf = rdat.tex_x, syf = rdat.tex_y;
     int dx = sx == width - 1 ? -1 : 1, dy = sy == height - 1 ? -1 : 1;
     const render_data& tl = rdata[sy * width + sx];
-    const render_data& tr = rdata[sy * width + sx + dx];
-    const render_data& bl = rdata[(sy + dy) * width + sx];
+    // a frame one pixel wide (high) has no horizontal (vertical) neighbour: the reference reads rdata[-1] / rdata[sx - width] there;
+    // here the pixel stands in for it (difference zero, the footprint is the "+ 1" padding), as kernels/shading.hip has it
+    const render_data& tr = rdata[sy * width + sx + (width > 1 ? dx : 0)];
+    const render_data& bl = rdata[(sy + (height > 1 ? dy : 0)) * width + sx];
     const float bias = 1.3f;
     float dxu = circular_diff(tl.tex_x, tr.tex_x) / bias, dxv = circular_diff(tl.tex_y, tr.tex_y) / bias;
     float dyu = circular_diff(tl.tex_x, bl.tex_x) / bias, dyv = circular_diff(tl.tex_y, bl.tex_y) / bias;

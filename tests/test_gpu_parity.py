@@ -14,6 +14,7 @@ and libm, and rays near photon orbits amplify 1-ulp differences - SURVEY.md sect
                            percentile of all terminated rays is held to the same 1e-3; total attempts within 0.3 %
   render_data              tex_coord abs 2e-6 (periodic), z_shift 1e-4 relative to |1 + z|, flags exact
   render (pixels)          RMSE <= 1e-5, max 2e-4 from golden render_data
+                           (the same two on records made by hand, against a float64 model: tests/test_gpu_shading.py)
   end to end (pixels)      RMSE <= 1e-4 after masking pixels off by > 1e-3; mask <= 0.5 %
                            (super-extremal Kerr, a naked singularity with chaotic orbits: mask <= 10 %, RMSE <= 3e-4)
 """
