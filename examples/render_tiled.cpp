@@ -9,9 +9,12 @@
 //   examples/render_tiled --spawn 8 --self-test 1 ...    first contact with a new node: N ranks on whatever GPUs there are (rank r on
 //       device r % count; fewer GPUs than ranks: RCCL through sockets as above), rank 0 compares the gathered frame with the same frame
 //       rendered on its own GPU alone, and the launcher prints which RCCL transport every channel took (P2P/IPC over xGMI, SHM, NET)
+//   --supersample N   every rank traces its rows at N x N rays a pixel (1..4) and box-averages them on its own GPU before they leave it
+//   --rgba8           ... and encodes them there: the frame travels, and arrives on rank 0, as 8-bit sRGB - 4 bytes a pixel instead of 16
+//       (both through gr_render_frame_tiled_as; --self-test compares with rank 0's own whole frame in the same format)
 //
 // Every rank renders its (rotating) share of the image rows with frames in flight on streams of their own, rank 0 receives
-// every block at its place in the frame (gr_render_frame_tiled), writes the last frame as a PNG and prints frames per second
+// every block at its place in the frame (gr_render_frame_tiled_as), writes the last frame as a PNG and prints frames per second
 // with and without the transfer (a second pass renders the same shares without sending them).
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -38,6 +41,8 @@
 
 static int g_rank = 0;
 static int g_self_test = 0;
+static int g_supersample = 1;   // --supersample
+static int g_rgba8 = 0;         // --rgba8
 
 // the id of gr_tiled_unique_id from rank 0 to everybody: written to a temporary name and renamed, so a reader sees all of it or nothing
 static bool publish_id(const std::string& path, const unsigned char id[128]) {
@@ -72,6 +77,9 @@ static int worker(int world, int rank, int device, const std::string& id_file, i
     int first_override = 5;
     if (argc > 5 && !std::strchr(argv[5], '=')) { frames = std::atoi(argv[5]); first_override = 6; }
     const int block_rows = 48, in_flight = 3;
+    const int format = g_rgba8 ? GR_FRAME_RGBA8 : GR_FRAME_F32;
+    const size_t pixel_bytes = g_rgba8 ? 4 : 16;
+    const auto render_frame = g_rgba8 ? gr_render_frame_rgba8 : gr_render_frame;
 
     if (g_self_test) {
         // whatever GPUs this node has: rank r on device r % count; with fewer GPUs than ranks every rank claims a host of its own so
@@ -151,9 +159,9 @@ static int worker(int world, int rank, int device, const std::string& id_file, i
     std::vector<gr_render_state*> states(in_flight, nullptr);
     std::vector<void*> streams(in_flight, nullptr), frames_on_root(in_flight, nullptr);
     for (int j = 0; j < in_flight; j++) {
-        CHECK(gr_render_state_create(device, width, height, &states[j]));
+        CHECK(gr_render_state_create_supersampled(device, width, height, g_supersample, &states[j]));
         CHECK(gr_stream_create(device, 0, &streams[j]));
-        if (rank == 0) CHECK(gr_device_alloc(device, (size_t)width * height * 16, &frames_on_root[j]));
+        if (rank == 0) CHECK(gr_device_alloc(device, (size_t)width * height * pixel_bytes, &frames_on_root[j]));
     }
     gr_camera camera;
     gr_camera_default(&camera);
@@ -167,17 +175,17 @@ static int worker(int world, int rank, int device, const std::string& id_file, i
             gr_frame_options_default(&options);
             options.next_camera = &camera;   // a batch renderer knows the next camera: its prepass runs ahead on a side stream
             if (transfer) {
-                CHECK(gr_render_frame_tiled(tiled, states[j], program, metric, streams[j], &camera, &features, cfg.data(), info.num_dynamic_vars,
-                                            d_background, d_background, bw, bh, levels, frames_on_root[j], &options, k));
+                CHECK(gr_render_frame_tiled_as(tiled, states[j], program, metric, streams[j], &camera, &features, cfg.data(), info.num_dynamic_vars,
+                                               d_background, d_background, bw, bh, levels, frames_on_root[j], &options, k, format));
             } else {   // the same share, rendered and left where it is
                 options.strip_count = world;
                 options.strip_rank = gr_tiled_share(tiled, k);
                 options.block_rows = block_rows;
                 options.compact_out = 0;
                 static void* scratch = nullptr;
-                if (!scratch) CHECK(gr_device_alloc(device, (size_t)width * height * 16, &scratch));
-                CHECK(gr_render_frame(states[j], program, metric, streams[j], &camera, &features, cfg.data(), info.num_dynamic_vars, d_background,
-                                      d_background, bw, bh, levels, scratch, &options));
+                if (!scratch) CHECK(gr_device_alloc(device, (size_t)width * height * pixel_bytes, &scratch));
+                CHECK(render_frame(states[j], program, metric, streams[j], &camera, &features, cfg.data(), info.num_dynamic_vars, d_background,
+                                   d_background, bw, bh, levels, scratch, &options));
             }
         }
         for (int j = 0; j < in_flight; j++) CHECK(gr_stream_synchronize(streams[j]));
@@ -191,37 +199,59 @@ static int worker(int world, int rank, int device, const std::string& id_file, i
 
     if (rank == 0) {
         const int last = (frames - 1) % in_flight;
-        std::vector<float> frame((size_t)width * height * 4);
-        CHECK(gr_device_download(device, frame.data(), frames_on_root[last], frame.size() * sizeof(float)));
-        CHECK(gr_write_frame_png(out_path, frame.data(), width, height));
-        std::printf("%s %dx%d over %d GPU(s), %d frames, %d in flight: %.1f frames/s with the transfer to rank 0, %.1f without; wrote %s\n", name, width,
-                    height, world, frames, in_flight, frames / with_transfer, frames / without_transfer, out_path);
+        std::vector<float> frame(g_rgba8 ? 0 : (size_t)width * height * 4);
+        std::vector<unsigned char> bytes(g_rgba8 ? (size_t)width * height * 4 : 0);
+        if (g_rgba8) {
+            CHECK(gr_device_download(device, bytes.data(), frames_on_root[last], bytes.size()));
+            CHECK(gr_write_png_rgba8(out_path, bytes.data(), width, height));
+        } else {
+            CHECK(gr_device_download(device, frame.data(), frames_on_root[last], frame.size() * sizeof(float)));
+            CHECK(gr_write_frame_png(out_path, frame.data(), width, height));
+        }
+        std::printf("%s %dx%d over %d GPU(s), %d x %d rays a pixel, %s rows (%zu bytes a pixel shipped), %d frames, %d in flight: %.1f frames/s with the transfer "
+                    "to rank 0, %.1f without; wrote %s\n", name, width, height, world, g_supersample, g_supersample, g_rgba8 ? "8-bit sRGB" : "float4", pixel_bytes,
+                    frames, in_flight, frames / with_transfer, frames / without_transfer, out_path);
         if (g_self_test) {
-            // the same frame on this GPU alone (the split changes who traces a row, not what is traced: the frames are equal bit for bit)
+            // the same frame on this GPU alone, same factor, same format (the split changes who traces a row, not what is traced: the frames
+            // are equal bit for bit)
             gr_render_state* whole = nullptr;
             void* d_whole = nullptr;
-            CHECK(gr_render_state_create(device, width, height, &whole));
-            CHECK(gr_device_alloc(device, (size_t)width * height * 16, &d_whole));
+            CHECK(gr_render_state_create_supersampled(device, width, height, g_supersample, &whole));
+            CHECK(gr_device_alloc(device, (size_t)width * height * pixel_bytes, &d_whole));
             gr_frame_options options;
             gr_frame_options_default(&options);
             options.mode = GR_MODE_FUSED;
-            CHECK(gr_render_frame(whole, program, metric, streams[0], &camera, &features, cfg.data(), info.num_dynamic_vars, d_background, d_background,
-                                  bw, bh, levels, d_whole, &options));
+            CHECK(render_frame(whole, program, metric, streams[0], &camera, &features, cfg.data(), info.num_dynamic_vars, d_background, d_background,
+                               bw, bh, levels, d_whole, &options));
             CHECK(gr_stream_synchronize(streams[0]));
-            std::vector<float> alone((size_t)width * height * 4);
-            CHECK(gr_device_download(device, alone.data(), d_whole, alone.size() * sizeof(float)));
-            size_t differing = 0;
-            double worst = 0;
-            for (size_t i = 0; i < alone.size(); i++) {
-                const double d = std::fabs((double)alone[i] - (double)frame[i]);
-                if (d > 0) differing++;
-                if (d > worst || d != d) worst = d != d ? 1e30 : d;
+            size_t differing = 0, values = 0;
+            double worst = 0, allowed = 1e-3;
+            if (g_rgba8) {
+                std::vector<unsigned char> alone(bytes.size());
+                CHECK(gr_device_download(device, alone.data(), d_whole, alone.size()));
+                values = alone.size();
+                allowed = 0;   // bytes: equal or not
+                for (size_t i = 0; i < alone.size(); i++) {
+                    const double d = std::fabs((double)alone[i] - (double)bytes[i]);
+                    if (d > 0) differing++;
+                    if (d > worst) worst = d;
+                }
+            } else {
+                std::vector<float> alone((size_t)width * height * 4);
+                CHECK(gr_device_download(device, alone.data(), d_whole, alone.size() * sizeof(float)));
+                values = alone.size();
+                for (size_t i = 0; i < alone.size(); i++) {
+                    const double d = std::fabs((double)alone[i] - (double)frame[i]);
+                    if (d > 0) differing++;
+                    if (d > worst || d != d) worst = d != d ? 1e30 : d;
+                }
             }
-            std::printf("self-test: gathered frame against the single-GPU frame: %zu of %zu values differ, largest difference %.3g -> %s\n", differing,
-                        alone.size(), worst, differing == 0 ? "IDENTICAL" : worst <= 1e-3 ? "within 1e-3" : "MISMATCH");
+            std::printf("self-test: gathered frame against the single-GPU frame (%s, factor %d): %zu of %zu values differ, largest difference %.3g -> %s\n",
+                        g_rgba8 ? "8-bit sRGB" : "float4", g_supersample, differing, values, worst,
+                        differing == 0 ? "IDENTICAL" : worst <= allowed ? "within 1e-3" : "MISMATCH");
             gr_device_free(device, d_whole);
             gr_render_state_destroy(whole);
-            if (worst > 1e-3) return 1;
+            if (worst > allowed) return 1;
         }
     }
     gr_tiled_destroy(tiled);
@@ -241,6 +271,7 @@ int main(int argc, char** argv) {
     std::string id_file;
     int a = 1;
     for (; a < argc && std::strncmp(argv[a], "--", 2) == 0; a += 2) {
+        if (!std::strcmp(argv[a], "--rgba8")) { g_rgba8 = 1; a--; continue; }   // (the one switch that takes no value)
         if (a + 1 >= argc) break;
         if (!std::strcmp(argv[a], "--spawn")) spawn = std::atoi(argv[a + 1]);
         else if (!std::strcmp(argv[a], "--world")) world = std::atoi(argv[a + 1]);
@@ -249,10 +280,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--id-file")) id_file = argv[a + 1];
         else if (!std::strcmp(argv[a], "--one-device")) one_device = std::atoi(argv[a + 1]);
         else if (!std::strcmp(argv[a], "--self-test")) g_self_test = std::atoi(argv[a + 1]);
+        else if (!std::strcmp(argv[a], "--supersample")) g_supersample = std::atoi(argv[a + 1]);
         else { std::fprintf(stderr, "unknown option %s\n", argv[a]); return 2; }
     }
+    if (g_supersample < 1 || g_supersample > 4) { std::fprintf(stderr, "--supersample: 1, 2, 3 or 4\n"); return 2; }
     if (argc - a < 5) {
-        std::fprintf(stderr, "usage: %s (--spawn N [--one-device 1] | --world N --rank R [--device D] --id-file PATH) <scripts dir> <metric> <width> <height> <out.png> "
+        std::fprintf(stderr, "usage: %s (--spawn N [--one-device 1] | --world N --rank R [--device D] --id-file PATH) [--supersample N] [--rgba8] <scripts dir> <metric> <width> <height> <out.png> "
                              "[frames] [name=value ...]\n", argv[0]);
         return 2;
     }

@@ -121,6 +121,7 @@ class Transport(ctypes.Structure):
 
 
 MODE_REFERENCE, MODE_FUSED = 0, 1
+FRAME_F32, FRAME_RGBA8 = 0, 1
 EVAL_METRIC_TENSOR, EVAL_METRIC_DERIVATIVES, EVAL_ACCELERATION, EVAL_TO_POLAR, EVAL_FROM_POLAR, EVAL_ORIGIN_DISTANCE = range(6)
 (STAGE_CAMERA, STAGE_PREPASS, STAGE_INIT, STAGE_TRACE, STAGE_RENDER_DATA, STAGE_ADAPTIVE, STAGE_RENDER) = range(7)
 STAGE_NAMES = ["camera", "prepass", "init", "trace", "render_data", "adaptive", "render"]
@@ -273,9 +274,13 @@ _SIGNATURES = {
     "gr_render_frame_tiled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
                                       ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                       ctypes.POINTER(FrameOptions), c_int]),
+    "gr_render_frame_tiled_as": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
+                                         ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                         ctypes.POINTER(FrameOptions), c_int, c_int]),
     "gr_tiled_join": (c_int, [c_void_p, c_void_p]),
     "gr_tiled_create_custom": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "gr_tiled_exchange": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gr_tiled_exchange_as": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
     "gr_tiled_staging_bytes": (c_size_t, [c_void_p]),
     "gr_tiled_look_ahead": (c_int, [c_void_p, c_int]),
     "gr_tiled_share": (c_int, [c_void_p, c_int]),

@@ -498,15 +498,21 @@ size_t gr_tiled_staging_bytes(const gr_tiled* t) { return t ? t->staging_bytes()
 // The transfer of one frame: every block of every other participant's share from its compact place in that participant's
 // `staging` to its rows of the root's frame.  Point-to-point transports: one group per frame, on the owner one send per block in
 // block order, on the root the matching receives peer by peer in the same block order (sends and receives between two ranks
-// match in issue order).
-int gr_tiled_exchange(gr_tiled* t, const void* staging, void* frame_on_root, int rotation, void* stream_v) {
+// match in issue order).  `format` sets the size of a pixel - 16 bytes (GR_FRAME_F32) or 4 (GR_FRAME_RGBA8) - and with it every offset
+// and count: rows of a byte frame are a quarter as long, in the frame and in the staged blocks alike, and a table's send / recv is
+// given a block as 4-byte words whatever they hold (RCCL moves them as ncclFloat: bytes in, the same bytes out).
+static int pixel_bytes_of(int format) { return format == GR_FRAME_F32 ? 16 : format == GR_FRAME_RGBA8 ? 4 : 0; }
+
+int gr_tiled_exchange_as(gr_tiled* t, const void* staging, void* frame_on_root, int rotation, void* stream_v, int format) {
     if (!t) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
+    const size_t pixel_bytes = (size_t)pixel_bytes_of(format);
+    if (!pixel_bytes) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_tiled_exchange_as: unknown frame format " + std::to_string(format) + " (GR_FRAME_F32 or GR_FRAME_RGBA8)").c_str());
     if (t->world == 1) return GR_OK;
     hipStream_t stream = (hipStream_t)stream_v;
     const bool is_root = t->rank == t->root;
     if (is_root ? !frame_on_root : !staging) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "the root needs the frame, the others their staged rows");
     const int share = gr_tiled_share(t, rotation);
-    const size_t row_bytes = (size_t)t->width * 16, row_floats = (size_t)t->width * 4;
+    const size_t row_bytes = (size_t)t->width * pixel_bytes, row_words = row_bytes / 4;
     if (t->transport == GR_TRANSPORT_PEER) {
         if (!frame_on_root) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "peer transport: every participant is given the root's frame buffer");
         if (is_root) return GR_OK;
@@ -531,40 +537,50 @@ int gr_tiled_exchange(gr_tiled* t, const void* staging, void* frame_on_root, int
             for (int i = 0; i < t->blocks_per_share && rc == GR_OK; i++) {
                 int a, b;
                 if (gr_tiled_block_rows_of(t, peer_share, i, &a, &b) != 1) continue;
-                rc = link.recv(link.user, (char*)frame_on_root + (size_t)a * row_bytes, (size_t)(b - a) * row_floats, peer, stream_v);
+                rc = link.recv(link.user, (char*)frame_on_root + (size_t)a * row_bytes, (size_t)(b - a) * row_words, peer, stream_v);
             }
         }
     } else {
         for (int i = 0; i < t->blocks_per_share && rc == GR_OK; i++) {
             int a, b;
             if (gr_tiled_block_rows_of(t, share, i, &a, &b) != 1) continue;
-            rc = link.send(link.user, (const char*)staging + (size_t)i * t->block_rows * row_bytes, (size_t)(b - a) * row_floats, t->root, stream_v);
+            rc = link.send(link.user, (const char*)staging + (size_t)i * t->block_rows * row_bytes, (size_t)(b - a) * row_words, t->root, stream_v);
         }
     }
     const int end_rc = link.group_end ? link.group_end(link.user) : GR_OK;
     return rc != GR_OK ? rc : end_rc;
 }
 
-int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream_v, const gr_camera* camera,
-                          const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
-                          int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation) {
-    if (!t || !s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
-    {   // (the staging buffers and the transfers are laid out for rows of the participant's own size: a supersampled state's share would
-        // have to be resolved before it is shipped, which gr_render_frame's strip mode can do and this function does not do yet)
-        int factor = 1;
-        gr_render_state_supersample(s, &factor, nullptr, nullptr);
-        if (factor != 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a supersampled render state (gr_render_state_create_supersampled) cannot render a split frame yet; use gr_render_frame's strip mode, or a state of factor 1");
-    }
-    if (t->device < 0) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "this participant was created without a device (schedule tests): nothing to render with");
-    {   // (the staging buffers and the blocks' places in the root's frame are those of the participant's frame size)
-        int sw = 0, sh = 0;
-        gr_internal_render_state_size(s, &sw, &sh);
-        if (sw != t->width || sh != t->height) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "the render state is not of the size the participant was created for");
-    }
-    hipStream_t stream = (hipStream_t)stream_v;
+int gr_tiled_exchange(gr_tiled* t, const void* staging, void* frame_on_root, int rotation, void* stream_v) {
+    return gr_tiled_exchange_as(t, staging, frame_on_root, rotation, stream_v, GR_FRAME_F32);
+}
+
+// A participant's share of one frame in either format, at any supersampling factor, and its transfer.  The share is rendered by
+// gr_render_frame / gr_render_frame_rgba8 in strip mode: both trace blocks of factor x block_rows rows into the state's own traced
+// frame and resolve (and encode) them on this device into rows of the participant's size - compactly into the staging slot on a
+// participant other than the root, in place on the root - so what leaves a device is width x rows pixels of the format whatever the
+// factor.  The staging ring is sized for float4 rows; a byte frame's blocks lie back to back in the first quarter of a slot.
+int gr_render_frame_tiled_as(gr_tiled* t, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream_v, const gr_camera* camera,
+                             const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
+                             int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation, int format) {
+    if (!t) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (!pixel_bytes_of(format)) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_render_frame_tiled_as: unknown frame format " + std::to_string(format) + " (GR_FRAME_F32 or GR_FRAME_RGBA8)").c_str());
     const bool is_root = t->rank == t->root;
     if (is_root && !frame_on_root) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "the root needs the frame buffer");
     if (t->transport == GR_TRANSPORT_PEER && !frame_on_root) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "peer transport: every participant is given the root's frame buffer");
+    if (!s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (t->device < 0) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "this participant was created without a device (schedule tests): nothing to render with");
+    {   // (the staging buffers and the blocks' places in the root's frame are those of the participant's frame size: the size of the
+        // state's frames, which a supersampled state traces at factor x that)
+        int factor = 1, tw = 0, th = 0;
+        gr_render_state_supersample(s, &factor, &tw, &th);
+        if (factor < 1 || tw != (long long)t->width * factor || th != (long long)t->height * factor)
+            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "the render state is not of the size the participant was created for");
+        if (t->block_rows > 0x7fffffff / factor)
+            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_render_frame_tiled_as: blocks of " + std::to_string(t->block_rows) + " rows traced at factor " + std::to_string(factor) + " have more rows than an int counts").c_str());
+    }
+    hipStream_t stream = (hipStream_t)stream_v;
+    const auto render = format == GR_FRAME_RGBA8 ? gr_render_frame_rgba8 : gr_render_frame;
     gr_frame_options opt;
     gr_frame_options_default(&opt);
     if (options) opt = *options;
@@ -590,21 +606,33 @@ int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const 
     }
     HIP_CHECK(hipSetDevice(t->device));
     if (t->world == 1)
-        return gr_render_frame(s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, frame_on_root, &opt);
+        return render(s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, frame_on_root, &opt);
     frame_slot* sl = nullptr;
     int rc = next_slot(t, stream, &sl);
     if (rc != GR_OK) return rc;
-    const int render_rc = gr_render_frame(s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
-                                          is_root ? frame_on_root : sl->buffer, &opt);
+    const int render_rc = render(s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
+                                 is_root ? frame_on_root : sl->buffer, &opt);
     std::string render_error = render_rc != GR_OK ? gr_last_error() : "";
     // The transfers are issued even when this participant's render failed: the others have matching sends / receives in their
     // groups and would wait for ever.  The caller sees the render's error.
-    rc = gr_tiled_exchange(t, sl->buffer, frame_on_root, rotation, stream_v);
+    rc = gr_tiled_exchange_as(t, sl->buffer, frame_on_root, rotation, stream_v, format);
     HIP_CHECK(hipEventRecord(sl->done, stream));
     sl->recorded = true;
     sl->pending = t->transport == GR_TRANSPORT_PEER;
     if (render_rc != GR_OK) return gr_internal_fail(render_rc, render_error.c_str());
     return rc;
+}
+
+// The factor-1 float frame, as ever.
+int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream_v, const gr_camera* camera,
+                          const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
+                          int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation) {
+    if (!t || !s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
+    int factor = 1;
+    gr_render_state_supersample(s, &factor, nullptr, nullptr);
+    if (factor != 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a supersampled render state (gr_render_state_create_supersampled) renders its split frames through gr_render_frame_tiled_as; this entry point takes a state of factor 1");
+    return gr_render_frame_tiled_as(t, s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
+                                    frame_on_root, options, rotation, GR_FRAME_F32);
 }
 
 int gr_tiled_join(gr_tiled* root, void* stream_v) {

@@ -4,8 +4,8 @@ import ctypes
 
 import numpy as np
 
-from . import (Camera, Features, FrameOptions, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int, c_size_t,
-               c_void_p, check, lib)
+from . import (Camera, Features, FrameOptions, FRAME_F32, FRAME_RGBA8, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
+               c_size_t, c_void_p, check, lib)
 
 LIGHTRAY_DTYPE = np.dtype([("position", "<f4", 4), ("velocity", "<f4", 4), ("initial_quat", "<f4", 4),
                            ("acceleration", "<f4", 4), ("ku_uobsu", "<f4"), ("running_dlambda_dnew", "<f4"),
@@ -201,6 +201,17 @@ class TiledFrame:
 
     def render(self, state, program, metric, camera, frame_ptr, background=None, features=None, cfg_values=None, options=None, stream=None,
                rotation=0):
+        """this participant's share of a float frame from a state of factor 1 (gr_render_frame_tiled)"""
+        self._render(None, state, program, metric, camera, frame_ptr, background, features, cfg_values, options, stream, rotation)
+
+    def render_as(self, state, program, metric, camera, frame_ptr, background=None, features=None, cfg_values=None, options=None, stream=None,
+                  rotation=0, rgba8=False):
+        """render() for a state of any supersampling factor, in either format (gr_render_frame_tiled_as): the share is traced at the state's
+        factor and resolved on this participant's device; rgba8 = True ships it as 8-bit sRGB, 4 bytes a pixel, and `frame_ptr` (on
+        participant 0's device) is then width*height*4 bytes - RenderState.render_rgba8's bytes."""
+        self._render(FRAME_RGBA8 if rgba8 else FRAME_F32, state, program, metric, camera, frame_ptr, background, features, cfg_values, options, stream, rotation)
+
+    def _render(self, frame_format, state, program, metric, camera, frame_ptr, background, features, cfg_values, options, stream, rotation):
         arr, n = None, 0
         if cfg_values is not None:
             n = len(cfg_values)
@@ -212,9 +223,9 @@ class TiledFrame:
             bg1, bg2 = ptrs if isinstance(ptrs, tuple) else (ptrs, ptrs)
         if features is None:
             features = metric.features()
-        check(lib.gr_render_frame_tiled(self.handle, state.handle, program.handle, metric.handle, stream, ctypes.byref(camera),
-                                        ctypes.byref(features), arr, n, bg1, bg2, bw, bh, bl, frame_ptr,
-                                        ctypes.byref(options) if options is not None else None, rotation))
+        args = (self.handle, state.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n, bg1, bg2, bw, bh, bl,
+                frame_ptr, ctypes.byref(options) if options is not None else None, rotation)
+        check(lib.gr_render_frame_tiled(*args) if frame_format is None else lib.gr_render_frame_tiled_as(*args, frame_format))
 
     def join(self, stream=None):
         check(lib.gr_tiled_join(self.handle, stream))

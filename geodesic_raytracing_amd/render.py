@@ -4,6 +4,8 @@
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 1920x1080 --supersample 2 --out kerr_ss2.png
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --encode device --out kerr_4k.png
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --background sky.png --mips device --out kerr_sky.png
+    # one frame over four GPUs (one process, peer copies): every device traces its rows at 4 x 4 rays a pixel and ships them as 8-bit sRGB
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --devices 0,1,2,3 --supersample 4 --encode device --out poster.png
     python -m geodesic_raytracing_amd.render --metric alcubierre --redshift --camera 0,0,-6,0.5 --background sky.png --out warp.png
     # camera riding its own timelike geodesic: 24 frames, 0.5 units of proper time apart -> fall_000.png .. fall_023.png
     python -m geodesic_raytracing_amd.render --metric schwarzschild --camera 0,0,-8,0 --geodesic-speed 0,0.3,0 \
@@ -105,6 +107,61 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
             pinned.free()
 
 
+def split_block_rows(height, block_rows=16):
+    """the rows of a block of a split frame: `block_rows`, or the next multiple of 8 with which the image's last row does not start a block
+    (its filter reads the row above: gr_tiled_create_local refuses that)"""
+    while height > 1 and (height - 1) % block_rows == 0:
+        block_rows += 8
+    return block_rows
+
+
+def render_split(metric_name, width, height, devices, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, background=None,
+                 fov=90.0, universe=20.0, wait_for_static=True, supersample=1, rgba8=False, mips="host", frames=1, block_rows=16):
+    """render() of a Cartesian camera with the rows of every frame dealt to `devices` (TiledFrame.local: one process, peer copies, participant
+    r on devices[r]; a device may be named more than once, which is how a box with one GPU rehearses it).  Every device has its own program,
+    sky (with mips="device" built there, once per device) and render state, traces its share at `supersample` x per axis, resolves it
+    there and ships width x rows pixels to devices[0] - float4, or with rgba8 4 bytes each (TiledFrame.render_as).  Frame k is rendered
+    with rotation k, so the shares go round over `frames`.  Returns the list of frames: the arrays render() returns, bit for bit."""
+    if mips not in ("host", "device"):
+        raise ValueError(f"render_split: mips={mips!r} (host or device)")
+    devices = [int(d) for d in devices]
+    if not devices:
+        raise ValueError("render_split: no devices")
+    metric = gra.Metric(metric_name, scripts or os.path.join(HERE, "scripts"))
+    feats = metric.features(adaptive_sampling=0, redshift=int(redshift), field_of_view=fov, universe_size=universe)
+    cfg_values = metric.cfg_values(**(cfg or {}))
+    rgba = background if background is not None else gra.synthetic_background(2048, 1024)
+    managers, programs, skies = {}, {}, {}
+    for d in devices:   # once per device, however many participants it carries
+        if d in programs:
+            continue
+        managers[d] = ProgramManager(metric, d, feats, cfg_values)
+        programs[d] = managers[d].current(wait=wait_for_static)
+        if mips == "device":
+            dbg, levels = gra.build_background(programs[d], rgba, d)
+        else:
+            packed, levels = gra.pack_background(rgba)
+            dbg = DeviceBuffer.from_numpy(d, packed)
+        skies[d] = (dbg, (dbg.ptr, rgba.shape[1], rgba.shape[0], levels))
+    parts = gra.TiledFrame.local(devices, width, height, split_block_rows(height, block_rows))
+    try:
+        states = [gra.RenderState(width, height, d, supersample=supersample) for d in devices]
+        out = DeviceBuffer(devices[0], width * height * (4 if rgba8 else 16))
+        cam = gra.default_camera(camera_pos, camera_quat)
+        result = []
+        for k in range(max(int(frames), 1)):
+            for r, d in enumerate(devices):
+                parts[r].render_as(states[r], programs[d], metric, cam, out.ptr, skies[d][1], feats, cfg_values, gra.frame_options(mode=gra.MODE_FUSED),
+                                   rotation=k, rgba8=rgba8)
+            parts[0].join()
+            gra.check(gra.lib.gr_device_synchronize(devices[0]))
+            result.append(out.to_numpy(np.uint8 if rgba8 else np.float32, (height, width, 4)))
+        return result
+    finally:
+        for part in parts:
+            part.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--metric", required=True)
@@ -131,18 +188,40 @@ def main(argv=None):
     ap.add_argument("--mips", choices=["host", "device"], default="host", help="where the sky's mip slices are made: host = pack them on the CPU "
                     "and upload all of them; device = upload the image and build the slices on the GPU (the same bytes)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--devices", default=None, help="0,1,2,3: deal the rows of every frame to these GPUs (one process, peer copies; a device may "
+                    "repeat); each traces, resolves and - with --encode device - encodes its share, the share rotating over --frames")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     w, h = (int(v) for v in a.size.lower().split("x"))
     cfg = {k: float(v) for k, v in (kv.split("=") for kv in a.cfg)}
     speed = [float(v) for v in a.geodesic_speed.split(",")] if a.geodesic_speed else None
     times = [a.geodesic_time + i * a.geodesic_dt for i in range(max(a.frames, 1))]
+    write = write_rgba8_png if a.encode == "device" else write_frame_png
+    if a.devices is not None:
+        try:
+            devices = [int(v) for v in a.devices.split(",")]
+        except ValueError:
+            devices = []
+        if not devices or min(devices) < 0:
+            ap.error("--devices: a comma-separated list of device numbers, e.g. 0,1,2,3")
+        if a.adaptive:
+            ap.error("--adaptive with --devices: adaptive sampling runs in reference mode, which renders whole frames (no strips)")
+        if speed is not None:
+            ap.error("--geodesic-speed with --devices: a split frame takes a Cartesian camera")
+        result = render_split(a.metric, w, h, devices, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
+                              [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, read_png(a.background) if a.background else None,
+                              a.fov, a.universe, supersample=a.supersample, rgba8=a.encode == "device", mips=a.mips, frames=a.frames)
+        stem, ext = os.path.splitext(a.out)
+        for i, frame in enumerate(result):
+            path = a.out if len(result) == 1 else f"{stem}_{i:03d}{ext}"
+            write(path, frame)
+            print(f"wrote {path} ({w}x{h}, {len(devices)} participants, rotation {i})")
+        return 0
     result = render(a.metric, w, h, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
                     [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, a.adaptive,
                     read_png(a.background) if a.background else None, a.device, a.fov, a.universe, geodesic_speed=speed,
                     geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample, rgba8=a.encode == "device",
                     mips=a.mips)
-    write = write_rgba8_png if a.encode == "device" else write_frame_png
     if speed is None:
         write(a.out, result)
         print(f"wrote {a.out} ({w}x{h})")

@@ -85,12 +85,11 @@ float gr_metric_dynamic_var_default(const gr_metric* m, int index);
 int gr_metric_argument_string(const gr_metric* m, const gr_features* features, int is_static, const float* cfg_values, int
                               num_cfg_values, char* buffer, size_t capacity, size_t* needed);
 
-/* The metric's generated expressions evaluated on the HOST at one point, in double: the symbolic graph the macro strings are printed from,
- * interpreted - no device, no compiler (BASELINE configs[0], SURVEY.md 7.2c: "CPU evaluator of generated metric code").  For a host that
- * wants to look at a metric; not a rendering path.  position = chart coordinates (v1..v4), velocity = their d/dlambda (iv1..iv4; NULL
- * where unused), cfg_values NULL = defaults.  Writes gr_metric_evaluate_count(what) doubles: 16 g_ij row-major | 64 d g_ij / d x^k as
- * [k][i][j] | 4 accelerations -Gamma^i_jk v^j v^k (GEO_ACCEL0..3) | 4 polar coordinates of the chart point (TO_COORDn) | 4 chart
- * coordinates of the polar point in `position` (FROM_COORDn) | 1 DISTANCE_FUNC of the chart point. */
+/* The metric's generated expressions evaluated on the HOST at one point, in double: the symbolic graph the macro strings are printed from, interpreted -
+ * no device, no compiler (BASELINE configs[0], SURVEY.md 7.2c: "CPU evaluator of generated metric code").  For a host that wants to look at a metric; not
+ * a rendering path.  position = chart coordinates (v1..v4), velocity = their d/dlambda (iv1..iv4; NULL where unused), cfg_values NULL = defaults.  Writes
+ * gr_metric_evaluate_count(what) doubles: 16 g_ij row-major | 64 d g_ij / d x^k as [k][i][j] | 4 accelerations -Gamma^i_jk v^j v^k (GEO_ACCEL0..3) | 4 polar
+ * coordinates of the chart point (TO_COORDn) | 4 chart coordinates of the polar point in `position` (FROM_COORDn) | 1 DISTANCE_FUNC of the chart point. */
 enum { GR_EVAL_METRIC_TENSOR = 0, GR_EVAL_METRIC_DERIVATIVES = 1, GR_EVAL_ACCELERATION = 2, GR_EVAL_TO_POLAR = 3, GR_EVAL_FROM_POLAR = 4,
        GR_EVAL_ORIGIN_DISTANCE = 5 };
 int gr_metric_evaluate_count(int what);
@@ -105,20 +104,18 @@ typedef struct gr_program gr_program;
  * and ignored; -cl-fp32-correctly-rounded-divide-sqrt, OpenCL's own switch, is honoured) and loads them on HIP device `device`.
  * Code objects are cached on disk keyed by a hash of source + arguments. */
 int gr_program_create(const char* argument_string, int device, gr_program** out);
-/* A program is usable as soon as the kernels a fused frame launches are there; the kernels of the reference-shaped sequence are a second
- * code object that - when it is not in the cache yet - is still being built when gr_program_create returns, and the first launcher that
- * needs one of them waits for it.  gr_program_complete waits now (and reports that build's error, if any). */
+/* A program is usable as soon as the kernels a fused frame launches are there; the kernels of the reference-shaped sequence are a second code object that
+ * - when not cached yet - is still being built when gr_program_create returns, and the first launcher that needs one waits for it; _complete waits now. */
 int gr_program_complete(gr_program* p);
 /* Compile only (no device needed): fills the on-disk cache; used by the build step. */
 int gr_program_precompile(const char* argument_string);
 void gr_program_destroy(gr_program* p);
 
-/* metric_manager (metric_manager.hpp:19-219) as an object.  _create builds the dynamic program of `m` (blocking, as the reference does
- * for a newly selected metric) and starts the substituted build for `features` / `cfg_values` (NULL = defaults) on a worker thread.
- * _current is check_substitution: once per frame, swaps the substituted program in when its build has finished (wait != 0: waits) and
- * hands back the program to launch - owned by the manager, valid until two later updates have retired it.  _update is the soft
- * recompile: other values put the dynamic program back at once and start the new build (an overtaken build is not waited for); equal
- * values change nothing.  The metric must outlive the manager.  One thread at a time. */
+/* metric_manager (metric_manager.hpp:19-219) as an object.  _create builds the dynamic program of `m` (blocking, as the reference does for a newly
+ * selected metric) and starts the substituted build for `features` / `cfg_values` (NULL = defaults) on a worker thread.  _current is check_substitution:
+ * once per frame, swaps the substituted program in when its build has finished (wait != 0: waits) and hands back the program to launch - owned by the
+ * manager, valid until two later updates have retired it.  _update is the soft recompile: other values put the dynamic program back at once and start the
+ * new build (an overtaken build is not waited for); equal values change nothing.  The metric must outlive the manager.  One thread at a time. */
 typedef struct gr_program_manager gr_program_manager;
 int gr_program_manager_create(const gr_metric* m, int device, const gr_features* features, const float* cfg_values, int
                               num_cfg_values, gr_program_manager** out);
@@ -143,9 +140,8 @@ int gr_init_rays_generic(gr_program* p, void* stream, const void* camera_generic
                          int flip_geodesic_direction, const void* e0, const void* e1, const void* e2, const void* e3, const void*
                          cfg, const void* dfg, int i_am_prepass, int tiled);
 int gr_tiled_slot_count(int width, int height);
-/* do_generic_rays, cl.cl:3954-4247; execute_kernel main.cpp:139-205.  `num_rays` sizes the grid (the reference launches width*height
- * work-items); the device-side count is still honoured.  ray_time_min/max, ray_write, mouse_x/y: signature parity (triangle path,
- * unused).  attempt_counter (extension, may be NULL): device uint64 accumulating Verlet step attempts. */
+/* do_generic_rays, cl.cl:3954-4247; execute_kernel main.cpp:139-205.  `num_rays` sizes the grid (the reference launches width*height work-items); the device-side
+ * count is still honoured.  ray_time_min/max, ray_write, mouse_x/y: signature parity (triangle path, unused).  attempt_counter (extension, may be NULL): device uint64 of step attempts. */
 int gr_do_generic_rays(gr_program* p, void* stream, void* rays, const void* ray_count, int num_rays, void* ray_time_min, void*
                        ray_time_max, const void* cfg, const void* dfg, int width, int height, int mouse_x, int mouse_y, void*
                        ray_write, void* ray_write_counts, int max_write, void* attempt_counter);
@@ -216,9 +212,8 @@ typedef struct gr_frame_tuning gr_frame_tuning;   /* geodesic_hip_internal.h: wh
 typedef struct gr_frame_options {
     int mode;              /* GR_MODE_* */
     int tiled;             /* reference mode only: 8x8-tile ray order (ignored when adaptive sampling is on) */
-    int use_prepass;       /* -1: per metric config (metric_cfg.use_prepass), 0 / 1 force it off / on for this frame; -2: per metric config
-                            * and - whole frames on the fused path - only while it skips >= 2 % of the pixels (not output-neutral where
-                            * the reference is not either: a skipped pixel is black by decree) */
+    int use_prepass;       /* -1: per metric config (metric_cfg.use_prepass), 0 / 1 force it off / on for this frame; -2: per metric config and - whole frames on the
+                            * fused path - only while it skips >= 2 % of the pixels (not output-neutral where the reference is not either: a skipped pixel is black) */
     int max_probes;        /* anisotropy, graphics_settings.hpp:34 (8) */
     int strip_rank;        /* fused mode, multi-GPU: image rows are dealt in blocks of block_rows rows,          */
     int strip_count;       /*   global block b belongs to device b % strip_count (1 = whole image on this device) */
@@ -258,9 +253,9 @@ enum { GR_STAGE_CAMERA = 0, GR_STAGE_PREPASS = 1, GR_STAGE_INIT = 2, GR_STAGE_TR
 /* elapsed milliseconds of a stage of the last timed frame (synchronises on the stage's stop event) */
 int gr_render_state_stage_ms(gr_render_state* s, int stage, float* ms);
 
-/* Camera on a timelike geodesic, object form of main.cpp:2675-2760: _snapshot launches cart_to_generic, init_basis_vectors, boost_tetrad,
- * init_inertial_ray, get_geodesic_path and four parallel_transport_quantity on `stream`, then synchronises once to report the number of
- * samples and the proper time the path covers.  geodesic_basis_speed is g_geodesic_basis_speed (main.cpp:2253-2261), |v| < 1. */
+/* Camera on a timelike geodesic, object form of main.cpp:2675-2760: _snapshot launches cart_to_generic, init_basis_vectors, boost_tetrad, init_inertial_ray,
+ * get_geodesic_path and four parallel_transport_quantity on `stream`, then synchronises once to report the number of samples and the proper time the path
+ * covers.  geodesic_basis_speed is g_geodesic_basis_speed (main.cpp:2253-2261), |v| < 1. */
 int gr_geodesic_camera_create(int device, int max_path_length, gr_geodesic_camera** out);
 void gr_geodesic_camera_destroy(gr_geodesic_camera* g);
 int gr_geodesic_camera_snapshot(gr_geodesic_camera* g, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
@@ -283,24 +278,24 @@ int gr_stream_destroy(void* stream);
 int gr_device_count(int* count);
 
 /* ---- one frame over several GPUs (the reference is single-GPU) ------------------------------------------
- * Image rows are dealt to `world` participants in blocks of block_rows rows, block-cyclically; each renders its share with
- * gr_render_frame's strip mode (own prepass cells, one halo row per block, nothing exchanged while tracing) and the finished float4
- * rows go to participant 0, every block straight to its rows of the frame.  gr_render_frame_tiled = gr_render_frame for the share +
- * that transfer (`options` as there; mode, strip_* and compact_out are overridden).  `rotation`: participant r renders share
- * (r + rotation) % world - rotate with the frame number to even out shares of different cost.  frame_on_root: float4[height * width]
- * on participant 0's device (NULL elsewhere, except with peer copies: the same pointer for everybody).  Frames may be in flight on
- * several streams: a participant stages its rows in a ring of GR_TILED_STAGING (4) buffers.
+ * Image rows are dealt to `world` participants in blocks of block_rows rows, block-cyclically; each renders its share in gr_render_frame's
+ * strip mode (own prepass cells, one halo row per block, nothing exchanged while tracing) and the finished rows go to participant 0, every
+ * block straight to its rows of the frame.  gr_render_frame_tiled = gr_render_frame for the share + that transfer (`options` as there; mode,
+ * strip_* and compact_out are overridden).  `rotation`: participant r renders share (r + rotation) % world - rotate with the frame number
+ * to even out shares of different cost.  frame_on_root: float4[height * width] on participant 0's device (NULL elsewhere, except with peer
+ * copies: the same pointer for everybody).  Frames may be in flight on several streams: rows are staged in a ring of GR_TILED_STAGING (4) buffers.
  *   GR_TRANSPORT_RCCL    one process per GPU; participant 0 hands gr_tiled_unique_id's 128 bytes to the others, gr_tiled_create is
  *                        collective; per frame one group of ncclSend (owner) / ncclRecv (participant 0) per block.  librccl is dlopen'ed.
  *   GR_TRANSPORT_PEER    one process driving several devices (gr_tiled_create_local): hipMemcpyPeerAsync per block; gr_tiled_join
  *                        makes participant 0's stream wait for every frame issued so far.
  *   GR_TRANSPORT_CUSTOM  the caller's point-to-point library behind a gr_transport table, called in RCCL's pattern.
- *   GR_TRANSPORT_IPC     one process per participant, participants may share a device (RCCL refuses that): the same calls in the same
- *                        order over inter-process memory handles, matched in a shared-memory mailbox named after `session`; blocks
- *                        the host at the end of a group - a rehearsal stage for boxes with fewer GPUs than ranks, not a product path. */
+ *   GR_TRANSPORT_IPC     one process per participant, participants may share a device (RCCL refuses that): the same calls in the same order
+ *                        over inter-process memory handles and a shared-memory mailbox named after `session`; blocks the host at the end
+ *                        of a group - a rehearsal stage for boxes with fewer GPUs than ranks, not a product path. */
 typedef struct gr_tiled gr_tiled;
 enum { GR_TRANSPORT_RCCL = 0, GR_TRANSPORT_PEER = 1, GR_TRANSPORT_CUSTOM = 2, GR_TRANSPORT_IPC = 3 };
-/* the point-to-point calls a split frame needs (the subset of RCCL it uses); group_begin / group_end may be NULL */
+/* the point-to-point calls a split frame needs (the subset of RCCL it uses); group_begin / group_end may be NULL.  float_count counts 4-byte
+ * WORDS: floats of a GR_FRAME_F32 block (4 a pixel), RGBA8 pixels of a GR_FRAME_RGBA8 block (1 a pixel) - move them as they are */
 typedef struct gr_transport {
     void* user;
     int (*group_begin)(void* user);
@@ -317,22 +312,27 @@ void gr_tiled_destroy(gr_tiled* t);
 int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
                           const gr_features* features, const float* cfg_values, int num_cfg_values, const void* background1, const void* background2,
                           int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation);
+/* The same in either format, for a state of any supersampling factor (gr_render_frame_tiled: GR_FRAME_F32 at factor 1 only).  Every share is
+ * traced at factor x, resolved on its own device, and leaves it as width x rows pixels: float4, or (GR_FRAME_RGBA8: the share goes through
+ * gr_render_frame_rgba8, frame_on_root is width*height*4 bytes) 4 bytes a pixel.  Frames of both formats may share a participant's ring. */
+enum { GR_FRAME_F32 = 0, GR_FRAME_RGBA8 = 1 };
+int gr_render_frame_tiled_as(gr_tiled* t, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
+                             const gr_features* features, const float* cfg_values, int num_cfg_values, const void* background1, const void* background2,
+                             int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation, int format);
 int gr_tiled_join(gr_tiled* root, void* stream);
 /* the share participant t renders in a frame with this rotation */
 int gr_tiled_share(const gr_tiled* t, int rotation);
-/* A caller that cycles through n render states (n frames in flight) and passes options->next_camera says so here: the look-ahead frame of a
- * call with rotation k is then the frame of rotation k + n (next_camera2: k + 2 n), and gr_render_frame_tiled computes its prepass for the
- * share the participant will have by then.  Default 1. */
+/* A caller that cycles through n render states (n frames in flight) and passes options->next_camera says so here: the look-ahead frame of a call with
+ * rotation k is then that of rotation k + n (next_camera2: k + 2 n), whose prepass is computed for the share the participant has by then.  Default 1. */
 int gr_tiled_look_ahead(gr_tiled* t, int rotations);
 
 /* ---- host helper: background image ----------------------------------------------------------- */
 /* load_mipped_image (graphics_settings.cpp:152-212): an RGBA8 image and its box-filtered mip chain in `levels` same-size slices (mip i
  * in the top-left corner of slice i, edge replicated).  Returns the number of levels; out needs levels*width*height*4 bytes (NULL asks). */
 int gr_pack_mipped_background(const unsigned char* rgba, int width, int height, unsigned char* out);
-/* The same bytes made on the device (p: any program; its set-up module holds the kernels): rgba8 (device, width*height*4 bytes) -> packed_out
- * (device, levels*width*height*4 bytes), asynchronous on `stream`; scratch: _scratch_bytes' answer (0 for a one-level image), device.  rgba8 ==
- * packed_out is allowed (the image was uploaded into slice 0, which is left as it is).  Refused before any device call: any other overlap of
- * the three, a NULL, a short scratch, more than 1.7e9 texels, rgba8 not aligned to 4 bytes, packed_out or scratch not to 16.  Returns levels. */
+/* The same bytes made on the device (p: any program; its set-up module holds the kernels): rgba8 (device, width*height*4 bytes) -> packed_out (device, levels*width*height*4
+ * bytes), asynchronous on `stream`; scratch: _scratch_bytes' answer (0 for a one-level image), device.  rgba8 == packed_out is allowed (the image was uploaded into slice 0, which
+ * stays).  Refused before any device call: any other overlap of the three, a NULL, a short scratch, more than 1.7e9 texels, rgba8 not aligned to 4 bytes, packed_out or scratch not to 16.  Returns levels. */
 int gr_mipped_background_scratch_bytes(int width, int height, size_t* bytes);
 int gr_build_mipped_background(gr_program* p, void* stream, const void* rgba8, int width, int height, void* packed_out, void* scratch, size_t scratch_bytes);
 

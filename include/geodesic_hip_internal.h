@@ -420,6 +420,10 @@ int gr_render_state_counters(gr_render_state* s, unsigned long long* words, int 
 /* the transfer step of gr_render_frame_tiled on its own: `staging` = this participant's compact rows (blocks back to back,
  * gr_tiled_staging_bytes; unused on participant 0), frame_on_root as there */
 int gr_tiled_exchange(gr_tiled* t, const void* staging, void* frame_on_root, int rotation, void* stream);
+/* the same for a frame of either format (gr_render_frame_tiled_as; gr_tiled_exchange is its GR_FRAME_F32 case): rows of a GR_FRAME_RGBA8
+ * frame are width * 4 bytes, in frame_on_root and in the staged blocks alike - block i of this participant at i * block_rows * width * 4,
+ * so a byte frame fills the first quarter of gr_tiled_staging_bytes - and a gr_transport is handed width * rows words per block */
+int gr_tiled_exchange_as(gr_tiled* t, const void* staging, void* frame_on_root, int rotation, void* stream, int format);
 size_t gr_tiled_staging_bytes(const gr_tiled* t);
 /* rows [row_begin, row_end) of the local_block-th block of a share; returns 1, 0 for a padding block past the image, -1 on bad
  * arguments.  Pure arithmetic: global block = local_block * world + share. */
