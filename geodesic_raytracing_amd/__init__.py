@@ -122,6 +122,7 @@ class Transport(ctypes.Structure):
 
 MODE_REFERENCE, MODE_FUSED = 0, 1
 FRAME_F32, FRAME_RGBA8 = 0, 1
+YUV420_I420, YUV420_NV12 = 0, 1   # GR_YUV420_*: the layouts of an 8-bit Y'CbCr 4:2:0 frame (include/geodesic_hip.h, "video frames")
 EVAL_METRIC_TENSOR, EVAL_METRIC_DERIVATIVES, EVAL_ACCELERATION, EVAL_TO_POLAR, EVAL_FROM_POLAR, EVAL_ORIGIN_DISTANCE = range(6)
 (STAGE_CAMERA, STAGE_PREPASS, STAGE_INIT, STAGE_TRACE, STAGE_RENDER_DATA, STAGE_ADAPTIVE, STAGE_RENDER) = range(7)
 STAGE_NAMES = ["camera", "prepass", "init", "trace", "render_data", "adaptive", "render"]
@@ -238,6 +239,7 @@ _SIGNATURES = {
     "gr_render_state_resolve_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     "gr_resolve_supersampled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "gr_present_rgba8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "gr_present_yuv420": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
     "gr_srgb8_thresholds": (c_int, [ctypes.POINTER(c_float)]),
     "gr_mipped_background_scratch_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "gr_build_mipped_background": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t]),
@@ -248,6 +250,9 @@ _SIGNATURES = {
     "gr_render_frame_rgba8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
                                       ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                       ctypes.POINTER(FrameOptions)]),
+    "gr_render_frame_yuv420": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
+                                       ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                       ctypes.POINTER(FrameOptions)]),
     "gr_geodesic_camera_create": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p)]),
     "gr_geodesic_camera_destroy": (None, [c_void_p]),
     "gr_geodesic_camera_snapshot": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(c_float),
@@ -304,6 +309,11 @@ _SIGNATURES = {
     "gr_write_frame_png": (c_int, [c_char_p, c_void_p, c_int, c_int]),
     "gr_write_png_rgba8": (c_int, [c_char_p, c_void_p, c_int, c_int]),
     "gr_read_png_rgba8": (c_int, [c_char_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_size_t]),
+    "gr_yuv420_bytes": (c_size_t, [c_int, c_int]),
+    "gr_rgba8_to_yuv420": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gr_y4m_open": (c_int, [c_char_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "gr_y4m_write_frame": (c_int, [c_void_p, c_void_p]),
+    "gr_y4m_close": (c_int, [c_void_p]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():
@@ -325,4 +335,5 @@ def check(rc):
 
 
 from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, build_background,  # noqa: E402,F401
-                       default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background)
+                       default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background, rgba8_to_yuv420,
+                       yuv420_bytes, Y4MWriter)

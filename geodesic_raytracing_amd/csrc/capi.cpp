@@ -98,20 +98,20 @@ const char* const KERNEL_NAMES[] = {
     "gr_do_generic_rays", "gr_calculate_singularities", "gr_calculate_render_data",
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
-    "gr_background_reduce", "gr_background_slices"};
+    "gr_background_reduce", "gr_background_slices", "gr_present_yuv420"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_COUNT
 };
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
-// filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB encode (kernels/present.hip) and the sky's mip slices
+// filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
 // (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
-           k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES;
+           k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420;
 }
 
 std::vector<std::string> split_arguments(const std::string& s) {
@@ -1519,6 +1519,24 @@ int gr_present_rgba8(gr_program* p, void* stream, const void* src, void* dst_rgb
     int local_rows = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_rows;
     void* args[] = {&src, &dst_rgba8, &width, &height, &factor, &block_rows, &strip_rank, &strip_count, &compact_out, &local_rows};
     return launch(p, K_PRESENT_RGBA8, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
+}
+
+// gr_present_rgba8's resolve and encode, then BT.709 Y'CbCr 4:2:0 (kernels/present.hip): a lane per 2 rows x 4 columns, a workgroup of
+// 64 x 4 lanes on 256 columns x 8 rows.  Whole frames only.  Everything is refused before the first device call.
+int gr_present_yuv420(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout) {
+    const char* who = "gr_present_yuv420";
+    GR_NEED(who, src, dst);
+    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": null program");
+    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": factor " + std::to_string(factor) + " (1 to 4)");
+    if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the frame's size");
+    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": layout " + std::to_string(layout) + " (GR_YUV420_I420 or GR_YUV420_NV12)");
+    if ((uintptr_t)dst % 4) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": dst must be aligned to 4 bytes");
+    const unsigned gx = blocks(((long long)width + 3) / 4, 64), gy = blocks(((long long)height + 1) / 2, 4);
+    if (gy > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a frame of " + std::to_string(height) + " rows does not fit the grid");
+    void* args[] = {&src, &dst, &width, &height, &factor, &layout};
+    return launch(p, K_PRESENT_YUV420, stream, gx, gy, 64, 4, args);
 }
 
 // ---- the sky's mip slices on the device (kernels/background.hip) ------------------------------------

@@ -1634,4 +1634,43 @@ int gr_render_frame_rgba8(gr_render_state* s, gr_program* p, const gr_metric* m,
     return GR_OK;
 }
 
+// gr_render_frame_rgba8 with gr_present_yuv420 as the one launch after the frame: the state's traced frame -> BT.709 Y'CbCr 4:2:0 planes
+// in the caller's memory.  Whole frames only.  Everything the launch itself would refuse is refused here, before the frame is rendered
+// (and before a factor-1 state allocates its traced frame).
+int gr_render_frame_yuv420(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
+                           const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height,
+                           int bg_levels, void* out_yuv420, int layout, const gr_frame_options* options) {
+    if (!s || !p || !m || !camera || !out_yuv420) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: null argument");
+    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: layout (GR_YUV420_I420 or GR_YUV420_NV12)");
+    if ((uintptr_t)out_yuv420 % 4) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: out_yuv420 must be aligned to 4 bytes");
+    gr_frame_options opt;
+    gr_frame_options_default(&opt);
+    if (options) opt = *options;
+    if (opt.strip_count > 1)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: whole frames only (strip_count > 1); a split frame travels as float4 or "
+                                                           "RGBA8: gr_render_frame_tiled_as");
+    s->resolve_timed = false;
+    const int factor = s->supersample;
+    if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: block_rows");
+    opt.block_rows *= factor;
+    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out_yuv420));
+    if (!s->traced_frame) {   // a factor-1 state's first encoded frame (nothing is allocated for a call that is refused)
+        HIP_CHECK(hipSetDevice(s->device));
+        HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
+        for (auto& ev : s->ev_resolve)
+            if (!ev) HIP_CHECK(hipEventCreate(&ev));
+    }
+    GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
+                                 s->traced_frame, &opt));
+    const bool timed = opt.time_kernels == 1;
+    if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
+    GR_CHECK(gr_present_yuv420(p, stream, s->traced_frame, out_yuv420, s->out_width, s->out_height, factor, layout));
+    if (timed) {
+        HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
+        s->resolve_timed = true;
+    }
+    return GR_OK;
+}
+
 }  // extern "C"

@@ -1,4 +1,5 @@
-// imageio.cpp — PNG in/out for the headless renderer (host side, not on the hot path).
+// imageio.cpp — PNG in/out for the headless renderer (host side, not on the hot path), and video frames: the host statement of the
+// 8-bit Y'CbCr 4:2:0 encode (gr_rgba8_to_yuv420, which kernels/present.hip's gr_present_yuv420 is held to) and a YUV4MPEG2 writer.
 //
 // Reference counterparts: the screenshot path main.cpp:2762-2808 (read the float4 frame, clamp, linear -> sRGB,
 // clamp, 8-bit, PNG through sf::Image) and the background loader graphics_settings.cpp:214-243 (sf::Image from a
@@ -6,6 +7,7 @@
 // writer = RGBA8, filter 0; reader = 8-bit greyscale / RGB / RGBA / palette, non-interlaced, all five filters.
 #include <zlib.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -196,6 +198,98 @@ int gr_read_png_rgba8(const char* path, int* width, int* height, unsigned char* 
         prev.swap(cur);
     }
     return GR_OK;
+}
+
+// ---- video frames (include/geodesic_hip.h says all of it: formulas, siting, layouts, the stream's format) ----------------------------
+
+size_t gr_yuv420_bytes(int width, int height) {
+    if (width < 1 || height < 1) return 0;
+    const size_t cw = ((size_t)width + 1) / 2, ch = ((size_t)height + 1) / 2;
+    return (size_t)width * height + 2 * cw * ch;
+}
+
+// BT.709, limited range, 16 fractional bits, int32 throughout (the largest intermediate is 28784 * 1020 + 131072 < 2^25); each chroma
+// row sums to zero, so a grey block gives 128 exactly.  A missing column or row of the last block is the edge pixel itself.
+int gr_rgba8_to_yuv420(const unsigned char* rgba8, int width, int height, int layout, unsigned char* out) {
+    if (!rgba8 || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_rgba8_to_yuv420: null argument");
+    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_rgba8_to_yuv420: the frame's size");
+    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_rgba8_to_yuv420: layout (GR_YUV420_I420 or GR_YUV420_NV12)");
+    const size_t w = (size_t)width, h = (size_t)height, cw = (w + 1) / 2, ch = (h + 1) / 2;
+    for (size_t i = 0; i < w * h; i++) {
+        const int32_t r = rgba8[4 * i], g = rgba8[4 * i + 1], b = rgba8[4 * i + 2];
+        out[i] = (unsigned char)(16 + ((11966 * r + 40254 * g + 4064 * b + 32768) >> 16));
+    }
+    unsigned char* chroma = out + w * h;
+    for (size_t cy = 0; cy < ch; cy++)
+        for (size_t cx = 0; cx < cw; cx++) {
+            int32_t sr = 0, sg = 0, sb = 0;
+            for (size_t j = 0; j < 2; j++)
+                for (size_t i = 0; i < 2; i++) {
+                    const size_t x = std::min(2 * cx + i, w - 1), y = std::min(2 * cy + j, h - 1);
+                    const unsigned char* px = rgba8 + 4 * (y * w + x);
+                    sr += px[0]; sg += px[1]; sb += px[2];
+                }
+            const unsigned char cb = (unsigned char)(128 + ((-6596 * sr - 22188 * sg + 28784 * sb + 131072) >> 18));
+            const unsigned char cr = (unsigned char)(128 + ((28784 * sr - 26145 * sg - 2639 * sb + 131072) >> 18));
+            if (layout == GR_YUV420_NV12) {
+                chroma[2 * (cy * cw + cx)] = cb;
+                chroma[2 * (cy * cw + cx) + 1] = cr;
+            } else {
+                chroma[cy * cw + cx] = cb;
+                chroma[cw * ch + cy * cw + cx] = cr;
+            }
+        }
+    return GR_OK;
+}
+
+struct gr_y4m {
+    FILE* file;          // NULL after a short write: the handle then only waits for gr_y4m_close
+    size_t frame_bytes;
+    std::string path;
+};
+
+// all of `bytes`, flushed; on a short write the file is closed and the handle keeps none
+static int y4m_put(gr_y4m* y, const void* data, size_t bytes, const char* what) {
+    if (fwrite(data, 1, bytes, y->file) == bytes && fflush(y->file) == 0) return GR_OK;
+    fclose(y->file);
+    y->file = nullptr;
+    return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string("gr_y4m: short write of ") + what + " to " + y->path).c_str());
+}
+
+int gr_y4m_open(const char* path, int width, int height, int fps_num, int fps_den, gr_y4m** out) {
+    if (out) *out = nullptr;
+    if (!path || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_y4m_open: null argument");
+    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_y4m_open: the frame's size");
+    if (fps_num < 1 || fps_den < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_y4m_open: the frame rate fps_num / fps_den needs both parts >= 1");
+    FILE* f = fopen(path, "wb");
+    if (!f) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string("gr_y4m_open: cannot write ") + path).c_str());
+    gr_y4m* y = new gr_y4m{f, gr_yuv420_bytes(width, height), path};
+    const std::string header = "YUV4MPEG2 W" + std::to_string(width) + " H" + std::to_string(height) + " F" + std::to_string(fps_num) + ":" +
+                               std::to_string(fps_den) + " Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n";
+    const int rc = y4m_put(y, header.data(), header.size(), "the header");
+    if (rc != GR_OK) { delete y; return rc; }
+    *out = y;
+    return GR_OK;
+}
+
+int gr_y4m_write_frame(gr_y4m* y, const unsigned char* i420) {
+    if (!y || !i420) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_y4m_write_frame: null argument");
+    if (!y->file) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_y4m_write_frame: " + y->path + " was closed by a failed write").c_str());
+    if (fwrite("FRAME\n", 1, 6, y->file) != 6) {
+        fclose(y->file);
+        y->file = nullptr;
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_y4m: short write of a frame to " + y->path).c_str());
+    }
+    return y4m_put(y, i420, y->frame_bytes, "a frame");
+}
+
+int gr_y4m_close(gr_y4m* y) {
+    if (!y) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_y4m_close: null argument");
+    const bool complete = y->file && fclose(y->file) == 0;
+    const std::string path = y->path;
+    delete y;
+    return complete ? GR_OK : gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_y4m_close: " + path + " is incomplete (a write failed)").c_str());
 }
 
 }  // extern "C"

@@ -62,3 +62,103 @@ extern "C" __global__ void __launch_bounds__(256) gr_present_rgba8(const float4*
     // bytes R, G, B, A in memory order
     out[(size_t)at * width + x] = srgb8_of(tree, pixel.x) | (srgb8_of(tree, pixel.y) << 8) | (srgb8_of(tree, pixel.z) << 16) | (srgb8_of(tree, pixel.w) << 24);
 }
+
+// ------------------------------------------------------------------------------------------------
+// gr_present_yuv420 - the same chain in a third format: resolve -> sRGB bytes -> 8-bit BT.709 Y'CbCr, limited range, chroma subsampled
+// 2 x 2 (centre sited: the average of the four ENCODED pixels), as csrc/imageio.cpp states it on the host (gr_rgba8_to_yuv420; the
+// formulas and the layouts are in include/geodesic_hip.h).  The R, G, B bytes are gr_present_rgba8's: box_average<F> and srgb8_of above,
+// over the same table; alpha is not encoded.  The matrix is 32-bit integer arithmetic with arithmetic shifts - no float after the bytes -
+// so the launch can be held to the host function byte for byte.  Whole frames only (no strips: 1.5 bytes a pixel in planes do not fit the
+// exchange of a split frame).
+//
+// Shape: a lane owns 2 rows x 4 columns, so each of its two chroma samples is formed in registers - no second pass, no LDS exchange, no
+// atomics.  A workgroup is 64 x 4 as above: lane x of 64 on columns 4 x ... 4 x + 3, a wave along one row PAIR - 256 columns, and a
+// workgroup on 256 columns x 8 rows.  Per source row a lane reads 4 f consecutive float4 and a wave 4 KiB f contiguously; a wave writes
+// 256 contiguous bytes to each of its two luma rows and 128 to each chroma plane (256 to NV12's one).  Where width % 4 == 0 (every
+// video size; dst is aligned to 4 bytes, the launcher refuses anything else) every group of a lane is one store: 4 bytes a luma row,
+// 2 bytes a chroma plane or 4 bytes of NV12 - the alignment follows from width % 4 == 0 for every plane offset.  Any other width
+// stores byte by byte.  A pixel past the right or bottom edge is the edge pixel itself (x and y are clamped BEFORE the read: nothing is
+// read outside the source), which is the definition's rule for an odd width or height; what lies past the edge is not stored.
+// The table is copied and the barrier met before any lane leaves, as in gr_present_rgba8.  No claim about its speed is made here:
+// tools/present_yuv_probe.py times it against gr_present_rgba8 on the same source, and DESIGN.md ("Video frames") says what that gave.
+
+#define GR_YUV420_I420 0
+#define GR_YUV420_NV12 1
+
+template <int F>
+__device__ __forceinline__ void present_yuv420_lane(const float* tree, const float4* __restrict__ source, unsigned char* __restrict__ out,
+                                                    int width, int height, int layout, int x0, int y0) {
+    const size_t source_width = (size_t)width * F;
+    unsigned int luma[2][4];
+    int sum_r[2] = {0, 0}, sum_g[2] = {0, 0}, sum_b[2] = {0, 0};   // of the 2 x 2 block behind chroma sample 0 and 1 of this lane
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int y = min(y0 + j, height - 1);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int x = min(x0 + i, width - 1);
+            const float4 pixel = box_average<F>(source + (size_t)y * F * source_width + (size_t)x * F, source_width);
+            const int r = (int)srgb8_of(tree, pixel.x), g = (int)srgb8_of(tree, pixel.y), b = (int)srgb8_of(tree, pixel.z);
+            luma[j][i] = (unsigned int)(16 + ((11966 * r + 40254 * g + 4064 * b + 32768) >> 16));
+            sum_r[i / 2] += r;
+            sum_g[i / 2] += g;
+            sum_b[i / 2] += b;
+        }
+    }
+    unsigned int cb[2], cr[2];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        cb[k] = (unsigned int)(128 + ((-6596 * sum_r[k] - 22188 * sum_g[k] + 28784 * sum_b[k] + 131072) >> 18));
+        cr[k] = (unsigned int)(128 + ((28784 * sum_r[k] - 26145 * sum_g[k] - 2639 * sum_b[k] + 131072) >> 18));
+    }
+    const size_t chroma_width = (size_t)((width + 1) / 2), chroma_height = (size_t)((height + 1) / 2);
+    unsigned char* chroma = out + (size_t)width * height;   // both layouts: the chroma follows the luma plane
+    const size_t cx = (size_t)(x0 / 2), cy = (size_t)(y0 / 2);
+    if ((width & 3) == 0) {   // (uniform) x0 + 3 < width, every plane offset below is a multiple of its store's size
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+            if (y0 + j < height)
+                *(unsigned int*)(out + (size_t)(y0 + j) * width + x0) = luma[j][0] | (luma[j][1] << 8) | (luma[j][2] << 16) | (luma[j][3] << 24);
+        if (layout == GR_YUV420_NV12) {
+            *(unsigned int*)(chroma + cy * 2 * chroma_width + 2 * cx) = cb[0] | (cr[0] << 8) | (cb[1] << 16) | (cr[1] << 24);
+        } else {
+            *(unsigned short*)(chroma + cy * chroma_width + cx) = (unsigned short)(cb[0] | (cb[1] << 8));
+            *(unsigned short*)(chroma + chroma_width * chroma_height + cy * chroma_width + cx) = (unsigned short)(cr[0] | (cr[1] << 8));
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (y0 + j < height && x0 + i < width) out[(size_t)(y0 + j) * width + x0 + i] = (unsigned char)luma[j][i];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        if (x0 + 2 * k >= width) continue;
+        if (layout == GR_YUV420_NV12) {
+            chroma[cy * 2 * chroma_width + 2 * (cx + k)] = (unsigned char)cb[k];
+            chroma[cy * 2 * chroma_width + 2 * (cx + k) + 1] = (unsigned char)cr[k];
+        } else {
+            chroma[cy * chroma_width + cx + k] = (unsigned char)cb[k];
+            chroma[chroma_width * chroma_height + cy * chroma_width + cx + k] = (unsigned char)cr[k];
+        }
+    }
+}
+
+extern "C" __global__ void __launch_bounds__(256) gr_present_yuv420(const float4* __restrict__ source, unsigned char* __restrict__ out, int width,
+                                                                    int height, int factor, int layout) {
+    __shared__ float tree[256];
+    const unsigned int lane = threadIdx.y * 64u + threadIdx.x;   // the launcher's workgroup is 64 x 4: one entry per lane
+    tree[lane] = __uint_as_float(GR_SRGB8_TREE_BITS[lane]);
+    __syncthreads();
+    const long long column = 4ll * ((long long)blockIdx.x * blockDim.x + threadIdx.x), row = 2ll * ((long long)blockIdx.y * blockDim.y + threadIdx.y);
+    if (column >= width || row >= height) return;
+    const int x0 = (int)column, y0 = (int)row;
+    switch (factor) {
+        case 1: present_yuv420_lane<1>(tree, source, out, width, height, layout, x0, y0); break;
+        case 2: present_yuv420_lane<2>(tree, source, out, width, height, layout, x0, y0); break;
+        case 3: present_yuv420_lane<3>(tree, source, out, width, height, layout, x0, y0); break;
+        case 4: present_yuv420_lane<4>(tree, source, out, width, height, layout, x0, y0); break;
+        default: return;
+    }
+}

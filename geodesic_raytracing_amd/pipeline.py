@@ -1,10 +1,11 @@
 """Thin object layer over the C ABI: Metric, Program, RenderState (host mirror of the reference's
 metric_manager / render_state roles).  All compute happens inside libgeodesic_hip.so."""
 import ctypes
+import os
 
 import numpy as np
 
-from . import (Camera, Features, FrameOptions, FRAME_F32, FRAME_RGBA8, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
+from . import (Camera, Features, FrameOptions, FRAME_F32, FRAME_RGBA8, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
                c_size_t, c_void_p, check, lib)
 
 LIGHTRAY_DTYPE = np.dtype([("position", "<f4", 4), ("velocity", "<f4", 4), ("initial_quat", "<f4", 4),
@@ -395,9 +396,10 @@ class RenderState:
             lib.gr_render_state_destroy(self.handle)
             self.handle = None
 
-    def render(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None, rgba8=False):
+    def render(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None, rgba8=False,
+               yuv420=None):
         """Enqueue one frame. `out_ptr`: device pointer to float4[width*height] (or None to stop after render-data);
-        `background`: (device_ptr, width, height, levels) or ((ptr1, ptr2), width, height, levels)."""
+        `background`: (device_ptr, width, height, levels) or ((ptr1, ptr2), width, height, levels).  yuv420 = a layout: render_yuv420."""
         arr, n = None, 0
         if cfg_values is not None:
             n = len(cfg_values)
@@ -409,14 +411,26 @@ class RenderState:
             bg1, bg2 = ptrs if isinstance(ptrs, tuple) else (ptrs, ptrs)
         if features is None:
             features = metric.features()
+        options = ctypes.byref(options) if options is not None else None
+        if yuv420 is not None:
+            check(lib.gr_render_frame_yuv420(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n,
+                                             bg1, bg2, bw, bh, bl, out_ptr, int(yuv420), options))
+            return
         entry = lib.gr_render_frame_rgba8 if rgba8 else lib.gr_render_frame
         check(entry(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n, bg1, bg2, bw, bh, bl,
-                    out_ptr, ctypes.byref(options) if options is not None else None))
+                    out_ptr, options))
 
     def render_rgba8(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None):
         """render(), delivered as 8-bit sRGB (gr_render_frame_rgba8): `out_ptr` is a device pointer to width*height*4 bytes, R G B A, rows
         laid out as render() lays out its float rows; every byte is encode_srgb8's of the float render() writes (a NaN gives 0)."""
         self.render(program, metric, camera, out_ptr, background, features, cfg_values, options, stream, rgba8=True)
+
+    def render_yuv420(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None,
+                      layout=YUV420_I420):
+        """render(), delivered as 8-bit BT.709 Y'CbCr 4:2:0 (gr_render_frame_yuv420): `out_ptr` is a device pointer to
+        yuv420_bytes(width, height) bytes, aligned to 4, in `layout` (YUV420_I420: planes Y, Cb, Cr; YUV420_NV12: Y, then Cb Cr pairs);
+        every byte is rgba8_to_yuv420's of the frame render_rgba8() writes.  Whole frames only."""
+        self.render(program, metric, camera, out_ptr, background, features, cfg_values, options, stream, yuv420=layout)
 
     def prepass_policy(self):
         """(frames rendered with a prepass, frames the policy rendered without, fraction of cells the last inspected prepass marked)"""
@@ -550,6 +564,58 @@ def encode_srgb8(frame):
     if frame.size:
         check(lib.gr_frame_to_rgba8(frame.ctypes.data_as(c_void_p), frame.shape[1], frame.shape[0], out.ctypes.data_as(c_void_p)))
     return out
+
+
+def yuv420_bytes(width, height):
+    """the bytes of a width x height frame in 8-bit Y'CbCr 4:2:0, either layout: width*height + 2 * ((width+1)//2) * ((height+1)//2)"""
+    return int(lib.gr_yuv420_bytes(int(width), int(height)))
+
+
+def rgba8_to_yuv420(pixels, layout=YUV420_I420):
+    """The host statement of the video encode (gr_rgba8_to_yuv420; include/geodesic_hip.h gives the integer formulas): uint8 [H, W, 4] in
+    sRGB -> uint8 [yuv420_bytes(W, H)], BT.709 limited range, one chroma pair per 2 x 2 block (an odd edge counts twice), alpha dropped.
+    What gr_present_yuv420 computes on the device from the float frame, byte for byte."""
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+    if pixels.ndim != 3 or pixels.shape[2] != 4 or pixels.size == 0:
+        raise ValueError(f"rgba8_to_yuv420: a frame of shape {pixels.shape} is not [H, W, 4]")
+    h, w = pixels.shape[:2]
+    out = np.empty(yuv420_bytes(w, h), dtype=np.uint8)
+    check(lib.gr_rgba8_to_yuv420(pixels.ctypes.data_as(c_void_p), w, h, int(layout), out.ctypes.data_as(c_void_p)))
+    return out
+
+
+class Y4MWriter:
+    """An uncompressed YUV4MPEG2 file (gr_y4m_open / _write_frame / _close): one header line, then "FRAME\\n" + the I420 bytes per frame.
+    fps: an int, or (numerator, denominator).  Use as a context manager, or call close()."""
+
+    def __init__(self, path, width, height, fps=24):
+        num, den = fps if isinstance(fps, tuple) else (fps, 1)
+        self.frame_bytes = yuv420_bytes(width, height)
+        self.handle = c_void_p()
+        check(lib.gr_y4m_open(os.fsencode(path), int(width), int(height), int(num), int(den), ctypes.byref(self.handle)))
+
+    def write(self, i420):
+        i420 = np.ascontiguousarray(i420, dtype=np.uint8)
+        if i420.size != self.frame_bytes:
+            raise ValueError(f"Y4MWriter: a frame of {i420.size} bytes, {self.frame_bytes} expected")
+        check(lib.gr_y4m_write_frame(self.handle, i420.ctypes.data_as(c_void_p)))
+
+    def close(self):
+        handle, self.handle = getattr(self, "handle", None), None
+        if handle:
+            check(lib.gr_y4m_close(handle))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (a destructor has nobody to raise to; close() called by hand does raise)
+            pass
 
 
 def synthetic_background(width=1024, height=512, seed=0x5EED, stars=None):

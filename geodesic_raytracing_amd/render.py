@@ -10,6 +10,10 @@
     # camera riding its own timelike geodesic: 24 frames, 0.5 units of proper time apart -> fall_000.png .. fall_023.png
     python -m geodesic_raytracing_amd.render --metric schwarzschild --camera 0,0,-8,0 --geodesic-speed 0,0.3,0 \
         --geodesic-time 0 --geodesic-dt 0.5 --frames 24 --out fall.png
+    # the same fall as one video file: every frame leaves the device as 8-bit BT.709 Y'CbCr 4:2:0, 1.5 bytes a pixel, into uncompressed YUV4MPEG2
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --geodesic-speed 0,0.3,0 --frames 24 --out fall.y4m
+    # a camera that rides no geodesic: position and orientation interpolated from --camera / --quat to --camera-to / --quat-to over --frames
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --fps 30000/1001 --out pan.y4m
 """
 import argparse
 import ctypes
@@ -19,7 +23,7 @@ import sys
 import numpy as np
 
 import geodesic_raytracing_amd as gra
-from geodesic_raytracing_amd.pipeline import DeviceBuffer, PinnedBuffer, ProgramManager
+from geodesic_raytracing_amd.pipeline import DeviceBuffer, PinnedBuffer, ProgramManager, Y4MWriter, yuv420_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -45,18 +49,61 @@ def write_rgba8_png(path, pixels):
     gra.check(gra.lib.gr_write_png_rgba8(path.encode(), pixels.ctypes.data_as(ctypes.c_void_p), w, h))
 
 
+def parse_fps(text):
+    """'24' or '30000/1001' -> (numerator, denominator), both >= 1; ValueError otherwise"""
+    parts = str(text).split("/")
+    if len(parts) not in (1, 2):
+        raise ValueError(f"a frame rate of {text!r} is not N or N/D")
+    num, den = int(parts[0]), int(parts[1]) if len(parts) == 2 else 1
+    if num < 1 or den < 1:
+        raise ValueError(f"a frame rate of {text!r}: both parts are at least 1")
+    return num, den
+
+
+def camera_path(position, quat, position_to=None, quat_to=None, frames=1):
+    """`frames` poses from (position, quat) to (position_to, quat_to), both ends included: the position (t, x, y, z) linear, the quaternion
+    (x, y, z, w) a normalised slerp along the shorter arc.  An end that is None stays where the start is.  Returns [(position, quat)]."""
+    p0 = np.array(position if position is not None else gra.default_camera().position[:], dtype=np.float64)
+    q0 = np.array(quat if quat is not None else gra.default_camera().quat[:], dtype=np.float64)
+    p1 = p0 if position_to is None else np.array(position_to, dtype=np.float64)
+    q1 = q0 if quat_to is None else np.array(quat_to, dtype=np.float64)
+    if p0.shape != (4,) or p1.shape != (4,) or q0.shape != (4,) or q1.shape != (4,):
+        raise ValueError("camera_path: a position is t,x,y,z and a quaternion x,y,z,w")
+    if not np.linalg.norm(q0) > 0 or not np.linalg.norm(q1) > 0:
+        raise ValueError("camera_path: a quaternion of length zero")
+    q0, q1 = q0 / np.linalg.norm(q0), q1 / np.linalg.norm(q1)
+    if np.dot(q0, q1) < 0:
+        q1 = -q1
+    angle = np.arccos(min(1.0, float(np.dot(q0, q1))))
+    poses = []
+    for k in range(max(int(frames), 1)):
+        u = k / (frames - 1) if frames > 1 else 0.0
+        if angle < 1e-6:
+            q = (1 - u) * q0 + u * q1
+        else:
+            q = (np.sin((1 - u) * angle) * q0 + np.sin(u * angle) * q1) / np.sin(angle)
+        poses.append(([float(v) for v in (1 - u) * p0 + u * p1], [float(v) for v in q / np.linalg.norm(q)]))
+    return poses
+
+
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
-           parallel_transport=True, supersample=1, rgba8=False, mips="host"):
+           parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
     rgba8: the frames are uint8 [H, W, 4] in sRGB instead, encoded on the device (RenderState.render_rgba8) and fetched at 4 bytes a
     pixel through pinned memory - the bytes pipeline.encode_srgb8 makes of the float frame.
+    yuv420: the frames are uint8 [yuv420_bytes(W, H)] instead: 8-bit BT.709 Y'CbCr 4:2:0 in I420 order (planes Y, Cb, Cr), made on the device in
+    the launch that resolves and encodes (RenderState.render_yuv420) and fetched at 1.5 bytes a pixel through pinned memory - the bytes
+    pipeline.rgba8_to_yuv420 makes of the rgba8 frame.
+    cameras: [(position, quat)] (camera_path) - a list of frames, one per pose, of a camera that rides no geodesic (not with geodesic_speed).
     mips: where the sky's mip slices are made - "host" (pack_background, all slices uploaded) or "device" (build_background: the image is
     uploaded and the slices are built there, the same bytes)."""
     if mips not in ("host", "device"):
         raise ValueError(f"render: mips={mips!r} (host or device)")
+    if cameras is not None and geodesic_speed is not None:
+        raise ValueError("render: cameras (interpolated poses) and geodesic_speed (a camera on its geodesic) exclude each other")
     metric = gra.Metric(metric_name, scripts or os.path.join(HERE, "scripts"))
     feats = metric.features(adaptive_sampling=int(adaptive), redshift=int(redshift), field_of_view=fov, universe_size=universe)
     cfg_values = metric.cfg_values(**(cfg or {}))
@@ -69,23 +116,29 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     else:
         packed, levels = gra.pack_background(rgba)
         dbg = DeviceBuffer.from_numpy(device, packed)
-    out = DeviceBuffer(device, width * height * (4 if rgba8 else 16))
-    pinned = PinnedBuffer(width * height * 4) if rgba8 else None
+    out_bytes = yuv420_bytes(width, height) if yuv420 else width * height * (4 if rgba8 else 16)
+    out = DeviceBuffer(device, out_bytes)
+    pinned = PinnedBuffer(out_bytes) if rgba8 or yuv420 else None
     cam = gra.default_camera(camera_pos, camera_quat)
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
     bg = (dbg.ptr, rgba.shape[1], rgba.shape[0], levels)
 
-    def one_frame(options):
-        if not rgba8:
+    def one_frame(options, cam=cam):
+        if yuv420:
+            state.render_yuv420(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
+        elif rgba8:
+            state.render_rgba8(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
+        else:
             state.render(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
             state.synchronize()
             return out.to_numpy(np.float32, (height, width, 4))
-        state.render_rgba8(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
-        pinned.download_async(None, out.ptr, width * height * 4)   # the frame's stream: copies queue behind its launches
+        pinned.download_async(None, out.ptr, out_bytes)   # the frame's stream: copies queue behind its launches
         gra.check(gra.lib.gr_stream_synchronize(None))
-        return pinned.view(np.uint8, (height, width, 4)).copy()
+        return pinned.view(np.uint8, (out_bytes,) if yuv420 else (height, width, 4)).copy()
 
     def frames_of_the_call():
+        if cameras is not None:
+            return [one_frame(gra.frame_options(mode=mode), gra.default_camera(position, quat)) for position, quat in cameras]
         if geodesic_speed is None:
             return one_frame(gra.frame_options(mode=mode))
         gc = gra.GeodesicCamera(device=device)
@@ -170,6 +223,9 @@ def main(argv=None):
     ap.add_argument("--cfg", action="append", default=[], help="NAME=VALUE, a $cfg parameter of the metric (repeatable)")
     ap.add_argument("--camera", default=None, help="t,x,y,z")
     ap.add_argument("--quat", default=None, help="x,y,z,w")
+    ap.add_argument("--camera-to", default=None, help="t,x,y,z: the camera's position in the last of --frames frames; frame k is rendered from the "
+                    "position interpolated linearly between --camera and this (a camera that rides no geodesic; not with --geodesic-speed)")
+    ap.add_argument("--quat-to", default=None, help="x,y,z,w: the orientation in the last frame, reached from --quat by a normalised slerp")
     ap.add_argument("--fov", type=float, default=90.0)
     ap.add_argument("--universe", type=float, default=20.0)
     ap.add_argument("--redshift", action="store_true")
@@ -184,14 +240,28 @@ def main(argv=None):
     ap.add_argument("--supersample", type=int, choices=[1, 2, 3, 4], default=1, help="anti-aliasing: trace N x N rays per pixel of --size and "
                     "average them on the device (the output keeps the size given by --size)")
     ap.add_argument("--encode", choices=["host", "device"], default="host", help="where the frame becomes 8-bit sRGB: host = download float4 and "
-                    "convert there; device = encode on the GPU and download 4 bytes a pixel (the same bytes)")
+                    "convert there; device = encode on the GPU and download 4 bytes a pixel (the same bytes).  Ignored for --out NAME.y4m, "
+                    "whose frames are always encoded on the device")
     ap.add_argument("--mips", choices=["host", "device"], default="host", help="where the sky's mip slices are made: host = pack them on the CPU "
                     "and upload all of them; device = upload the image and build the slices on the GPU (the same bytes)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--devices", default=None, help="0,1,2,3: deal the rows of every frame to these GPUs (one process, peer copies; a device may "
                     "repeat); each traces, resolves and - with --encode device - encodes its share, the share rotating over --frames")
-    ap.add_argument("--out", required=True)
+    ap.add_argument("--fps", default="24", help="frame rate of a .y4m file: N or N/D (24; 30000/1001)")
+    ap.add_argument("--out", required=True, help="NAME.png: one PNG, or NAME_000.png ... for a sequence.  NAME.y4m: all frames in one uncompressed "
+                    "YUV4MPEG2 file of 8-bit BT.709 Y'CbCr 4:2:0 frames, converted on the device")
     a = ap.parse_args(argv)
+    video = a.out.lower().endswith(".y4m")
+    try:
+        fps = parse_fps(a.fps)
+    except ValueError as e:
+        ap.error(f"--fps: {e}")
+    if video and a.devices is not None:
+        ap.error("--out NAME.y4m with --devices: a split frame travels as float4 or RGBA8, not as 4:2:0 planes; render the video on one device")
+    if (a.camera_to or a.quat_to) and a.geodesic_speed:
+        ap.error("--camera-to / --quat-to with --geodesic-speed: the camera either follows the interpolated poses or rides its geodesic")
+    if (a.camera_to or a.quat_to) and a.devices is not None:
+        ap.error("--camera-to / --quat-to with --devices: a split sequence renders one camera")
     w, h = (int(v) for v in a.size.lower().split("x"))
     cfg = {k: float(v) for k, v in (kv.split("=") for kv in a.cfg)}
     speed = [float(v) for v in a.geodesic_speed.split(",")] if a.geodesic_speed else None
@@ -217,20 +287,32 @@ def main(argv=None):
             write(path, frame)
             print(f"wrote {path} ({w}x{h}, {len(devices)} participants, rotation {i})")
         return 0
-    result = render(a.metric, w, h, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
-                    [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, a.adaptive,
+    position, quat = ([float(v) for v in text.split(",")] if text else None for text in (a.camera, a.quat))
+    cameras = None
+    if a.camera_to or a.quat_to:
+        try:
+            cameras = camera_path(position, quat, [float(v) for v in a.camera_to.split(",")] if a.camera_to else None,
+                                  [float(v) for v in a.quat_to.split(",")] if a.quat_to else None, max(a.frames, 1))
+        except ValueError as e:
+            ap.error(f"--camera-to / --quat-to: {e}")
+    result = render(a.metric, w, h, a.scripts, cfg, position, quat, a.redshift, a.adaptive,
                     read_png(a.background) if a.background else None, a.device, a.fov, a.universe, geodesic_speed=speed,
-                    geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample, rgba8=a.encode == "device",
-                    mips=a.mips)
-    if speed is None:
-        write(a.out, result)
-        print(f"wrote {a.out} ({w}x{h})")
+                    geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
+                    rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras)
+    if speed is None and cameras is None:
+        result = [result]
+    if video:
+        with Y4MWriter(a.out, w, h, fps) as stream:
+            for frame in result:
+                stream.write(frame)
+        print(f"wrote {a.out} ({w}x{h}, {len(result)} frames at {fps[0]}/{fps[1]} a second, BT.709 Y'CbCr 4:2:0)")
         return 0
     stem, ext = os.path.splitext(a.out)
     for i, frame in enumerate(result):
         path = a.out if len(result) == 1 else f"{stem}_{i:03d}{ext}"
         write(path, frame)
-        print(f"wrote {path} ({w}x{h}, proper time {times[i]:.3f})")
+        print(f"wrote {path} ({w}x{h})" if speed is None and cameras is None else
+              f"wrote {path} ({w}x{h}, proper time {times[i]:.3f})" if cameras is None else f"wrote {path} ({w}x{h}, pose {i})")
     return 0
 
 

@@ -36,25 +36,21 @@ typedef struct gr_lightray {
     int terminated;            /* 0 = lost/absorbed, 1 = reached a boundary, 2 = skipped by the prepass */
     int sx, sy, pad_[3];
 } gr_lightray;
-
 /* struct render_data, cl.cl:5066-5074 / render_state.hpp:21-29; 32 bytes */
 typedef struct gr_render_data {
     float tex_coord[2], z_shift;
     int sx, sy, terminated, side, pad_;
 } gr_render_data;
-
 /* struct dynamic_feature_config as packed by dynamic_feature_config::alloc_and_write_gpu_buffer (dynamic_feature_config.cpp:182-237):
  * floats in alphabetical order, then bools as int. 48 bytes.  Defaults: main.cpp:1123-1158. */
 typedef struct gr_features {
     float adaptive_sampling_threshold, field_of_view, max_acceleration_change, max_precision_radius, min_step, ray_skip, universe_size;
     int adaptive_sampling, redshift, reparameterisation, use_old_redshift, use_triangle_rendering;
 } gr_features;
-
 void gr_features_default(gr_features* out);
 
 /* ---- host side: metric -> macro string ----------------------------------------------------- */
 typedef struct gr_metric gr_metric;
-
 /* per-metric settings that steer the frame driver (metrics::metric_config, metric.hpp:330-357) */
 typedef struct gr_metric_info {
     int is_big, is_constant_theta;   /* GENERIC_BIG_METRIC, GENERIC_CONSTANT_THETA */
@@ -63,14 +59,11 @@ typedef struct gr_metric_info {
     int num_dynamic_vars;            /* $cfg.NAME parameters */
     int accel_ops, accel_transcendentals, coord_ops;   /* DAG op counts of GEO_ACCEL0..3 and of TO_COORDn + DISTANCE_FUNC (roofline accounting) */
 } gr_metric_info;
-
 /* One of the built-in metrics: "minkowski", "schwarzschild", "kerr_boyer", "alcubierre". */
 int gr_metric_builtin(const char* name, gr_metric** out);
-
 /* Loads <scripts_dir>/<name>.json (+ one level of inherit_settings) and the scripts it names, exactly
  * as content_manager.cpp:9-112 does; the script dialect is the reference's (js_interop.cpp:665-959). */
 int gr_metric_load_script(const char* scripts_dir, const char* name, gr_metric** out);
-
 /* A metric that is only what gr_render_frame reads off one (gr_metric_info, the $cfg names and defaults), for a caller that already
  * holds the argument strings (a program cache, a fixture); gr_metric_argument_string fails on it.  var_names may be NULL. */
 int gr_metric_from_info(const gr_metric_info* info, const char* const* var_names, const float* var_defaults, gr_metric** out);
@@ -78,13 +71,11 @@ void gr_metric_destroy(gr_metric* m);
 int gr_metric_get_info(const gr_metric* m, gr_metric_info* out);
 const char* gr_metric_dynamic_var_name(const gr_metric* m, int index);
 float gr_metric_dynamic_var_default(const gr_metric* m, int index);
-
 /* metrics::build_argument_string (metric.hpp:725-959).  is_static = 0: "dynamic" program - expressions read cfg->NAME, features come
  * from the feature struct (KERNEL_IS_DYNAMIC); 1: "substituted" program - cfg_values (NULL = defaults) and `features` baked in as
  * literals (KERNEL_IS_STATIC, metric_manager.hpp:153-166).  *needed = capacity required incl. the NUL; buffer = NULL, capacity = 0 asks. */
 int gr_metric_argument_string(const gr_metric* m, const gr_features* features, int is_static, const float* cfg_values, int
                               num_cfg_values, char* buffer, size_t capacity, size_t* needed);
-
 /* The metric's generated expressions evaluated on the HOST at one point, in double: the symbolic graph the macro strings are printed from, interpreted -
  * no device, no compiler (BASELINE configs[0], SURVEY.md 7.2c: "CPU evaluator of generated metric code").  For a host that wants to look at a metric; not
  * a rendering path.  position = chart coordinates (v1..v4), velocity = their d/dlambda (iv1..iv4; NULL where unused), cfg_values NULL = defaults.  Writes
@@ -98,7 +89,6 @@ int gr_metric_evaluate(const gr_metric* m, int what, const double position[4], c
 
 /* ---- device program ------------------------------------------------------------------------- */
 typedef struct gr_program gr_program;
-
 /* cl::build_program_with_cache({"cl.cl"}, argument_string) (metric_manager.hpp:88-108): compiles the kernels for gfx950 specialised
  * by `argument_string` (the macro set above; macros of dead device code - CART_TO_POLn, FIX_LIGHTn, METRIC_TIME_G00 - are accepted
  * and ignored; -cl-fp32-correctly-rounded-divide-sqrt, OpenCL's own switch, is honoured) and loads them on HIP device `device`.
@@ -110,7 +100,6 @@ int gr_program_complete(gr_program* p);
 /* Compile only (no device needed): fills the on-disk cache; used by the build step. */
 int gr_program_precompile(const char* argument_string);
 void gr_program_destroy(gr_program* p);
-
 /* metric_manager (metric_manager.hpp:19-219) as an object.  _create builds the dynamic program of `m` (blocking, as the reference does for a newly
  * selected metric) and starts the substituted build for `features` / `cfg_values` (NULL = defaults) on a worker thread.  _current is check_substitution:
  * once per frame, swaps the substituted program in when its build has finished (wait != 0: waits) and hands back the program to launch - owned by the
@@ -187,7 +176,6 @@ int gr_handle_interpolating_geodesic(gr_program* p, void* stream, const void* ge
 
 /* ---- frame driver (the enqueue sequence of main.cpp:2244-2526) ------------------------------- */
 typedef struct gr_render_state gr_render_state;   /* render_state.hpp:97-197: all per-frame device buffers */
-
 /* camera, main.cpp:664-673: Cartesian (t,x,y,z) position, orientation quaternion (x,y,z,w) */
 typedef struct gr_camera gr_camera;
 struct gr_camera {
@@ -198,17 +186,13 @@ struct gr_camera {
 };
 /* pos (0,0,-4,0), axis-angle (1,0,0,-pi/2) */
 void gr_camera_default(gr_camera* out);
-
 enum {
     GR_MODE_REFERENCE = 0,   /* one launch per reference kernel, 96-byte ray records in HBM */
     GR_MODE_FUSED = 1        /* gr_prepass_fused + gr_trace_fused + gr_render */
 };
-
 /* The camera's own timelike geodesic on the device: the buffers of main.cpp:1232-1242 and the four parallel-transported tetrad legs */
 typedef struct gr_geodesic_camera gr_geodesic_camera;
-
 typedef struct gr_frame_tuning gr_frame_tuning;   /* geodesic_hip_internal.h: which fused kernel, schedule and launch size (defaults are right) */
-
 typedef struct gr_frame_options {
     int mode;              /* GR_MODE_* */
     int tiled;             /* reference mode only: 8x8-tile ray order (ignored when adaptive sampling is on) */
@@ -231,11 +215,9 @@ typedef struct gr_frame_options {
                                         * measurement switches live (geodesic_hip_internal.h) */
 } gr_frame_options;
 void gr_frame_options_default(gr_frame_options* out);
-
 int gr_render_state_create(int device, int width, int height, gr_render_state** out);
 int gr_render_state_create_supersampled(int device, int width, int height, int factor, gr_render_state** out);   /* frames of this state are traced at factor x per axis (graphics_settings.hpp:23-24) and box-averaged into out */
 void gr_render_state_destroy(gr_render_state* s);
-
 /* Renders one frame into out_rgba_f32 (device memory, always float4[width*height] of the state's constructor, supersampled or not; in
  * fused strip mode only this device's rows are written).  cfg_values = the $cfg parameters (NULL = metric defaults). */
 int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features*
@@ -246,13 +228,15 @@ int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void*
 int gr_render_frame_rgba8(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features*
                           features, const float* cfg_values, int num_cfg_values, const void* background1, const void* background2, int
                           bg_width, int bg_height, int bg_levels, void* out_rgba8, const gr_frame_options* options);
-
+/* The same frame as 8-bit BT.709 Y'CbCr 4:2:0 ("video frames" below), converted on the device by the ONE launch that resolves and encodes - no RGBA8 frame in between: gr_rgba8_to_yuv420's bytes of gr_render_frame_rgba8's frame.
+ * out_yuv420: device, width*height + 2*cw*ch bytes, aligned to 4.  Whole frames only: refused with options->strip_count > 1 (a split frame travels as F32 or RGBA8: gr_render_frame_tiled_as), like a NULL or an unknown layout before any device call. */
+int gr_render_frame_yuv420(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features, const float* cfg_values, int num_cfg_values, const void* background1,
+                           const void* background2, int bg_width, int bg_height, int bg_levels, void* out_yuv420, int layout, const gr_frame_options* options);
 /* stage timing of a frame rendered with options->time_kernels = 1 (the reference's -bench mode times frames on the host, main.cpp:2864-2871) */
 enum { GR_STAGE_CAMERA = 0, GR_STAGE_PREPASS = 1, GR_STAGE_INIT = 2, GR_STAGE_TRACE = 3, GR_STAGE_RENDER_DATA = 4,
        GR_STAGE_ADAPTIVE = 5, GR_STAGE_RENDER = 6, GR_STAGE_COUNT = 7 };
 /* elapsed milliseconds of a stage of the last timed frame (synchronises on the stage's stop event) */
 int gr_render_state_stage_ms(gr_render_state* s, int stage, float* ms);
-
 /* Camera on a timelike geodesic, object form of main.cpp:2675-2760: _snapshot launches cart_to_generic, init_basis_vectors, boost_tetrad, init_inertial_ray,
  * get_geodesic_path and four parallel_transport_quantity on `stream`, then synchronises once to report the number of samples and the proper time the path
  * covers.  geodesic_basis_speed is g_geodesic_basis_speed (main.cpp:2253-2261), |v| < 1. */
@@ -343,6 +327,22 @@ int gr_write_frame_png(const char* path, const float* frame_rgba_f32, int width,
 int gr_write_png_rgba8(const char* path, const unsigned char* rgba, int width, int height);
 /* 8-bit non-interlaced PNG -> RGBA8; call with out = NULL to query the size */
 int gr_read_png_rgba8(const char* path, int* width, int* height, unsigned char* out, size_t capacity);
+/* ---- video frames: 8-bit BT.709 Y'CbCr 4:2:0, limited range, and an uncompressed YUV4MPEG2 (.y4m) writer.  Input: the R, G, B bytes (sRGB-encoded, 0 ... 255) of an RGBA8 frame, alpha ignored.  int32 arithmetic, >> arithmetic (it floors):
+ *   per pixel  Y = 16 + ((11966*R + 40254*G + 4064*B + 32768) >> 16);   per 2 x 2 block, SR SG SB the sums of its four pixels' bytes:  Cb = 128 + ((-6596*SR - 22188*SG + 28784*SB + 131072) >> 18),  Cr = 128 + ((28784*SR - 26145*SG - 2639*SB + 131072) >> 18)
+ * Chroma: cw = (width+1)/2 by ch = (height+1)/2 samples, sample (i, j) over pixels (2i ... 2i+1, 2j ... 2j+1) and sited at their centre (the mean of the four ENCODED pixels: C420jpeg); an odd width / height counts the edge column / row twice.
+ * Layouts, width*height + 2*cw*ch bytes each (gr_yuv420_bytes), no padding: GR_YUV420_I420 = the Y plane (rows from the top), the Cb plane (ch rows of cw bytes), the Cr plane; GR_YUV420_NV12 = the Y plane, then ch rows of cw (Cb, Cr) byte pairs.
+ * BT.709 (Kr 0.2126, Kb 0.0722) at 16 fractional bits: Y = 16 + 219 E'y, Cb = 128 + 224 E'pb, Cr = 128 + 224 E'pr; a grey gives Cb = Cr = 128 exactly, Y is in [16, 235], Cb and Cr in [16, 240], each within 0.51 of a code of the real-valued
+ * formula.  To decode: E'y = (Y-16)/219, E'pb = (Cb-128)/224, E'pr = (Cr-128)/224;  R' = E'y + 1.5748 E'pr,  B' = E'y + 1.8556 E'pb,  G' = E'y - 0.18732 E'pb - 0.46812 E'pr: sRGB-ENCODED values in [0, 1] (IEC 61966-2-1's transfer function).
+ * rgba8: width*height*4 bytes; out: width*height + 2*cw*ch bytes, nothing else is written.  Refused: a NULL, a size below 1, an unknown layout. */
+enum { GR_YUV420_I420 = 0, GR_YUV420_NV12 = 1 };
+int gr_rgba8_to_yuv420(const unsigned char* rgba8, int width, int height, int layout, unsigned char* out);
+/* A .y4m file: the line "YUV4MPEG2 W<width> H<height> F<fps_num>:<fps_den> Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n" (progressive, square pixels), then per frame the six bytes "FRAME\n" + the frame's GR_YUV420_I420 bytes; nothing follows the
+ * last frame.  Y4M has no field that names the matrix: a player assumes BT.709 for HD sizes (and usually BT.601 below 1280 x 720).  _open refuses a NULL, a size or a part of the frame rate below 1, a path it cannot create; *out is then NULL.
+ * A short write - header or frame - returns an error and closes the file: no handle stays open and later writes fail; _close is still owed (it frees the gr_y4m) and then reports the file incomplete.  i420: host memory. */
+typedef struct gr_y4m gr_y4m;
+int gr_y4m_open(const char* path, int width, int height, int fps_num, int fps_den, gr_y4m** out);
+int gr_y4m_write_frame(gr_y4m* y, const unsigned char* i420);
+int gr_y4m_close(gr_y4m* y);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,16 @@ int gr_resolve_supersampled(gr_program* p, void* stream, const void* src, void* 
  * any device call), same row dealing; factor 1 encodes src as it is. */
 int gr_present_rgba8(gr_program* p, void* stream, const void* src, void* dst_rgba8, int width, int height, int factor, int block_rows,
                      int strip_rank, int strip_count, int compact_out);
+/* gr_present_rgba8's resolve and encode followed by gr_rgba8_to_yuv420's integer matrix (geodesic_hip.h), in one launch of the same
+ * module: dst (device, gr_yuv420_bytes(width, height) bytes, layout GR_YUV420_I420 or GR_YUV420_NV12) holds exactly
+ * gr_rgba8_to_yuv420(gr_present_rgba8(src)); no RGBA8 frame is written.  src: float4, width*factor x height*factor; factor 1..4.  Whole
+ * frames only, every width and height >= 1 (width % 4 == 0 stores 4 bytes at a time, any other width single bytes).  Refused before any
+ * device call: a NULL (the program included), a factor outside 1..4, a size below 1 or with more than 2^31 - 1 source pixels or more
+ * than 524 280 rows, an unknown layout, dst not aligned to 4 bytes. */
+int gr_present_yuv420(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout);
+/* The bytes of a width x height frame in 8-bit Y'CbCr 4:2:0, either layout: width*height + 2 * ((width+1)/2) * ((height+1)/2), as geodesic_hip.h
+ * ("video frames") gives it; 0 for a size below 1.  (Here and not there only because the contract header keeps to 80 names: the formula is public.) */
+size_t gr_yuv420_bytes(int width, int height);
 /* What defines that encode: out[k] = the smallest float of [0, 1] whose byte under gr_frame_to_rgba8 is >= k (out[0] = 0; +infinity for a
  * k no input reaches), found by bisection with the host function itself.  byte(c) = the largest k with out[k] <= c; the device searches
  * this table, so it agrees with the host's powf by construction.  NaN: the host conversion is undefined, the device writes 0. */
