@@ -3,13 +3,6 @@
 // Reference counterparts: render_state.hpp:97-197 (buffers), main.cpp:2244-2526 (the sequence of
 // launches on one in-order queue), execute_kernel main.cpp:139-205.  Everything is asynchronous on
 // the caller's stream; the only host->device traffic per frame is camera (48 B), cfg and features.
-// library default of gr_frame_options.rays_per_lane = 0 (see include/geodesic_hip.h)
-#ifndef GR_DEFAULT_TILE_HISTORY
-#define GR_DEFAULT_TILE_HISTORY 1
-#endif
-#ifndef GR_DEFAULT_RAYS_PER_LANE
-#define GR_DEFAULT_RAYS_PER_LANE 2   /* where the program has gr_trace_pair (capi.cpp: pair_kernel_applies) */
-#endif
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -21,6 +14,11 @@
 #include <mutex>
 
 #include "../../include/geodesic_hip_internal.h"
+#include "frame_plan.hpp"
+
+using frame_plan::origin_on_screen;
+using frame_plan::picture_motion;
+namespace switches = frame_plan::switches;
 
 extern "C" int gr_internal_fail(int code, const char* msg);   // capi.cpp
 
@@ -252,60 +250,22 @@ struct gr_geodesic_camera {
     float proper_time = 0;
 };
 
+// features and $cfg values as a frame or a snapshot gets them: the caller's, else the metric's defaults
+static int resolve_parameters(const gr_metric* m, const gr_features* features_in, const float* cfg_values, int num_cfg_values, gr_metric_info& info,
+                              gr_features& features, std::vector<float>& cfg) {
+    GR_CHECK(gr_metric_get_info(m, &info));
+    gr_features_default(&features);
+    if (features_in) features = *features_in;
+    else features.max_acceleration_change = info.max_acceleration_change;   // metric_manager.hpp:50
+    // dynamic_config: $cfg values in declaration order (metric_manager.hpp:60-66)
+    cfg.assign(info.num_dynamic_vars > 0 ? info.num_dynamic_vars : 1, 0.f);
+    for (int i = 0; i < info.num_dynamic_vars; i++)
+        cfg[i] = (cfg_values && i < num_cfg_values) ? cfg_values[i] : gr_metric_dynamic_var_default(m, i);
+    if ((int)cfg.size() > CFG_MAX) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "too many dynamic variables");
+    return GR_OK;
+}
+
 extern "C" {
-
-// Where a camera sees the coordinate origin, in pixels, as if space were flat (the inverse of the kernels' pixel_direction).  Between
-// two frames of a moving or turning camera the picture of whatever sits there - the hole, the bubble, the throat, which is where the
-// dear tiles are - moves by about as much as this point does; false if the origin is behind the camera or the camera sits on it.
-static bool origin_on_screen(const gr_camera& c, float fov_degrees, int width, int height, float out[2]) {   // = gr_camera_origin_on_screen
-    const double px = c.position[1], py = c.position[2], pz = c.position[3];
-    const double r = std::sqrt(px * px + py * py + pz * pz);
-    double qx = c.quat[0], qy = c.quat[1], qz = c.quat[2], qw = c.quat[3];
-    const double qn = std::sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
-    if (!(r > 1e-6) || !(qn > 1e-6)) return false;
-    qx = -qx / qn; qy = -qy / qn; qz = -qz / qn; qw /= qn;   // the inverse rotation: world -> camera
-    const double d[3] = {-px / r, -py / r, -pz / r};
-    const double t[3] = {2 * (qy * d[2] - qz * d[1]), 2 * (qz * d[0] - qx * d[2]), 2 * (qx * d[1] - qy * d[0])};
-    const double v[3] = {d[0] + qw * t[0] + (qy * t[2] - qz * t[1]), d[1] + qw * t[1] + (qz * t[0] - qx * t[2]),
-                         d[2] + qw * t[2] + (qx * t[1] - qy * t[0])};
-    if (!(v[2] > 0.05)) return false;
-    const double f_stop = (width / 2.0) / std::tan(fov_degrees / 360.0 * M_PI);
-    out[0] = (float)(width / 2.0 + f_stop * v[0] / v[2]);
-    out[1] = (float)(height / 2.0 + f_stop * v[1] / v[2]);
-    return std::isfinite(out[0]) && std::isfinite(out[1]);
-}
-
-// An upper estimate of how many pixels the picture moves between two cameras: the angle between the two orientations and the
-// parallax of the origin, at the focal length.  A history the picture has moved more than 48 px away from is not followed: a wrong
-// order is worse than none (a camera rolling 5 degrees a frame, 170 px at the edge: 4K Kerr 7.8 -> 13.4 ms, a = 0.9 27 -> 85 ms following
-// it blindly; up to 43 px - 0.08 units sideways or 1 degree of roll a frame - it measured a gain or nothing).
-// the two parts on their own: a turn of the camera moves the picture rigidly (the history's shift follows it), a step moves it by parallax
-static bool picture_motion_parts(const gr_camera& a, const gr_camera& b, float fov_degrees, int width, float& turn_px, float& parallax_px) {
-    double dot = 0, na = 0, nb = 0, dp = 0, r = 0;
-    for (int i = 0; i < 4; i++) { dot += (double)a.quat[i] * b.quat[i]; na += (double)a.quat[i] * a.quat[i]; nb += (double)b.quat[i] * b.quat[i]; }
-    for (int i = 1; i < 4; i++) { dp += ((double)a.position[i] - b.position[i]) * ((double)a.position[i] - b.position[i]); r += (double)b.position[i] * b.position[i]; }
-    turn_px = parallax_px = 1e9f;
-    if (!(na > 0) || !(nb > 0)) return false;
-    if (a.flip != b.flip || memcmp(a.basis_speed, b.basis_speed, sizeof(a.basis_speed)) != 0) return false;
-    const double c = std::min(1.0, std::fabs(dot) / std::sqrt(na * nb));
-    const double f_stop = (width / 2.0) / std::tan(fov_degrees / 360.0 * M_PI);
-    const double turn = 2 * std::acos(c) * f_stop, parallax = std::sqrt(dp) / std::max(std::sqrt(r), 1e-3) * f_stop;
-    if (!std::isfinite(turn) || !std::isfinite(parallax)) return false;
-    turn_px = (float)turn; parallax_px = (float)parallax;
-    return true;
-}
-
-static float picture_motion(const gr_camera& a, const gr_camera& b, float fov_degrees, int width) {
-    double dot = 0, na = 0, nb = 0, dp = 0, r = 0;
-    for (int i = 0; i < 4; i++) { dot += (double)a.quat[i] * b.quat[i]; na += (double)a.quat[i] * a.quat[i]; nb += (double)b.quat[i] * b.quat[i]; }
-    for (int i = 1; i < 4; i++) { dp += ((double)a.position[i] - b.position[i]) * ((double)a.position[i] - b.position[i]); r += (double)b.position[i] * b.position[i]; }
-    if (!(na > 0) || !(nb > 0)) return 1e9f;
-    const double c = std::min(1.0, std::fabs(dot) / std::sqrt(na * nb));
-    const double f_stop = (width / 2.0) / std::tan(fov_degrees / 360.0 * M_PI);
-    const double motion = (2 * std::acos(c) + std::sqrt(dp) / std::max(std::sqrt(r), 1e-3)) * f_stop;
-    if (a.flip != b.flip || memcmp(a.basis_speed, b.basis_speed, sizeof(a.basis_speed)) != 0) return 1e9f;
-    return std::isfinite(motion) ? (float)motion : 1e9f;
-}
 
 int gr_render_state_tile_history(gr_render_state* s, unsigned long long* frames_recorded, unsigned long long* frames_followed, int last_shift[2]) {
     if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
@@ -802,15 +762,9 @@ int gr_geodesic_camera_snapshot(gr_geodesic_camera* g, gr_program* p, const gr_m
     hipStream_t stream = (hipStream_t)stream_v;
     HIP_CHECK(hipSetDevice(g->device));
     gr_metric_info info;
-    GR_CHECK(gr_metric_get_info(m, &info));
     gr_features features;
-    gr_features_default(&features);
-    if (features_in) features = *features_in;
-    else features.max_acceleration_change = info.max_acceleration_change;
-    std::vector<float> cfg(info.num_dynamic_vars > 0 ? info.num_dynamic_vars : 1, 0.f);
-    for (int i = 0; i < info.num_dynamic_vars; i++)
-        cfg[i] = (cfg_values && i < num_cfg_values) ? cfg_values[i] : gr_metric_dynamic_var_default(m, i);
-    if ((int)cfg.size() > CFG_MAX) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "too many dynamic variables");
+    std::vector<float> cfg;
+    GR_CHECK(resolve_parameters(m, features_in, cfg_values, num_cfg_values, info, features, cfg));
     float speed4[4] = {geodesic_basis_speed[0], geodesic_basis_speed[1], geodesic_basis_speed[2], 0.f};
     if (speed4[0] * speed4[0] + speed4[1] * speed4[1] + speed4[2] * speed4[2] >= 1.f)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "geodesic basis speed must be below c");
@@ -879,9 +833,7 @@ void* gr_geodesic_camera_buffer(gr_geodesic_camera* g, int which) {
     return nullptr;
 }
 
-// one frame at the state's traced size: out is float4[s->width * s->height] (gr_render_frame below for a state of factor 1, and what a
-// supersampled state shades into its own traced frame)
-// What a frame refuses before any HIP call (render_traced_frame, and gr_render_frame_rgba8 before it allocates for a factor-1 state).
+// What a frame refuses before any HIP call (render_traced_frame, and deliver_frame before it allocates for a factor-1 state).
 static int check_frame_arguments(const gr_render_state* s, const gr_program* p, const gr_metric* m, const gr_camera* camera, const float* cfg_values,
                                  int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height, int bg_levels, const void* out) {
     if (!s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
@@ -893,113 +845,39 @@ static int check_frame_arguments(const gr_render_state* s, const gr_program* p, 
     return GR_OK;
 }
 
-static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream_v, const gr_camera* camera,
-                               const gr_features* features_in, const float* cfg_values, int num_cfg_values, const void* bg1,
-                               const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* opt_in) {
-    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out));
-    hipStream_t stream = (hipStream_t)stream_v;
-    HIP_CHECK(hipSetDevice(s->device));
+// ---- one frame at the state's traced size: render_traced_frame, a sequence of the stages below ---------------------------------
+// What the stages share.  Decisions that need no device live in frame_plan.cpp (the fused path's: frame_plan::plan_fused); the stages
+// gather their inputs, carry them out, and keep the order of the HIP calls on every stream.
+struct frame_context {
+    gr_render_state* s; gr_program* p; hipStream_t stream; const gr_camera* camera;
+    const void *bg1, *bg2; int bg_width, bg_height, bg_levels;
+    void* out;   // float4[s->width * s->height], or NULL: stop after the render-data
     gr_frame_options opt;
-    gr_frame_options_default(&opt);
-    if (opt_in) opt = *opt_in;
     gr_frame_tuning tune;   // which fused kernel, schedule and launch size (geodesic_hip_internal.h; NULL = the defaults)
-    gr_frame_tuning_default(&tune);
-    if (opt.tuning) tune = *opt.tuning;
-    gr_metric_info info;
-    GR_CHECK(gr_metric_get_info(m, &info));
-
     gr_features features;
-    gr_features_default(&features);
-    if (features_in) features = *features_in;
-    else features.max_acceleration_change = info.max_acceleration_change;   // metric_manager.hpp:50
+    std::vector<float> cfg;
+    int width, height, prepass_width, prepass_height;
+    bool use_prepass, adaptive, cfg_changed, cfg_jumped, features_changed, prepass_by_policy;
+    bool prefetched = false, repeats_previous_frame = false, reuse_on = false, one_launch_setup = false, log_trace = false;
+    const gr_geodesic_camera* gc = nullptr;
+    void* attempts = nullptr;
+    // fused mode
+    frame_plan::fused_plan plan;
+    struct request { const gr_camera* camera; float time; int strip_rank; };   // strip_rank < 0: this frame's
+    std::vector<request> todo;   // look-ahead requests that are not already sitting in a slot
+    bool claimed[gr_render_state::LOOKAHEAD] = {};   // a slot serves one request (two frames may share one camera)
 
-    const int width = s->width, height = s->height;
-    // The defaults of gr_features (adaptive_sampling on, as the reference's GUI) and of gr_frame_options (fused mode) work
-    // together: a frame is sampled adaptively on the fused path (half-resolution lattice, gr_adaptive_refine, second fused
-    // launch over the marked pixels; cl.cl:3234-3250, 5223-5345) - a device's share of a split frame too: it traces the lattice
-    // rows its blocks' decisions read (two rows of halo either side) and its rows come out as those of the whole frame.
-    bool use_prepass = opt.use_prepass < 0 ? info.use_prepass != 0 : opt.use_prepass != 0;
-    bool adaptive = features.adaptive_sampling != 0 && !features.use_triangle_rendering;
-    // The 2x2 blocks of handle_adaptive_sampling cover 2 (W/2) x 2 (H/2) pixels (cl.cl:5228-5236): with an odd width or height the
-    // last column or row belongs to no block and would keep whatever its record held.  The fused path then traces every pixel.
-    if (opt.mode == GR_MODE_FUSED && ((width | height) & 1)) adaptive = false;
-
-    // dynamic_config: $cfg values in declaration order (metric_manager.hpp:60-66)
-    std::vector<float> cfg(info.num_dynamic_vars > 0 ? info.num_dynamic_vars : 1, 0.f);
-    for (int i = 0; i < info.num_dynamic_vars; i++)
-        cfg[i] = (cfg_values && i < num_cfg_values) ? cfg_values[i] : gr_metric_dynamic_var_default(m, i);
-    if ((int)cfg.size() > CFG_MAX) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "too many dynamic variables");
-    const bool cfg_changed = cfg != s->host_cfg;
-    // ... by a step of a slider (every parameter within a tenth of itself): the picture is nearly the one before, and what its tiles cost is
-    // still the best estimate there is of what they cost now - orders are only orders, a wrong one costs time, never a record.  A frame of a
-    // slider being dragged (the dynamic program, new parameters every frame: metric_manager.hpp:60-66) would otherwise start from image
-    // order every time (4K Kerr: 6.0 ms against 5.1).
-    const bool cfg_jumped = cfg_changed && [&] {
-        if (cfg.size() != s->host_cfg.size()) return true;
-        for (size_t i = 0; i < cfg.size(); i++) {
-            const float a = cfg[i], b = s->host_cfg[i];
-            if (!(std::fabs(a - b) <= 0.1f * std::max(std::max(std::fabs(a), std::fabs(b)), 0.05f))) return true;
-        }
-        return false;
-    }();
-    const bool features_changed = !s->features_valid || memcmp(&features, &s->host_features, sizeof(features)) != 0;
-    // another metric, parameter set or field of view: what the last frame's tiles cost says nothing about this one's (tile_history)
-    if (cfg_jumped || features_changed || gr_program_serial(p) != s->tile_cost_program) {
-        s->tile_cost_valid = false;
-        s->tile_cost_program = gr_program_serial(p);
+    int begin(int st) {
+        if (log_trace) { if (st == GR_STAGE_TRACE) HIP_CHECK(hipEventRecord(s->trace_log[s->trace_log_used].first, stream)); }
+        else if (opt.time_kernels) { HIP_CHECK(hipEventRecord(s->ev_start[st], stream)); }
+        return GR_OK;
     }
-    const bool prepass_by_policy = opt.use_prepass == -2 && use_prepass && opt.mode == GR_MODE_FUSED && opt.strip_count <= 1;
-    if (prepass_by_policy) {
-        auto& pol = s->policy;
-        const unsigned long long serial = gr_program_serial(p);
-        if (cfg_changed || features_changed || serial != s->policy_program) {   // another metric or parameter set: start over
-            pol.holiday = 0;
-            pol.last_fraction = -1.f;
-            if (pol.in_flight) { HIP_CHECK(hipEventSynchronize(pol.copied)); pol.in_flight = false; }
-            s->policy_program = serial;
-        }
-        if (pol.in_flight && hipEventQuery(pol.copied) == hipSuccess) {
-            // the share of the grid whose 5-point stencil is marked throughout: what init_rays_generic's test lets the trace skip
-            // (a pixel is skipped when the cell it rounds to and that cell's four neighbours are all marked, cl.cl:3213-3232)
-            size_t skippable = 0;
-            const int pw = pol.grid_width, ph = pol.cells && pw ? (int)(pol.cells / pw) : 0;
-            for (int y = 1; y + 1 < ph; y++)
-                for (int x = 1; x + 1 < pw; x++) {
-                    const int* c = pol.host_flags + (size_t)y * pw + x;
-                    skippable += c[0] == 1 && c[-1] == 1 && c[1] == 1 && c[-pw] == 1 && c[pw] == 1;
-                }
-            pol.last_fraction = pol.cells ? (float)skippable / (float)pol.cells : 0.f;
-            pol.in_flight = false;
-            if (pol.last_fraction < gr_render_state::PREPASS_MIN_SKIP) pol.holiday = gr_render_state::PREPASS_HOLIDAY;
-        } else if (pol.in_flight) {
-            (void)hipGetLastError();   // hipErrorNotReady is not an error
-        }
-        if (pol.holiday > 0) { pol.holiday--; pol.without_prepass++; use_prepass = false; }
-        else pol.with_prepass++;
+    int end(int st) {
+        if (log_trace) { if (st == GR_STAGE_TRACE) { HIP_CHECK(hipEventRecord(s->trace_log[s->trace_log_used].second, stream)); s->trace_log_used++; } }
+        else if (opt.time_kernels) { HIP_CHECK(hipEventRecord(s->ev_stop[st], stream)); s->stage_timed[st] = true; }
+        return GR_OK;
     }
-    if (cfg_changed || features_changed) {
-        // Look-ahead prepasses read s->cfg / s->dfg on their side streams: the upload below must not overtake one that is still
-        // running (it would read a mix of old and new parameters), and what the slots hold was computed for the old parameters.
-        for (auto& slot : s->pre) {
-            if (!slot.valid) continue;
-            HIP_CHECK(hipStreamWaitEvent(stream, slot.ready, 0));
-            slot.valid = false;
-        }
-    }
-    if (cfg_changed) {
-        GR_CHECK(s->uploads.copy(s->cfg, cfg.data(), cfg.size() * sizeof(float), stream));
-        s->host_cfg = cfg;
-    }
-    if (features_changed) {
-        GR_CHECK(s->uploads.copy(s->dfg, &features, sizeof(features), stream));
-        s->host_features = features;
-        s->features_valid = true;
-    }
-    int prepass_width = width / 16, prepass_height = height / 16;   // main.cpp:2380-2381
-    if (prepass_width < 1 || prepass_height < 1) use_prepass = false;
-
-    // was this frame's camera set-up + prepass already done on a side stream during an earlier frame?
-    auto make_key = [&](const gr_camera* c, float time, int frame_strip_rank) {
+    gr_render_state::prefetch_key make_key(const gr_camera* c, float time, int frame_strip_rank) const {
         gr_render_state::prefetch_key k;
         k.camera = *c;
         k.cfg = cfg;
@@ -1012,70 +890,11 @@ static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metri
         k.strip[1] = k.strip[2] > 1 ? frame_strip_rank : 0;
         k.strip[0] = k.strip[2] > 1 ? opt.block_rows : 0;
         return k;
-    };
-    s->frame_counter++;
-    bool prefetched = false;
-    if (opt.mode == GR_MODE_FUSED && use_prepass) {
-        const auto want = make_key(camera, opt.geodesic_time, opt.strip_rank);
-        gr_render_state::prefetch_slot* hit = nullptr;   // the oldest matching prefetch: it has had the most time to finish
-        for (auto& slot : s->pre)
-            if (slot.valid && slot.key == want && (!hit || slot.age < hit->age)) hit = &slot;
-        if (hit) {
-            s->swap_in(hit->set);
-            HIP_CHECK(hipStreamWaitEvent(stream, hit->ready, 0));
-            hit->valid = false;
-            prefetched = true;
-        }
     }
-    // ... or is it the previous frame of this state over again - camera, parameters, features, program, bit for bit, on the same stream
-    // (gr_frame_tuning.reuse_still_camera)?  Camera position, tetrad and the prepass verdicts are functions of exactly those, and they are
-    // where that frame left them: a viewer whose user has stopped moving pays neither again (the reference does, every frame:
-    // main.cpp:2311-2437).  Whole frames with a Cartesian camera whose tiles are not ordered by the prepass rays' costs.
-    static const int tile_order_mode = [] { const char* e = getenv("GR_TILE_ORDER"); return !e ? -1 : e[0] == '0' ? 0 : 1; }();
-    static const int reuse_default = [] { const char* e = getenv("GR_REUSE_STILL_CAMERA"); return !e ? 1 : e[0] != '0'; }();
-    const bool repeats_previous_frame = opt.mode == GR_MODE_FUSED && use_prepass && !opt.geodesic && opt.strip_count <= 1 && s->previous_key_valid &&
-                                        s->previous_key == make_key(camera, opt.geodesic_time, opt.strip_rank);
-    const bool reuse_on = (tune.reuse_still_camera < 0 ? reuse_default : tune.reuse_still_camera) != 0 && tile_order_mode != 1;
-    if (!prefetched && repeats_previous_frame && reuse_on && s->previous_stream == stream) {
-        prefetched = true;
-        s->prepass_reused++;
-    }
-    s->previous_key_valid = false;   // until this frame has left its own set-up and prepass behind
-    if (!prefetched) {
-        GR_CHECK(s->uploads.copy(s->camera_pos_cart, camera->position, 16, stream));
-        GR_CHECK(s->uploads.copy(s->camera_quat, camera->quat, 16, stream));
-    }
-
-    for (int i = 0; i < GR_STAGE_COUNT; i++) s->stage_timed[i] = false;
-    const bool log_trace = opt.time_kernels == 2;
-    if (log_trace && s->trace_log_used == s->trace_log.size()) {
-        hipEvent_t a = nullptr, b = nullptr;
-        HIP_CHECK(hipEventCreate(&a));
-        HIP_CHECK(hipEventCreate(&b));
-        s->trace_log.emplace_back(a, b);
-    }
-    auto begin = [&](int st) -> int {
-        if (log_trace) { if (st == GR_STAGE_TRACE) HIP_CHECK(hipEventRecord(s->trace_log[s->trace_log_used].first, stream)); }
-        else if (opt.time_kernels) { HIP_CHECK(hipEventRecord(s->ev_start[st], stream)); }
-        return GR_OK;
-    };
-    auto end = [&](int st) -> int {
-        if (log_trace) { if (st == GR_STAGE_TRACE) { HIP_CHECK(hipEventRecord(s->trace_log[s->trace_log_used].second, stream)); s->trace_log_used++; } }
-        else if (opt.time_kernels) { HIP_CHECK(hipEventRecord(s->ev_stop[st], stream)); s->stage_timed[st] = true; }
-        return GR_OK;
-    };
-    void* attempts = nullptr;
-    if (tune.count_attempts) {
-        HIP_CHECK(hipMemsetAsync(s->attempts, 0, GR_COUNTER_WORDS * 8, stream));
-        attempts = s->attempts;
-    }
-
+    gr_render_state::prefetch_key own_key() const { return make_key(camera, opt.geodesic_time, opt.strip_rank); }
     // camera position and tetrad: from the cartesian camera (main.cpp:2311, 2329), or - camera on a geodesic - interpolated
     // from the snapshot at the requested proper time (main.cpp:2264-2293)
-    const gr_geodesic_camera* gc = opt.geodesic;
-    if (gc && gc->device != s->device) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "geodesic camera lives on another device");
-    auto camera_setup = [&](hipStream_t st, void* cart, void* generic, void* const* tetrad, const gr_camera* cam, float time,
-                            void* velocity_out) -> int {
+    int camera_setup(hipStream_t st, void* cart, void* generic, void* const* tetrad, const gr_camera* cam, float time, void* velocity_out) const {
         if (gc)
             return gr_handle_interpolating_geodesic(p, st, gc->path, gc->velocity, gc->ds, generic, gc->transported[0], gc->transported[1],
                                                     gc->transported[2], gc->transported[3], tetrad[0], tetrad[1], tetrad[2], tetrad[3],
@@ -1083,405 +902,577 @@ static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metri
                                                     s->cfg);
         GR_CHECK(gr_cart_to_generic(p, st, cart, generic, 1, cam->flip, s->cfg));
         return gr_init_basis_vectors(p, st, generic, 1, cam->basis_speed, tetrad[0], tetrad[1], tetrad[2], tetrad[3], s->cfg);
-    };
-    // fused mode with a Cartesian camera: camera set-up and prepass are one call (gr_camera_prepass), issued below
-    const bool one_launch_setup = opt.mode == GR_MODE_FUSED && !gc;
-    if (!prefetched && !one_launch_setup) {
-        GR_CHECK(begin(GR_STAGE_CAMERA));
-        GR_CHECK(camera_setup(stream, s->camera_pos_cart, s->camera_pos_generic, s->tetrad, camera, opt.geodesic_time,
-                              gc ? gc->interpolated_velocity : nullptr));
-        GR_CHECK(end(GR_STAGE_CAMERA));
     }
-
-    if (opt.mode == GR_MODE_FUSED) {
-        int strip_count = opt.strip_count > 1 ? opt.strip_count : 1;
-        int strip_rank = strip_count > 1 ? opt.strip_rank : 0;
-        int block_rows = strip_count > 1 ? opt.block_rows : ((height + 7) / 8) * 8;
-        // The prepass rays' costs (kept behind the prepass flags in the termination buffer, which is allocated per pixel) order the
-        // tiles of the trace, longest first (gr_order_tiles).
-        // Default: on a device's share of a split frame (+8 % with three frames in flight, +35 % one frame at a time, one of 8
-        // devices), not on a whole frame (there image order measured 2 % faster); GR_TILE_ORDER=0 never, =1 always.
-        // The other source of an order: what the tiles of this state's previous frame cost (gr_order_tiles_by_history).
-        static const int history_default = [] { const char* e = getenv("GR_TILE_HISTORY"); return !e ? GR_DEFAULT_TILE_HISTORY : e[0] != '0'; }();
-        // Default: whole frames that find the device idle when they are submitted (they record their costs, and follow those of
-        // the frame before if that one did too).
-        // Not frames of more than 32 tiles per wave slot (8K Alcubierre: 72 short tiles of much the same cost; recording and sorting
-        // them measured +3 % on the frame, with nothing to gain).
-        // An adaptively sampled whole frame: the same for its lattice launch - the tiles of the half-resolution grid, their costs left by the
-        // lattice launch of the frame before (GR_LATTICE_HISTORY=0: image order as before round 6's fifth session).  Only for the metrics with a
-        // prepass - the ones with a shadow and long rays along its edge: there the launch gains by its speculative tiles when it traces
-        // its own cells, and by the order alone where it is long (4K Kerr a = 0.9, prepass reused: 12.2 -> 9.1 ms); recording + sorting cost
-        // the 0.4 ms frames of the metrics without a prepass 5-10 %.
-        static const bool lattice_history = [] { const char* e = getenv("GR_LATTICE_HISTORY"); return !(e && e[0] == '0'); }();
-        const int hist_width = adaptive ? width / 2 : width, hist_height = adaptive ? height / 2 : height;
-        const int hist_block_rows = adaptive ? ((hist_height + 7) / 8) * 8 : block_rows;
-        const long long tile_words = gr_tile_order_bytes(hist_width, hist_height, hist_block_rows, strip_rank, strip_count) / 8;
-        const bool history_wanted = (tune.tile_history < 0 ? history_default != 0 && strip_count == 1 && tile_words <= 32 * gr_trace_fused_wave_slots(p)
-                                                          : tune.tile_history != 0) && (!adaptive || (lattice_history && strip_count == 1 && use_prepass)) &&
-                                    (size_t)gr_tile_order_bytes(hist_width, hist_height, hist_block_rows, strip_rank, strip_count) <= s->tile_order_bytes;
-        // (the pixels traced ahead for the second launch of adaptive sampling - below - are for such lone frames too, prepass or not)
-        static const bool guess_default = [] { const char* e = getenv("GR_ADAPTIVE_GUESS"); return !(e && e[0] == '0'); }();
-        const bool guesses_wanted = guess_default && adaptive && strip_count == 1 && !opt.geodesic && tune.tile_history != 0 && history_default != 0;
-        const bool device_busy = (history_wanted || guesses_wanted) && tune.tile_history < 0 && earlier_frame_still_running(s->device, stream);
-        const bool tile_order_enabled = !history_wanted && (tile_order_mode == 1 || (tile_order_mode == -1 && strip_count > 1));
-        const size_t cells = use_prepass ? (size_t)prepass_width * prepass_height : 0;
-        // (a frame whose prepass rides in its trace launch - below - has no costs to order by; the frames it announces still do)
-        const bool order_capable = tile_order_enabled && use_prepass && !adaptive && 2 * cells <= (size_t)width * height &&
-                                   (size_t)gr_tile_order_bytes(width, height, block_rows, strip_rank, strip_count) <= s->tile_order_bytes;
-        const int prepass_margin = adaptive ? 2 : 0;   // the lattice rows beyond a block that its 2x2 decisions read
-        auto cost_plane = [&](void* termination_buffer) -> void* { return order_capable ? (void*)((unsigned int*)termination_buffer + cells) : nullptr; };
-        // which trace kernel this frame takes (needed here already: the prepass may ride in the trace launch)
-        // library default: no compaction (the benchmark workloads keep > 95 % of their lanes busy without it); experiments can
-        // switch it on for every frame with GR_TRACE_COMPACT=<keep_lanes>
-        static const int default_compaction = [] { const char* e = getenv("GR_TRACE_COMPACT"); int v = e ? atoi(e) : 0; return (v >= 1 && v <= 64) ? v : 0; }();
-        int keep_lanes = tune.ray_compaction < 0 ? default_compaction : tune.ray_compaction;
-        // What does not combine is refused, not silently dropped: ray compaction and the two-rays-per-lane kernel trace every
-        // pixel (no lattice / pending-only form), in-tile shading needs every pixel's record in its own tile's wave.
-        if (adaptive && tune.ray_compaction > 0)
-            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "ray_compaction > 0 with adaptive sampling: gr_trace_compact traces every pixel (switch one of them off)");
-        if (adaptive && tune.rays_per_lane == 2)
-            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "rays_per_lane = 2 with adaptive sampling: gr_trace_pair traces every pixel (switch one of them off)");
-        if (tune.fused_shading == 1 && (adaptive || keep_lanes > 0 || tune.rays_per_lane == 2))
-            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "fused_shading = 1 needs one ray per lane, no compaction and no adaptive sampling");
-        if (adaptive) keep_lanes = 0;   // GR_TRACE_COMPACT (an experiment switch for every frame) does not apply to adaptive frames
-        // two rays per lane (gr_trace_pair) where the program has that kernel, unless told otherwise
-        static const int default_rays_per_lane = [] { const char* e = getenv("GR_TRACE_RAYS_PER_LANE"); int v = e ? atoi(e) : 0; return (v == 1 || v == 2) ? v : GR_DEFAULT_RAYS_PER_LANE; }();
-        int rays_per_lane = tune.rays_per_lane == 1 || tune.rays_per_lane == 2 ? tune.rays_per_lane : default_rays_per_lane;
-        if (rays_per_lane == 2 && !gr_program_has_trace_pair(p)) {
-            if (tune.rays_per_lane == 2) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "rays_per_lane = 2: this program has no gr_trace_pair kernel");
-            rays_per_lane = 1;
-        }
-        // The prepass inside the trace launch (gr_trace_fused_args.inline_prepass): for a frame whose prepass was not computed
-        // ahead of time - an interactive caller does not know the next camera - the prepass's single-ray latency (1.1 ms at 4K
-        // Kerr, 8 ms with a = 0.9) then runs alongside the first tiles instead of in front of the whole trace.
-        static const int inline_default = [] { const char* e = getenv("GR_INLINE_PREPASS"); return !e ? 1 : e[0] != '0'; }();
-        // By default on whole frames that do not order their tiles (the order needs the prepass rays' costs first).  A device's share
-        // of a split frame can do it too (inline_prepass = 1: it traces the cells its rows look at), but does not by default, on
-        // measurement - one rank of 8 / of 4, one frame at a time, 2 wave slots per SIMD: 2.41 / 3.42 ms against 2.20 / 2.80 with the
-        // prepass in front and the tiles ordered by its costs (tools/strip_probe.py, STRIP_PROBE_DEPTH=0): a share is few tiles, and
-        // which of them start first matters more than the prepass's latency.
-        const bool inline_wanted = tune.inline_prepass < 0 ? (inline_default != 0 && strip_count == 1 && !order_capable) : tune.inline_prepass != 0;
-        // (an adaptively sampled whole frame: the cells ride in front of the lattice launch's tiles)
-        const bool inline_prepass = inline_wanted && !prefetched && one_launch_setup && use_prepass && (!adaptive || strip_count == 1) && keep_lanes == 0 &&
-                                    rays_per_lane == 1 && prepass_width != width && prepass_height != height;
-        const bool order_tiles = order_capable && !inline_prepass;
-        // (the kernels that record and follow the history are gr_trace_fused's: one ray per lane, no compaction)
-        const bool record_history = history_wanted && !device_busy && keep_lanes == 0 && rays_per_lane == 1;
-        if (history_wanted && !record_history) s->tile_cost_valid = false;   // (what is there would be older than the last frame)
-        const int shape[3] = {adaptive ? -hist_block_rows : block_rows, strip_rank, strip_count};   // (negative: the tiles of a lattice launch)
-        static const float history_max_motion = [] { const char* e = getenv("GR_TILE_HISTORY_MAX_MOTION"); return e ? (float)atof(e) : 48.f; }();
-        // ... or, when the camera mostly TURNED (mouse look: the picture shifts rigidly and the order shifts with it - follow_and_record_history -
-        // as long as both frames see the coordinate origin), up to GR_TILE_HISTORY_MAX_TURN px of turn with at most the 48 px of parallax:
-        // 1.5 degrees a frame at 4K (50 px) rendered in 6.23 ms with the history dropped and in 5.24 with it (a = 0.9: 24.0 and 21.9), 2.2 degrees
-        // (73 px) in 6.36 and 5.50 (24.4 and 23.3); at 3 degrees (100 px) the a = 0.9 frame loses badly (23.9 -> 33.8 ms: the shift is the
-        // picture centre's, a perspective picture moves by 1 / cos^2 more towards its edges, and beyond the guard ring of 48 px tiles
-        // guessed empty are dear): 64 px.
-        static const float history_max_turn = [] { const char* e = getenv("GR_TILE_HISTORY_MAX_TURN"); return e ? (float)atof(e) : 64.f; }();
-        const bool history_order = record_history && s->tile_cost_valid && memcmp(shape, s->tile_cost_shape, sizeof(shape)) == 0 && !gc && [&] {
-            if (picture_motion(s->tile_cost_camera, *camera, features.field_of_view, width) <= history_max_motion) return true;
-            float turn = 0, parallax = 0, anchor[2];
-            return picture_motion_parts(s->tile_cost_camera, *camera, features.field_of_view, width, turn, parallax) && parallax <= history_max_motion &&
-                   turn <= history_max_turn && s->tile_cost_anchored && origin_on_screen(*camera, features.field_of_view, width, height, anchor);
-        }();
-        if (!prefetched && one_launch_setup) {
-            GR_CHECK(begin(GR_STAGE_PREPASS));
-            GR_CHECK(gr_camera_prepass(p, stream, s->camera_pos_cart, camera->flip, camera->basis_speed, s->camera_pos_generic, s->tetrad[0],
-                                       s->tetrad[1], s->tetrad[2], s->tetrad[3], s->camera_quat, s->termination_buffer,
-                                       use_prepass && !inline_prepass ? prepass_width : 0, use_prepass && !inline_prepass ? prepass_height : 0, s->cfg,
-                                       s->dfg, height, block_rows, strip_rank, strip_count, cost_plane(s->termination_buffer), prepass_margin));
-            if (order_tiles)
-                GR_CHECK(gr_order_tiles(p, stream, s->termination_buffer, cost_plane(s->termination_buffer), prepass_width, prepass_height,
-                                        width, height, block_rows, strip_rank, strip_count, s->tile_order));
-            GR_CHECK(end(GR_STAGE_PREPASS));
-        } else if (use_prepass && !prefetched) {
-            GR_CHECK(begin(GR_STAGE_PREPASS));
-            GR_CHECK(gr_prepass_fused_strips(p, stream, s->camera_pos_generic, s->camera_quat, s->termination_buffer, prepass_width,
-                                             prepass_height, s->tetrad[0], s->tetrad[1], s->tetrad[2], s->tetrad[3], s->cfg, s->dfg,
-                                             height, block_rows, strip_rank, strip_count, cost_plane(s->termination_buffer), prepass_margin));
-            if (order_tiles)
-                GR_CHECK(gr_order_tiles(p, stream, s->termination_buffer, cost_plane(s->termination_buffer), prepass_width, prepass_height,
-                                        width, height, block_rows, strip_rank, strip_count, s->tile_order));
-            GR_CHECK(end(GR_STAGE_PREPASS));
-        }
-        // look-ahead requests that are not already sitting in a slot
-        struct request { const gr_camera* camera; float time; int strip_rank; };   // strip_rank < 0: this frame's
-        std::vector<request> todo;
-        bool claimed[gr_render_state::LOOKAHEAD] = {};   // a slot serves one request (two frames may share one camera)
-        if (use_prepass) {
-            request asked[2] = {{opt.next_camera, tune.next_geodesic_time, tune.next_strip_rank},
-                                {opt.next_camera2, tune.next_geodesic_time2, tune.next_strip_rank2}};
-            // nobody announced the next camera, and this frame is the previous one over again: the guess "the same once more"
-            // (gr_frame_tuning.guess_still_camera, off by default since reuse_still_camera does without the prepass altogether) - used
-            // by the next frame only if its key matches bit for bit
-            static const int guess_default = [] { const char* e = getenv("GR_GUESS_STILL_CAMERA"); return !e ? 0 : e[0] != '0'; }();
-            if (!opt.next_camera && !opt.next_camera2 && !gc && strip_count == 1 && (tune.guess_still_camera < 0 ? guess_default : tune.guess_still_camera) != 0 &&
-                repeats_previous_frame && !reuse_on)
-                asked[0] = {camera, opt.geodesic_time, -1};
-            for (auto& r : asked) {
-                if (!r.camera) continue;
-                if (r.strip_rank < 0 || r.strip_rank >= strip_count) r.strip_rank = strip_rank;
-                const auto k = make_key(r.camera, r.time, r.strip_rank);
-                bool have = false;
-                for (int i = 0; i < gr_render_state::LOOKAHEAD && !have; i++)
-                    if (!claimed[i] && s->pre[i].valid && s->pre[i].key == k) claimed[i] = have = true;
-                if (!have) todo.push_back(r);
-            }
-        }
-        if (!todo.empty()) HIP_CHECK(hipEventRecord(s->main_mark, stream));   // everything up to here is older than the prefetches
-        auto inspect_prepass = [&]() -> int {
-            if (!(prepass_by_policy && use_prepass && !s->policy.in_flight)) return GR_OK;
-            // this frame's prepass flags -> host, behind the prepass on the frame's stream; read when a later frame finds them there
-            auto& pol = s->policy;
-            if (pol.capacity < cells) {
-                if (pol.host_flags) (void)hipHostFree(pol.host_flags);
-                pol.host_flags = nullptr;
-                HIP_CHECK(hipHostMalloc((void**)&pol.host_flags, cells * sizeof(int), hipHostMallocDefault));
-                pol.capacity = cells;
-            }
-            if (!pol.copied) HIP_CHECK(hipEventCreateWithFlags(&pol.copied, hipEventDisableTiming));
-            HIP_CHECK(hipMemcpyAsync(pol.host_flags, s->termination_buffer, cells * sizeof(int), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipEventRecord(pol.copied, stream));
-            pol.cells = cells;
-            pol.grid_width = prepass_width;
-            pol.in_flight = true;
-            return GR_OK;
-        };
-        if (!inline_prepass) GR_CHECK(inspect_prepass());   // (with the prepass inside the trace launch: after it)
-        // every device runs the (tiny) prepass itself; its own row blocks (+ one halo row each) are traced here
-        bool shade_in_trace = false;
-        GR_CHECK(begin(GR_STAGE_TRACE));
-        // the order of the frame before's costs and the record of this frame's, for the launch that traces the frame's tiles
-        // (gr_trace_fused on every pixel, or the lattice launch of adaptive sampling: tiles of 8 x 8 lattice pixels = 16 x 16 pixels)
-        auto follow_and_record_history = [&](gr_trace_fused_args& a) -> int {
-            float anchor[2] = {0, 0};
-            const bool anchored = record_history && !gc && origin_on_screen(*camera, features.field_of_view, width, height, anchor);
-            if (history_order) {
-                // how far the picture has moved since the costs were recorded, in tiles
-                int shift[2] = {0, 0};
-                static const bool follow_camera = [] { const char* e = getenv("GR_TILE_HISTORY_FOLLOW"); return !(e && e[0] == '0'); }();
-                if (follow_camera && anchored && s->tile_cost_anchored)
-                    for (int i = 0; i < 2; i++)
-                        shift[i] = (int)std::lround(std::max(-4096.f, std::min(4096.f, (anchor[i] - s->tile_cost_anchor[i]) / (adaptive ? 16.f : 8.f))));
-                GR_CHECK(gr_order_tiles_by_history(p, stream, s->tile_cost, hist_width, hist_height, hist_block_rows, strip_rank, strip_count, s->tile_order,
-                                                   shift[0], shift[1]));
-                s->history_followed++;
-                s->history_last_shift[0] = shift[0]; s->history_last_shift[1] = shift[1];
-                a.tile_order = s->tile_order;
-                a.tile_order_by_history = 1;
-                a.speculative_classes = tune.speculative_classes < 0 ? 0 : tune.speculative_classes == 0 ? -1 : tune.speculative_classes;
-            }
-            if (record_history) {
-                a.tile_cost = s->tile_cost;
-                s->history_recorded++;
-                memcpy(s->tile_cost_shape, shape, sizeof(shape));
-                s->tile_cost_valid = true;
-                s->tile_cost_anchored = anchored;
-                s->tile_cost_anchor[0] = anchor[0]; s->tile_cost_anchor[1] = anchor[1];
-                s->tile_cost_camera = *camera;
-            }
-            return GR_OK;
-        };
-        if (keep_lanes > 0)
-            GR_CHECK(gr_trace_compact(p, stream, s->camera_pos_generic, s->camera_quat, s->render_data, width, height, block_rows,
-                                      strip_rank, strip_count, use_prepass ? s->termination_buffer : nullptr,
-                                      use_prepass ? prepass_width : width, use_prepass ? prepass_height : height, s->tetrad[0],
-                                      s->tetrad[1], s->tetrad[2], s->tetrad[3], s->cfg, s->dfg, attempts, keep_lanes));
-        else {
-            if (adaptive) {
-                // quarter of the primary rays (the pixels (2x, 2y)), then the blocks that need it refined by a second launch
-                const void* term = use_prepass ? s->termination_buffer : nullptr;
-                const int pw = use_prepass ? prepass_width : width, ph = use_prepass ? prepass_height : height;
-                gr_trace_fused_args a{};
-                a.camera_generic = s->camera_pos_generic; a.camera_quat = s->camera_quat; a.render_data = s->render_data;
-                a.width = width; a.height = height; a.block_rows = block_rows; a.strip_rank = strip_rank; a.strip_count = strip_count;
-                a.termination_buffer = term; a.prepass_width = pw; a.prepass_height = ph;
-                a.e0 = s->tetrad[0]; a.e1 = s->tetrad[1]; a.e2 = s->tetrad[2]; a.e3 = s->tetrad[3]; a.cfg = s->cfg; a.dfg = s->dfg;
-                a.attempt_counter = attempts;
-                a.waves_per_simd = tune.trace_waves_per_simd;
-                a.lattice = 2;
-                a.inline_prepass = inline_prepass ? 1 : 0;
-                if (!s->lattice_rays) HIP_CHECK(hipMalloc(&s->lattice_rays, gr_lattice_rays_bytes(width, height)));
-                if (!s->pending_list) HIP_CHECK(hipMalloc(&s->pending_list, gr_pending_list_bytes(width, height)));
-                a.lattice_rays = s->lattice_rays;
-                GR_CHECK(follow_and_record_history(a));
-                // Tracing ahead what the second launch will ask for (gr_apply_guessed): where the frame before's second launch found pixels of
-                // 4 096 attempts and more (program.hip GR_GUESSED_ATTEMPTS), this frame's lattice launch traces the same pixels beside its
-                // tiles.  Whole frames that find the device idle (GR_ADAPTIVE_GUESS=0: never).
-                // (a guess is a PIXEL: it is right when the picture has not moved - a viewer whose user is looking, or dragging a slider -
-                // and a ray traced for nothing otherwise: used up to half a pixel of motion, GR_ADAPTIVE_GUESS_MAX_MOTION)
-                static const float guess_max_motion = [] { const char* e = getenv("GR_ADAPTIVE_GUESS_MAX_MOTION"); return e ? (float)atof(e) : 0.5f; }();
-                const bool keep_guesses = guesses_wanted && !device_busy;
-                if (keep_guesses && !s->guessed[0])
-                    for (void*& g : s->guessed) { HIP_CHECK(hipMalloc(&g, gr_guessed_bytes())); HIP_CHECK(hipMemsetAsync(g, 0, 32, stream)); }
-                const bool use_guesses = keep_guesses && s->guessed_valid && s->block_cost_valid && !cfg_jumped && !features_changed &&
-                                         s->block_cost_program == gr_program_serial(p) &&
-                                         picture_motion(s->block_cost_camera, *camera, features.field_of_view, width) <= guess_max_motion;
-                if (keep_guesses && !use_guesses) HIP_CHECK(hipMemsetAsync(s->guessed[0], 0, 4, stream));   // (whatever is there is not for this picture)
-                a.guessed = keep_guesses ? s->guessed[0] : nullptr;
-                GR_CHECK(gr_trace_fused_launch(p, stream, &a));
-                a.tile_order = nullptr; a.tile_order_by_history = 0; a.tile_cost = nullptr;   // (the second launch below is not the lattice's)
-                GR_CHECK(end(GR_STAGE_TRACE));
-                GR_CHECK(begin(GR_STAGE_ADAPTIVE));
-                HIP_CHECK(hipMemsetAsync(s->rays_adaptive_count, 0, 4, stream));
-                // the decisions, the marked pixels as a list ordered dearest first, and the second launch over that list: every lane
-                // of every wave has a ray (GR_ADAPTIVE_PENDING_LIST=0: the marked pixels found by walking the image's tiles again)
-                static const bool as_list = [] { const char* e = getenv("GR_ADAPTIVE_PENDING_LIST"); return !(e && e[0] == '0'); }();
-                if (as_list) {
-                    // the list's order: what the lattice rays around a block cost, and - while the picture has moved little since - what
-                    // the block's own rays cost in this state's frame before (the long rays are filaments a pixel or two wide)
-                    static const float history_max_motion = [] { const char* e = getenv("GR_ADAPTIVE_HISTORY_MAX_MOTION"); return e ? (float)atof(e) : 48.f; }();
-                    const size_t image_blocks = (size_t)(width / 2) * (height / 2);
-                    std::swap(s->block_cost, s->block_cost_before);
-                    if (!s->block_cost) HIP_CHECK(hipMalloc(&s->block_cost, image_blocks * sizeof(unsigned int)));
-                    const bool by_history = strip_count == 1 && s->block_cost_valid && s->block_cost_before && !cfg_jumped && !features_changed &&
-                                            s->block_cost_program == gr_program_serial(p) && !gc &&
-                                            picture_motion(s->block_cost_camera, *camera, features.field_of_view, width) <= history_max_motion;
-                    HIP_CHECK(hipMemsetAsync(s->block_cost, 0, image_blocks * sizeof(unsigned int), stream));
-                    GR_CHECK(gr_adaptive_refine_list(p, stream, s->render_data, s->rays_adaptive_count, width, height, s->dfg, block_rows, strip_rank,
-                                                     strip_count, s->lattice_rays, s->cfg, s->pending_list, by_history ? s->block_cost_before : nullptr));
-                    if (keep_guesses) {
-                        HIP_CHECK(hipMemsetAsync(s->guessed[1], 0, 4, stream));
-                        GR_CHECK(gr_apply_guessed(p, stream, s->render_data, width, s->guessed[0], s->guessed[1], s->block_cost, attempts));
-                    }
-                    GR_CHECK(gr_trace_pending(p, stream, s->camera_pos_generic, s->camera_quat, s->render_data, width, height, s->tetrad[0],
-                                              s->tetrad[1], s->tetrad[2], s->tetrad[3], s->cfg, s->dfg, attempts, s->pending_list,
-                                              tune.trace_waves_per_simd, s->block_cost, keep_guesses ? s->guessed[1] : nullptr));
-                    if (keep_guesses) std::swap(s->guessed[0], s->guessed[1]);
-                    s->guessed_valid = keep_guesses;
-                    s->block_cost_valid = strip_count == 1;
-                    s->block_cost_program = gr_program_serial(p);
-                    s->block_cost_camera = *camera;
-                } else {
-                    s->block_cost_valid = false;
-                    s->guessed_valid = false;
-                    GR_CHECK(gr_adaptive_refine_strips(p, stream, s->render_data, s->rays_adaptive_count, width, height, s->dfg, block_rows,
-                                                       strip_rank, strip_count, s->lattice_rays, s->cfg));
-                    a.lattice = 1;
-                    a.pending_only = 1;
-                    a.inline_prepass = 0;
-                    GR_CHECK(gr_trace_fused_launch(p, stream, &a));
-                }
-                GR_CHECK(end(GR_STAGE_ADAPTIVE));
-            } else {
-            if (rays_per_lane == 2)
-                GR_CHECK(gr_trace_pair(p, stream, s->camera_pos_generic, s->camera_quat, s->render_data, width, height, block_rows,
-                                       strip_rank, strip_count, use_prepass ? s->termination_buffer : nullptr,
-                                       use_prepass ? prepass_width : width, use_prepass ? prepass_height : height, s->tetrad[0],
-                                       s->tetrad[1], s->tetrad[2], s->tetrad[3], s->cfg, s->dfg, attempts));
-            else {
-                gr_trace_fused_args a{};
-                a.camera_generic = s->camera_pos_generic; a.camera_quat = s->camera_quat; a.render_data = s->render_data;
-                a.width = width; a.height = height; a.block_rows = block_rows; a.strip_rank = strip_rank; a.strip_count = strip_count;
-                a.termination_buffer = use_prepass ? s->termination_buffer : nullptr;
-                a.prepass_width = use_prepass ? prepass_width : width; a.prepass_height = use_prepass ? prepass_height : height;
-                a.e0 = s->tetrad[0]; a.e1 = s->tetrad[1]; a.e2 = s->tetrad[2]; a.e3 = s->tetrad[3]; a.cfg = s->cfg; a.dfg = s->dfg;
-                a.attempt_counter = attempts;
-                a.tile_order = order_tiles ? s->tile_order : nullptr;
-                GR_CHECK(follow_and_record_history(a));
-                a.waves_per_simd = tune.trace_waves_per_simd;
-                a.inline_prepass = inline_prepass ? 1 : 0;
-                // parking (gr_trace_fused_parking): the lot is the state's, allocated the first time a frame asks for it - room for an
-                // eighth of the frame's rays (a = 0.9 at 4K parks 4 % of them, re-parked ones counted again; a full lot is not an error)
-                static const int park_default[2] = {[] { const char* e = getenv("GR_PARK"); return e ? atoi(e) : 0; }(),
-                                                    [] { const char* e = getenv("GR_PARK"); const char* c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : 0; }()};
-                const int park_lanes = tune.park_lanes < 0 ? park_default[0] : tune.park_lanes;
-                const int park_trips = tune.park_trips > 0 ? tune.park_trips : park_default[1] > 0 ? park_default[1] : 512;
-                if (tune.park_lanes > 1 && !gr_program_has_parking(p))
-                    return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "park_lanes: needs a program built with -DGR_PARKING appended to its argument string");
-                if (park_lanes > 1 && tune.fused_shading != 1 && gr_program_has_parking(p)) {
-                    const int slots = (int)std::min<long long>(1 << 24, std::max<long long>(65536, (long long)width * height / 8));
-                    if (!s->parking_records || s->parking_slots != slots) {
-                        if (s->parking_records) (void)hipFree(s->parking_records);
-                        if (s->parking_words) (void)hipFree(s->parking_words);
-                        s->parking_records = s->parking_words = nullptr;
-                        size_t words_bytes = 0;
-                        const size_t bytes = gr_parking_lot_bytes(slots, slots, &words_bytes);
-                        HIP_CHECK(hipMalloc(&s->parking_records, bytes));
-                        HIP_CHECK(hipMalloc(&s->parking_words, words_bytes));
-                        s->parking_slots = slots;
-                    }
-                    a.parking.records = s->parking_records; a.parking.words = s->parking_words;
-                    a.parking.lanes = std::min(park_lanes, 64); a.parking.trips = park_trips;
-                    a.parking.slots = slots; a.parking.groups = slots;
-                }
-                // the trace shades the pixels whose filter neighbours are in their own tile; gr_render_seams below does the rest
-                shade_in_trace = out && tune.fused_shading == 1 && width % 8 == 0 && height % 8 == 0 && gr_program_has_tile_shading(p);
-                if (tune.fused_shading == 1 && !shade_in_trace && out)   // default: off, on measurement
-                    return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT,
-                                            "fused_shading = 1: needs a program built with -DGR_TILE_SHADING and width, height multiples of 8");
-                if (shade_in_trace) {
-                    a.shading.out = out; a.shading.background1 = bg1; a.shading.background2 = bg2; a.shading.bg_width = bg_width;
-                    a.shading.bg_height = bg_height; a.shading.bg_levels = bg_levels; a.shading.max_probes = opt.max_probes;
-                    a.shading.compact_out = strip_count > 1 ? opt.compact_out : 0;
-                }
-                GR_CHECK(gr_trace_fused_launch(p, stream, &a));
-            }
-            }
-        }
-        if (!adaptive) GR_CHECK(end(GR_STAGE_TRACE));
-        if (inline_prepass) GR_CHECK(inspect_prepass());
-        for (const auto& r : todo) {
-            // a free slot, else the stalest one no current request claims (a camera that was announced but never came)
-            gr_render_state::prefetch_slot* slot = nullptr;
-            int chosen = -1;
-            for (int i = 0; i < gr_render_state::LOOKAHEAD; i++)
-                if (!claimed[i] && (chosen < 0 || (!s->pre[i].valid && s->pre[chosen].valid) ||
-                                    (s->pre[i].valid == s->pre[chosen].valid && s->pre[i].age < s->pre[chosen].age)))
-                    chosen = i;
-            if (chosen >= 0) { slot = &s->pre[chosen]; claimed[chosen] = true; }
-            if (!slot) break;
-            // camera set-up and prepass on the slot's stream, into the slot's buffer set, while the trace runs.  The set may
-            // have belonged to the previous frame (swapped out above): the stream first waits for everything the caller's
-            // stream had queued before this frame's trace.
-            HIP_CHECK(hipStreamWaitEvent(slot->stream, s->main_mark, 0));
-            GR_CHECK(s->uploads.copy(slot->set.camera_pos_cart, r.camera->position, 16, slot->stream));
-            GR_CHECK(s->uploads.copy(slot->set.camera_quat, r.camera->quat, 16, slot->stream));
-            if (one_launch_setup) {
-                GR_CHECK(gr_camera_prepass(p, slot->stream, slot->set.camera_pos_cart, r.camera->flip, r.camera->basis_speed,
-                                           slot->set.camera_pos_generic, slot->set.tetrad[0], slot->set.tetrad[1], slot->set.tetrad[2],
-                                           slot->set.tetrad[3], slot->set.camera_quat, slot->set.termination_buffer, prepass_width,
-                                           prepass_height, s->cfg, s->dfg, height, block_rows, r.strip_rank, strip_count,
-                                           cost_plane(slot->set.termination_buffer), prepass_margin));
-            } else {
-                GR_CHECK(camera_setup(slot->stream, slot->set.camera_pos_cart, slot->set.camera_pos_generic, slot->set.tetrad, r.camera, r.time,
-                                      slot->velocity));
-                GR_CHECK(gr_prepass_fused_strips(p, slot->stream, slot->set.camera_pos_generic, slot->set.camera_quat,
-                                                 slot->set.termination_buffer, prepass_width, prepass_height, slot->set.tetrad[0],
-                                                 slot->set.tetrad[1], slot->set.tetrad[2], slot->set.tetrad[3], s->cfg, s->dfg, height,
-                                                 block_rows, r.strip_rank, strip_count, cost_plane(slot->set.termination_buffer), prepass_margin));
-            }
-            if (order_capable)   // the look-ahead frame's order too: off the frame's critical path like its prepass
-                GR_CHECK(gr_order_tiles(p, slot->stream, slot->set.termination_buffer, cost_plane(slot->set.termination_buffer), prepass_width,
-                                        prepass_height, width, height, block_rows, r.strip_rank, strip_count, slot->set.tile_order));
-            HIP_CHECK(hipEventRecord(slot->ready, slot->stream));
-            slot->valid = true;
-            slot->age = s->frame_counter;
-            slot->key = make_key(r.camera, r.time, r.strip_rank);
-        }
-        s->previous_key_valid = use_prepass && strip_count == 1 && !gc;
-        if (s->previous_key_valid) { s->previous_key = make_key(camera, opt.geodesic_time, opt.strip_rank); s->previous_stream = stream; }
-        if (out) {
-            GR_CHECK(begin(GR_STAGE_RENDER));
-            if (shade_in_trace)
-                GR_CHECK(gr_render_seams(p, stream, s->render_data, out, bg1, bg2, bg_width, bg_height, bg_levels, width, height, block_rows,
-                                         strip_rank, strip_count, strip_count > 1 ? opt.compact_out : 0, opt.max_probes, s->cfg, s->dfg));
-            else
-                GR_CHECK(gr_render_strips(p, stream, s->render_data, out, bg1, bg2, bg_width, bg_height, bg_levels, width, height,
-                                          strip_count > 1 ? block_rows : height, strip_rank, strip_count,
-                                          strip_count > 1 ? opt.compact_out : 0, opt.max_probes, s->cfg, s->dfg));
-            GR_CHECK(end(GR_STAGE_RENDER));
-        }
-        if (history_wanted || guesses_wanted) mark_frame_end(s->device, stream);
-        return GR_OK;
+    // the prepass verdicts a trace or ray set-up reads, and their grid (without a prepass: none, and the image's own size)
+    const void* verdicts() const { return use_prepass ? s->termination_buffer : nullptr; }
+    int grid_width() const { return use_prepass ? prepass_width : width; }
+    int grid_height() const { return use_prepass ? prepass_height : height; }
+    // The prepass rays' costs are kept behind the prepass flags in the termination buffer, which is allocated per pixel
+    void* cost_plane(void* termination_buffer) const { return plan.order_capable ? (void*)((unsigned int*)termination_buffer + plan.cells) : nullptr; }
+    // are costs left by an earlier frame (same program, parameters within a step of a slider) still those of this picture, give or take max_motion px?
+    bool picture_kept(unsigned long long program_then, const gr_camera& camera_then, float max_motion) const {
+        return !cfg_jumped && !features_changed && program_then == gr_program_serial(p) &&
+               picture_motion(camera_then, *camera, features.field_of_view, width) <= max_motion;
     }
+};
 
-    // ---- reference-shaped sequence --------------------------------------------------------------------
-    int tiled = (opt.tiled && !adaptive) ? 1 : 0;
-    size_t slots = tiled ? (size_t)gr_tiled_slot_count(width, height) : (size_t)width * height;
-    GR_CHECK(ensure_rays(s, slots, adaptive));
+// options, tuning, features and $cfg values of this frame
+static int resolve_inputs(frame_context& f, const gr_metric* m, const gr_features* features_in, const float* cfg_values, int num_cfg_values,
+                          const gr_frame_options* opt_in) {
+    gr_frame_options_default(&f.opt);
+    if (opt_in) f.opt = *opt_in;
+    gr_frame_tuning_default(&f.tune);
+    if (f.opt.tuning) f.tune = *f.opt.tuning;
+    f.width = f.s->width; f.height = f.s->height;
+    gr_metric_info info;
+    GR_CHECK(resolve_parameters(m, features_in, cfg_values, num_cfg_values, info, f.features, f.cfg));
+    // The defaults of gr_features (adaptive_sampling on, as the reference's GUI) and of gr_frame_options (fused mode) work
+    // together: a frame is sampled adaptively on the fused path (half-resolution lattice, gr_adaptive_refine, second fused
+    // launch over the marked pixels; cl.cl:3234-3250, 5223-5345) - a device's share of a split frame too: it traces the lattice
+    // rows its blocks' decisions read (two rows of halo either side) and its rows come out as those of the whole frame.
+    f.use_prepass = f.opt.use_prepass < 0 ? info.use_prepass != 0 : f.opt.use_prepass != 0;
+    f.adaptive = f.features.adaptive_sampling != 0 && !f.features.use_triangle_rendering;
+    // The 2x2 blocks of handle_adaptive_sampling cover 2 (W/2) x 2 (H/2) pixels (cl.cl:5228-5236): with an odd width or height the
+    // last column or row belongs to no block and would keep whatever its record held.  The fused path then traces every pixel.
+    if (f.opt.mode == GR_MODE_FUSED && ((f.width | f.height) & 1)) f.adaptive = false;
+    return GR_OK;
+}
 
-    if (use_prepass) {
-        GR_CHECK(begin(GR_STAGE_PREPASS));
+// what changed since the state's last frame, and what that invalidates
+static void note_parameter_changes(frame_context& f) {
+    gr_render_state* s = f.s;
+    f.cfg_changed = f.cfg != s->host_cfg;
+    // ... by a step of a slider (every parameter within a tenth of itself): the picture is nearly the one before, and what its tiles cost is
+    // still the best estimate there is of what they cost now - orders are only orders, a wrong one costs time, never a record.  A frame of a
+    // slider being dragged (the dynamic program, new parameters every frame: metric_manager.hpp:60-66) would otherwise start from image
+    // order every time (4K Kerr: 6.0 ms against 5.1).
+    f.cfg_jumped = f.cfg_changed && [&] {
+        if (f.cfg.size() != s->host_cfg.size()) return true;
+        for (size_t i = 0; i < f.cfg.size(); i++) {
+            const float a = f.cfg[i], b = s->host_cfg[i];
+            if (!(std::fabs(a - b) <= 0.1f * std::max(std::max(std::fabs(a), std::fabs(b)), 0.05f))) return true;
+        }
+        return false;
+    }();
+    f.features_changed = !s->features_valid || memcmp(&f.features, &s->host_features, sizeof(f.features)) != 0;
+    // another metric, parameter set or field of view: what the last frame's tiles cost says nothing about this one's (tile_history)
+    if (f.cfg_jumped || f.features_changed || gr_program_serial(f.p) != s->tile_cost_program) {
+        s->tile_cost_valid = false;
+        s->tile_cost_program = gr_program_serial(f.p);
+    }
+}
+
+// use_prepass = -2: does this frame run its prepass (gr_render_state::prepass_policy)?
+static int apply_prepass_policy(frame_context& f) {
+    gr_render_state* s = f.s;
+    f.prepass_by_policy = f.opt.use_prepass == -2 && f.use_prepass && f.opt.mode == GR_MODE_FUSED && f.opt.strip_count <= 1;
+    if (!f.prepass_by_policy) return GR_OK;
+    auto& pol = s->policy;
+    const unsigned long long serial = gr_program_serial(f.p);
+    if (f.cfg_changed || f.features_changed || serial != s->policy_program) {   // another metric or parameter set: start over
+        pol.holiday = 0;
+        pol.last_fraction = -1.f;
+        if (pol.in_flight) { HIP_CHECK(hipEventSynchronize(pol.copied)); pol.in_flight = false; }
+        s->policy_program = serial;
+    }
+    if (pol.in_flight && hipEventQuery(pol.copied) == hipSuccess) {
+        // the share of the grid whose 5-point stencil is marked throughout: what init_rays_generic's test lets the trace skip
+        // (a pixel is skipped when the cell it rounds to and that cell's four neighbours are all marked, cl.cl:3213-3232)
+        size_t skippable = 0;
+        const int pw = pol.grid_width, ph = pol.cells && pw ? (int)(pol.cells / pw) : 0;
+        for (int y = 1; y + 1 < ph; y++)
+            for (int x = 1; x + 1 < pw; x++) {
+                const int* c = pol.host_flags + (size_t)y * pw + x;
+                skippable += c[0] == 1 && c[-1] == 1 && c[1] == 1 && c[-pw] == 1 && c[pw] == 1;
+            }
+        pol.last_fraction = pol.cells ? (float)skippable / (float)pol.cells : 0.f;
+        pol.in_flight = false;
+        if (pol.last_fraction < gr_render_state::PREPASS_MIN_SKIP) pol.holiday = gr_render_state::PREPASS_HOLIDAY;
+    } else if (pol.in_flight) {
+        (void)hipGetLastError();   // hipErrorNotReady is not an error
+    }
+    if (pol.holiday > 0) { pol.holiday--; pol.without_prepass++; f.use_prepass = false; }
+    else pol.with_prepass++;
+    return GR_OK;
+}
+
+// ... its flags -> host, behind the prepass on the frame's stream; read when a later frame finds them there
+static int inspect_prepass(frame_context& f) {
+    gr_render_state* s = f.s;
+    auto& pol = s->policy;
+    const size_t cells = f.plan.cells;
+    if (!(f.prepass_by_policy && f.use_prepass && !pol.in_flight)) return GR_OK;
+    if (pol.capacity < cells) {
+        if (pol.host_flags) (void)hipHostFree(pol.host_flags);
+        pol.host_flags = nullptr;
+        HIP_CHECK(hipHostMalloc((void**)&pol.host_flags, cells * sizeof(int), hipHostMallocDefault));
+        pol.capacity = cells;
+    }
+    if (!pol.copied) HIP_CHECK(hipEventCreateWithFlags(&pol.copied, hipEventDisableTiming));
+    HIP_CHECK(hipMemcpyAsync(pol.host_flags, s->termination_buffer, cells * sizeof(int), hipMemcpyDeviceToHost, f.stream));
+    HIP_CHECK(hipEventRecord(pol.copied, f.stream));
+    pol.cells = cells;
+    pol.grid_width = f.prepass_width;
+    pol.in_flight = true;
+    return GR_OK;
+}
+
+// new parameters go to the device, behind the look-ahead prepasses that still read the old ones
+static int upload_parameters(frame_context& f) {
+    gr_render_state* s = f.s;
+    if (f.cfg_changed || f.features_changed) {
+        // Look-ahead prepasses read s->cfg / s->dfg on their side streams: the upload below must not overtake one that is still
+        // running (it would read a mix of old and new parameters), and what the slots hold was computed for the old parameters.
+        for (auto& slot : s->pre) {
+            if (!slot.valid) continue;
+            HIP_CHECK(hipStreamWaitEvent(f.stream, slot.ready, 0));
+            slot.valid = false;
+        }
+    }
+    if (f.cfg_changed) {
+        GR_CHECK(s->uploads.copy(s->cfg, f.cfg.data(), f.cfg.size() * sizeof(float), f.stream));
+        s->host_cfg = f.cfg;
+    }
+    if (f.features_changed) {
+        GR_CHECK(s->uploads.copy(s->dfg, &f.features, sizeof(f.features), f.stream));
+        s->host_features = f.features;
+        s->features_valid = true;
+    }
+    return GR_OK;
+}
+
+// Was this frame's camera set-up + prepass already done - on a side stream during an earlier frame, or by the previous frame?
+static int take_prepared_setup(frame_context& f) {
+    gr_render_state* s = f.s;
+    const gr_frame_options& opt = f.opt;
+    f.prepass_width = f.width / 16; f.prepass_height = f.height / 16;   // main.cpp:2380-2381
+    if (f.prepass_width < 1 || f.prepass_height < 1) f.use_prepass = false;
+    s->frame_counter++;
+    if (opt.mode == GR_MODE_FUSED && f.use_prepass) {
+        const auto want = f.own_key();
+        gr_render_state::prefetch_slot* hit = nullptr;   // the oldest matching prefetch: it has had the most time to finish
+        for (auto& slot : s->pre)
+            if (slot.valid && slot.key == want && (!hit || slot.age < hit->age)) hit = &slot;
+        if (hit) {
+            s->swap_in(hit->set);
+            HIP_CHECK(hipStreamWaitEvent(f.stream, hit->ready, 0));
+            hit->valid = false;
+            f.prefetched = true;
+        }
+    }
+    // ... or is it the previous frame of this state over again - camera, parameters, features, program, bit for bit, on the same stream
+    // (gr_frame_tuning.reuse_still_camera)?  Camera position, tetrad and the prepass verdicts are functions of exactly those, and they are
+    // where that frame left them: a viewer whose user has stopped moving pays neither again (the reference does, every frame:
+    // main.cpp:2311-2437).  Whole frames with a Cartesian camera whose tiles are not ordered by the prepass rays' costs.
+    const int tile_order_mode = switches::tile_order();
+    const bool reuse_default = switches::reuse_still_camera();
+    f.repeats_previous_frame = opt.mode == GR_MODE_FUSED && f.use_prepass && !opt.geodesic && opt.strip_count <= 1 && s->previous_key_valid &&
+                               s->previous_key == f.own_key();
+    f.reuse_on = (f.tune.reuse_still_camera < 0 ? reuse_default : f.tune.reuse_still_camera != 0) && tile_order_mode != 1;
+    if (!f.prefetched && f.repeats_previous_frame && f.reuse_on && s->previous_stream == f.stream) {
+        f.prefetched = true;
+        s->prepass_reused++;
+    }
+    s->previous_key_valid = false;   // until this frame has left its own set-up and prepass behind
+    if (!f.prefetched) {
+        GR_CHECK(s->uploads.copy(s->camera_pos_cart, f.camera->position, 16, f.stream));
+        GR_CHECK(s->uploads.copy(s->camera_quat, f.camera->quat, 16, f.stream));
+    }
+    return GR_OK;
+}
+
+// timers and counters of this frame, and the camera set-up where it is a launch of its own
+static int begin_frame(frame_context& f) {
+    gr_render_state* s = f.s;
+    for (int i = 0; i < GR_STAGE_COUNT; i++) s->stage_timed[i] = false;
+    f.log_trace = f.opt.time_kernels == 2;
+    if (f.log_trace && s->trace_log_used == s->trace_log.size()) {
+        hipEvent_t a = nullptr, b = nullptr;
+        HIP_CHECK(hipEventCreate(&a));
+        HIP_CHECK(hipEventCreate(&b));
+        s->trace_log.emplace_back(a, b);
+    }
+    if (f.tune.count_attempts) {
+        HIP_CHECK(hipMemsetAsync(s->attempts, 0, GR_COUNTER_WORDS * 8, f.stream));
+        f.attempts = s->attempts;
+    }
+    f.gc = f.opt.geodesic;
+    if (f.gc && f.gc->device != s->device) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "geodesic camera lives on another device");
+    // fused mode with a Cartesian camera: camera set-up and prepass are one call (gr_camera_prepass), issued by fused_setup_and_prepass
+    f.one_launch_setup = f.opt.mode == GR_MODE_FUSED && !f.gc;
+    if (!f.prefetched && !f.one_launch_setup) {
+        GR_CHECK(f.begin(GR_STAGE_CAMERA));
+        GR_CHECK(f.camera_setup(f.stream, s->camera_pos_cart, s->camera_pos_generic, s->tetrad, f.camera, f.opt.geodesic_time,
+                                f.gc ? f.gc->interpolated_velocity : nullptr));
+        GR_CHECK(f.end(GR_STAGE_CAMERA));
+    }
+    return GR_OK;
+}
+
+// ---- the fused path ------------------------------------------------------------------------------------------------------------
+// frame_plan::plan_fused's inputs from the frame, the program and the state; its refusal, and the one write it asks for
+static int fused_plan_frame(frame_context& f) {
+    gr_render_state* s = f.s;
+    frame_plan::fused_input in;
+    in.width = f.width; in.height = f.height;
+    in.strip_count = f.opt.strip_count; in.strip_rank = f.opt.strip_rank; in.block_rows = f.opt.block_rows;
+    in.adaptive = f.adaptive; in.use_prepass = f.use_prepass; in.prefetched = f.prefetched; in.geodesic = f.gc != nullptr; in.out = f.out != nullptr;
+    in.tune = f.tune;
+    in.has_pair = gr_program_has_trace_pair(f.p) != 0; in.has_parking = gr_program_has_parking(f.p) != 0;
+    in.has_tile_shading = gr_program_has_tile_shading(f.p) != 0;
+    in.wave_slots = [&] { return gr_trace_fused_wave_slots(f.p); };
+    in.tile_order_bytes = gr_tile_order_bytes;
+    in.earlier_frame_still_running = [&] { return earlier_frame_still_running(s->device, f.stream); };
+    in.tile_order_bytes_held = s->tile_order_bytes;
+    in.tile_cost_valid = s->tile_cost_valid; in.tile_cost_anchored = s->tile_cost_anchored;
+    memcpy(in.tile_cost_shape, s->tile_cost_shape, sizeof(in.tile_cost_shape));
+    in.tile_cost_camera = s->tile_cost_camera; in.camera = *f.camera;
+    in.field_of_view = f.features.field_of_view;
+    f.plan = frame_plan::plan_fused(in);
+    if (f.plan.refused.code != GR_OK) return gr_internal_fail(f.plan.refused.code, f.plan.refused.message);
+    if (f.plan.invalidate_tile_cost) s->tile_cost_valid = false;
+    return GR_OK;
+}
+
+// camera set-up and prepass of one frame on one stream into one buffer set (this frame's, or a look-ahead slot's), and the order its costs give
+static int fused_setup_and_prepass(frame_context& f, hipStream_t stream, const gr_render_state::camera_set& set, const gr_camera* cam, float time,
+                                   int strip_rank, void* velocity, bool prepass_in_front, bool order_tiles) {
+    gr_render_state* s = f.s;
+    const auto& q = f.plan;
+    void* const costs = f.cost_plane(set.termination_buffer);
+    if (f.one_launch_setup) {
+        GR_CHECK(gr_camera_prepass(f.p, stream, set.camera_pos_cart, cam->flip, cam->basis_speed, set.camera_pos_generic, set.tetrad[0], set.tetrad[1],
+                                   set.tetrad[2], set.tetrad[3], set.camera_quat, set.termination_buffer, prepass_in_front ? f.prepass_width : 0,
+                                   prepass_in_front ? f.prepass_height : 0, s->cfg, s->dfg, f.height, q.block_rows, strip_rank, q.strip_count, costs,
+                                   q.prepass_margin));
+    } else {
+        if (velocity) GR_CHECK(f.camera_setup(stream, set.camera_pos_cart, set.camera_pos_generic, set.tetrad, cam, time, velocity));
+        GR_CHECK(gr_prepass_fused_strips(f.p, stream, set.camera_pos_generic, set.camera_quat, set.termination_buffer, f.prepass_width, f.prepass_height,
+                                         set.tetrad[0], set.tetrad[1], set.tetrad[2], set.tetrad[3], s->cfg, s->dfg, f.height, q.block_rows, strip_rank,
+                                         q.strip_count, costs, q.prepass_margin));
+    }
+    if (order_tiles)
+        GR_CHECK(gr_order_tiles(f.p, stream, set.termination_buffer, costs, f.prepass_width, f.prepass_height, f.width, f.height, q.block_rows,
+                                strip_rank, q.strip_count, set.tile_order));
+    return GR_OK;
+}
+
+// this frame's own, unless it was prepared (take_prepared_setup); a camera on a geodesic was set up by begin_frame
+static int fused_own_setup(frame_context& f) {
+    gr_render_state* s = f.s;
+    if (f.prefetched || !(f.one_launch_setup || f.use_prepass)) return GR_OK;
+    gr_render_state::camera_set own;
+    own.camera_pos_cart = s->camera_pos_cart; own.camera_quat = s->camera_quat; own.camera_pos_generic = s->camera_pos_generic;
+    for (int i = 0; i < 4; i++) own.tetrad[i] = s->tetrad[i];
+    own.termination_buffer = s->termination_buffer; own.tile_order = s->tile_order;
+    GR_CHECK(f.begin(GR_STAGE_PREPASS));
+    GR_CHECK(fused_setup_and_prepass(f, f.stream, own, f.camera, f.opt.geodesic_time, f.plan.strip_rank, nullptr, f.use_prepass && !f.plan.inline_prepass,
+                                     f.plan.order_tiles));
+    return f.end(GR_STAGE_PREPASS);
+}
+
+// the look-ahead requests (gr_frame_options.next_camera / next_camera2) that are not already sitting in a slot
+static int fused_collect_look_ahead(frame_context& f) {
+    gr_render_state* s = f.s;
+    const auto& q = f.plan;
+    if (f.use_prepass) {
+        frame_context::request asked[2] = {{f.opt.next_camera, f.tune.next_geodesic_time, f.tune.next_strip_rank},
+                                           {f.opt.next_camera2, f.tune.next_geodesic_time2, f.tune.next_strip_rank2}};
+        // nobody announced the next camera, and this frame is the previous one over again: the guess "the same once more"
+        // (gr_frame_tuning.guess_still_camera, off by default since reuse_still_camera does without the prepass altogether) - used
+        // by the next frame only if its key matches bit for bit
+        const bool guess_default = switches::guess_still_camera();
+        if (!f.opt.next_camera && !f.opt.next_camera2 && !f.gc && q.strip_count == 1 && (f.tune.guess_still_camera < 0 ? guess_default : f.tune.guess_still_camera != 0) &&
+            f.repeats_previous_frame && !f.reuse_on)
+            asked[0] = {f.camera, f.opt.geodesic_time, -1};
+        for (auto& r : asked) {
+            if (!r.camera) continue;
+            if (r.strip_rank < 0 || r.strip_rank >= q.strip_count) r.strip_rank = q.strip_rank;
+            const auto k = f.make_key(r.camera, r.time, r.strip_rank);
+            bool have = false;
+            for (int i = 0; i < gr_render_state::LOOKAHEAD && !have; i++)
+                if (!f.claimed[i] && s->pre[i].valid && s->pre[i].key == k) f.claimed[i] = have = true;
+            if (!have) f.todo.push_back(r);
+        }
+    }
+    if (!f.todo.empty()) HIP_CHECK(hipEventRecord(s->main_mark, f.stream));   // everything up to here is older than the prefetches
+    return GR_OK;
+}
+
+// ... each on a side stream, into a slot's buffer set, while this frame traces
+static int fused_submit_look_ahead(frame_context& f) {
+    gr_render_state* s = f.s;
+    for (const auto& r : f.todo) {
+        // a free slot, else the stalest one no current request claims (a camera that was announced but never came)
+        int chosen = -1;
+        for (int i = 0; i < gr_render_state::LOOKAHEAD; i++)
+            if (!f.claimed[i] && (chosen < 0 || (!s->pre[i].valid && s->pre[chosen].valid) ||
+                                  (s->pre[i].valid == s->pre[chosen].valid && s->pre[i].age < s->pre[chosen].age)))
+                chosen = i;
+        if (chosen < 0) break;
+        gr_render_state::prefetch_slot* slot = &s->pre[chosen];
+        f.claimed[chosen] = true;
+        // camera set-up and prepass on the slot's stream, into the slot's buffer set, while the trace runs.  The set may
+        // have belonged to the previous frame (swapped out above): the stream first waits for everything the caller's
+        // stream had queued before this frame's trace.
+        HIP_CHECK(hipStreamWaitEvent(slot->stream, s->main_mark, 0));
+        GR_CHECK(s->uploads.copy(slot->set.camera_pos_cart, r.camera->position, 16, slot->stream));
+        GR_CHECK(s->uploads.copy(slot->set.camera_quat, r.camera->quat, 16, slot->stream));
+        // (the look-ahead frame's order too: off the frame's critical path like its prepass)
+        GR_CHECK(fused_setup_and_prepass(f, slot->stream, slot->set, r.camera, r.time, r.strip_rank, slot->velocity, true, f.plan.order_capable));
+        HIP_CHECK(hipEventRecord(slot->ready, slot->stream));
+        slot->valid = true;
+        slot->age = s->frame_counter;
+        slot->key = f.make_key(r.camera, r.time, r.strip_rank);
+    }
+    return GR_OK;
+}
+
+// what every launch of gr_trace_fused of this frame is given
+static gr_trace_fused_args fused_trace_args(const frame_context& f) {
+    const gr_render_state* s = f.s;
+    gr_trace_fused_args a{};
+    a.camera_generic = s->camera_pos_generic; a.camera_quat = s->camera_quat; a.render_data = s->render_data;
+    a.width = f.width; a.height = f.height; a.block_rows = f.plan.block_rows; a.strip_rank = f.plan.strip_rank; a.strip_count = f.plan.strip_count;
+    a.termination_buffer = f.verdicts(); a.prepass_width = f.grid_width(); a.prepass_height = f.grid_height();
+    a.e0 = s->tetrad[0]; a.e1 = s->tetrad[1]; a.e2 = s->tetrad[2]; a.e3 = s->tetrad[3]; a.cfg = s->cfg; a.dfg = s->dfg;
+    a.attempt_counter = f.attempts;
+    a.waves_per_simd = f.tune.trace_waves_per_simd;
+    a.inline_prepass = f.plan.inline_prepass ? 1 : 0;
+    return a;
+}
+
+// the order of the frame before's costs and the record of this frame's, for the launch that traces the frame's tiles
+// (gr_trace_fused on every pixel, or the lattice launch of adaptive sampling: tiles of 8 x 8 lattice pixels = 16 x 16 pixels)
+static int follow_and_record_history(frame_context& f, gr_trace_fused_args& a) {
+    gr_render_state* s = f.s;
+    const auto& q = f.plan;
+    float anchor[2] = {0, 0};
+    const bool anchored = q.record_history && !f.gc && origin_on_screen(*f.camera, f.features.field_of_view, f.width, f.height, anchor);
+    if (q.history_order) {
+        // how far the picture has moved since the costs were recorded, in tiles
+        int shift[2] = {0, 0};
+        if (switches::tile_history_follow() && anchored && s->tile_cost_anchored)
+            for (int i = 0; i < 2; i++)
+                shift[i] = (int)std::lround(std::max(-4096.f, std::min(4096.f, (anchor[i] - s->tile_cost_anchor[i]) / (f.adaptive ? 16.f : 8.f))));
+        GR_CHECK(gr_order_tiles_by_history(f.p, f.stream, s->tile_cost, q.hist_width, q.hist_height, q.hist_block_rows, q.strip_rank, q.strip_count,
+                                           s->tile_order, shift[0], shift[1]));
+        s->history_followed++;
+        s->history_last_shift[0] = shift[0]; s->history_last_shift[1] = shift[1];
+        a.tile_order = s->tile_order;
+        a.tile_order_by_history = 1;
+        a.speculative_classes = f.tune.speculative_classes < 0 ? 0 : f.tune.speculative_classes == 0 ? -1 : f.tune.speculative_classes;
+    }
+    if (q.record_history) {
+        a.tile_cost = s->tile_cost;
+        s->history_recorded++;
+        memcpy(s->tile_cost_shape, q.shape, sizeof(q.shape));
+        s->tile_cost_valid = true;
+        s->tile_cost_anchored = anchored;
+        s->tile_cost_anchor[0] = anchor[0]; s->tile_cost_anchor[1] = anchor[1];
+        s->tile_cost_camera = *f.camera;
+    }
+    return GR_OK;
+}
+
+// every pixel, one ray per lane: gr_trace_fused, with parking and in-tile shading where the plan has them
+static int fused_trace_full(frame_context& f) {
+    gr_render_state* s = f.s;
+    const auto& q = f.plan;
+    gr_trace_fused_args a = fused_trace_args(f);
+    a.tile_order = q.order_tiles ? s->tile_order : nullptr;
+    GR_CHECK(follow_and_record_history(f, a));
+    if (q.refused_at_trace.code != GR_OK) return gr_internal_fail(q.refused_at_trace.code, q.refused_at_trace.message);
+    // parking (gr_trace_fused_parking): the lot is the state's, allocated the first time a frame asks for it - room for an
+    // eighth of the frame's rays (a = 0.9 at 4K parks 4 % of them, re-parked ones counted again; a full lot is not an error)
+    if (q.parking) {
+        const int slots = (int)std::min<long long>(1 << 24, std::max<long long>(65536, (long long)f.width * f.height / 8));
+        if (!s->parking_records || s->parking_slots != slots) {
+            if (s->parking_records) (void)hipFree(s->parking_records);
+            if (s->parking_words) (void)hipFree(s->parking_words);
+            s->parking_records = s->parking_words = nullptr;
+            size_t words_bytes = 0;
+            const size_t bytes = gr_parking_lot_bytes(slots, slots, &words_bytes);
+            HIP_CHECK(hipMalloc(&s->parking_records, bytes));
+            HIP_CHECK(hipMalloc(&s->parking_words, words_bytes));
+            s->parking_slots = slots;
+        }
+        a.parking.records = s->parking_records; a.parking.words = s->parking_words;
+        a.parking.lanes = std::min(q.park_lanes, 64); a.parking.trips = q.park_trips;
+        a.parking.slots = slots; a.parking.groups = slots;
+    }
+    // the trace shades the pixels whose filter neighbours are in their own tile; gr_render_seams (fused_shade) does the rest
+    if (q.shade_in_trace) {
+        a.shading.out = f.out; a.shading.background1 = f.bg1; a.shading.background2 = f.bg2; a.shading.bg_width = f.bg_width;
+        a.shading.bg_height = f.bg_height; a.shading.bg_levels = f.bg_levels; a.shading.max_probes = f.opt.max_probes;
+        a.shading.compact_out = q.strip_count > 1 ? f.opt.compact_out : 0;
+    }
+    return gr_trace_fused_launch(f.p, f.stream, &a);
+}
+
+// adaptive sampling: a quarter of the primary rays (the pixels (2x, 2y)), then the blocks that need it refined by a second launch
+static int fused_trace_adaptive(frame_context& f) {
+    gr_render_state* s = f.s;
+    gr_program* p = f.p;
+    hipStream_t stream = f.stream;
+    const auto& q = f.plan;
+    const int width = f.width, height = f.height;
+    gr_trace_fused_args a = fused_trace_args(f);
+    a.lattice = 2;
+    if (!s->lattice_rays) HIP_CHECK(hipMalloc(&s->lattice_rays, gr_lattice_rays_bytes(width, height)));
+    if (!s->pending_list) HIP_CHECK(hipMalloc(&s->pending_list, gr_pending_list_bytes(width, height)));
+    a.lattice_rays = s->lattice_rays;
+    GR_CHECK(follow_and_record_history(f, a));
+    // Tracing ahead what the second launch will ask for (gr_apply_guessed): where the frame before's second launch found pixels of
+    // 4 096 attempts and more (program.hip GR_GUESSED_ATTEMPTS), this frame's lattice launch traces the same pixels beside its
+    // tiles.  Whole frames that find the device idle (GR_ADAPTIVE_GUESS=0: never).
+    const float guess_max_motion = switches::adaptive_guess_max_motion();
+    const bool keep_guesses = q.guesses_wanted && !q.device_busy;
+    if (keep_guesses && !s->guessed[0])
+        for (void*& g : s->guessed) { HIP_CHECK(hipMalloc(&g, gr_guessed_bytes())); HIP_CHECK(hipMemsetAsync(g, 0, 32, stream)); }
+    const bool use_guesses = keep_guesses && s->guessed_valid && s->block_cost_valid && f.picture_kept(s->block_cost_program, s->block_cost_camera, guess_max_motion);
+    if (keep_guesses && !use_guesses) HIP_CHECK(hipMemsetAsync(s->guessed[0], 0, 4, stream));   // (whatever is there is not for this picture)
+    a.guessed = keep_guesses ? s->guessed[0] : nullptr;
+    GR_CHECK(gr_trace_fused_launch(p, stream, &a));
+    a.tile_order = nullptr; a.tile_order_by_history = 0; a.tile_cost = nullptr;   // (the second launch below is not the lattice's)
+    GR_CHECK(f.end(GR_STAGE_TRACE));
+    GR_CHECK(f.begin(GR_STAGE_ADAPTIVE));
+    HIP_CHECK(hipMemsetAsync(s->rays_adaptive_count, 0, 4, stream));
+    // the decisions, the marked pixels as a list ordered dearest first, and the second launch over that list: every lane
+    // of every wave has a ray (GR_ADAPTIVE_PENDING_LIST=0: the marked pixels found by walking the image's tiles again)
+    if (switches::adaptive_pending_list()) {
+        // the list's order: what the lattice rays around a block cost, and - while the picture has moved little since - what
+        // the block's own rays cost in this state's frame before (the long rays are filaments a pixel or two wide)
+        const float history_max_motion = switches::adaptive_history_max_motion();
+        const size_t image_blocks = (size_t)(width / 2) * (height / 2);
+        std::swap(s->block_cost, s->block_cost_before);
+        if (!s->block_cost) HIP_CHECK(hipMalloc(&s->block_cost, image_blocks * sizeof(unsigned int)));
+        const bool by_history = q.strip_count == 1 && s->block_cost_valid && s->block_cost_before && !f.gc &&
+                                f.picture_kept(s->block_cost_program, s->block_cost_camera, history_max_motion);
+        HIP_CHECK(hipMemsetAsync(s->block_cost, 0, image_blocks * sizeof(unsigned int), stream));
+        GR_CHECK(gr_adaptive_refine_list(p, stream, s->render_data, s->rays_adaptive_count, width, height, s->dfg, q.block_rows, q.strip_rank,
+                                         q.strip_count, s->lattice_rays, s->cfg, s->pending_list, by_history ? s->block_cost_before : nullptr));
+        if (keep_guesses) {
+            HIP_CHECK(hipMemsetAsync(s->guessed[1], 0, 4, stream));
+            GR_CHECK(gr_apply_guessed(p, stream, s->render_data, width, s->guessed[0], s->guessed[1], s->block_cost, f.attempts));
+        }
+        GR_CHECK(gr_trace_pending(p, stream, s->camera_pos_generic, s->camera_quat, s->render_data, width, height, s->tetrad[0],
+                                  s->tetrad[1], s->tetrad[2], s->tetrad[3], s->cfg, s->dfg, f.attempts, s->pending_list,
+                                  f.tune.trace_waves_per_simd, s->block_cost, keep_guesses ? s->guessed[1] : nullptr));
+        if (keep_guesses) std::swap(s->guessed[0], s->guessed[1]);
+        s->guessed_valid = keep_guesses;
+        s->block_cost_valid = q.strip_count == 1;
+        s->block_cost_program = gr_program_serial(p);
+        s->block_cost_camera = *f.camera;
+    } else {
+        s->block_cost_valid = false;
+        s->guessed_valid = false;
+        GR_CHECK(gr_adaptive_refine_strips(p, stream, s->render_data, s->rays_adaptive_count, width, height, s->dfg, q.block_rows,
+                                           q.strip_rank, q.strip_count, s->lattice_rays, s->cfg));
+        a.lattice = 1;
+        a.pending_only = 1;
+        a.inline_prepass = 0;
+        GR_CHECK(gr_trace_fused_launch(p, stream, &a));
+    }
+    return f.end(GR_STAGE_ADAPTIVE);
+}
+
+// every device runs the (tiny) prepass itself; its own row blocks (+ one halo row each) are traced here, by the kernel the plan names
+static int fused_trace(frame_context& f) {
+    gr_render_state* s = f.s;
+    const auto& q = f.plan;
+    GR_CHECK(f.begin(GR_STAGE_TRACE));
+    if (q.keep_lanes > 0)
+        GR_CHECK(gr_trace_compact(f.p, f.stream, s->camera_pos_generic, s->camera_quat, s->render_data, f.width, f.height, q.block_rows, q.strip_rank,
+                                  q.strip_count, f.verdicts(), f.grid_width(), f.grid_height(), s->tetrad[0], s->tetrad[1], s->tetrad[2], s->tetrad[3],
+                                  s->cfg, s->dfg, f.attempts, q.keep_lanes));
+    else if (f.adaptive)
+        return fused_trace_adaptive(f);   // (ends GR_STAGE_TRACE behind its lattice launch)
+    else if (q.rays_per_lane == 2)
+        GR_CHECK(gr_trace_pair(f.p, f.stream, s->camera_pos_generic, s->camera_quat, s->render_data, f.width, f.height, q.block_rows, q.strip_rank,
+                               q.strip_count, f.verdicts(), f.grid_width(), f.grid_height(), s->tetrad[0], s->tetrad[1], s->tetrad[2], s->tetrad[3],
+                               s->cfg, s->dfg, f.attempts));
+    else
+        GR_CHECK(fused_trace_full(f));
+    return f.end(GR_STAGE_TRACE);
+}
+
+static int fused_shade(frame_context& f) {
+    gr_render_state* s = f.s;
+    const auto& q = f.plan;
+    const int compact_out = q.strip_count > 1 ? f.opt.compact_out : 0;
+    if (!f.out) return GR_OK;
+    GR_CHECK(f.begin(GR_STAGE_RENDER));
+    if (q.shade_in_trace)
+        GR_CHECK(gr_render_seams(f.p, f.stream, s->render_data, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height, f.bg_levels, f.width, f.height, q.block_rows,
+                                 q.strip_rank, q.strip_count, compact_out, f.opt.max_probes, s->cfg, s->dfg));
+    else
+        GR_CHECK(gr_render_strips(f.p, f.stream, s->render_data, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height, f.bg_levels, f.width, f.height,
+                                  q.strip_count > 1 ? q.block_rows : f.height, q.strip_rank, q.strip_count, compact_out, f.opt.max_probes, s->cfg, s->dfg));
+    return f.end(GR_STAGE_RENDER);
+}
+
+static int render_fused(frame_context& f) {
+    gr_render_state* s = f.s;
+    GR_CHECK(fused_plan_frame(f));
+    GR_CHECK(fused_own_setup(f));
+    GR_CHECK(fused_collect_look_ahead(f));
+    if (!f.plan.inline_prepass) GR_CHECK(inspect_prepass(f));   // (with the prepass inside the trace launch: after it)
+    GR_CHECK(fused_trace(f));
+    if (f.plan.inline_prepass) GR_CHECK(inspect_prepass(f));
+    GR_CHECK(fused_submit_look_ahead(f));
+    s->previous_key_valid = f.use_prepass && f.plan.strip_count == 1 && !f.gc;
+    if (s->previous_key_valid) { s->previous_key = f.own_key(); s->previous_stream = f.stream; }
+    GR_CHECK(fused_shade(f));
+    if (f.plan.history_wanted || f.plan.guesses_wanted) mark_frame_end(s->device, f.stream);
+    return GR_OK;
+}
+
+// ---- the reference-shaped sequence ---------------------------------------------------------------------------------------------
+// Rays in tile slot order are traced the way the fused kernel's tiles are: the device filled once, tiles by ticket, dearest first by
+// what they cost in this state's frame before while the picture has moved little since (GR_REFERENCE_SCHEDULED=0: the reference's own
+// launch shape, one work item per record).  The records are the same either way.
+static int reference_trace_scheduled(frame_context& f) {
+    gr_render_state* s = f.s;
+    const int tiles_x = (f.width + 7) / 8, tiles_y = (f.height + 7) / 8, tile_count = tiles_x * tiles_y;
+    if (s->ref_cost_tiles != tile_count) {
+        for (void*& b : s->ref_cost) { if (b) (void)hipFree(b); b = nullptr; }
+        if (s->ref_order) (void)hipFree(s->ref_order);
+        if (s->ref_sort_work) (void)hipFree(s->ref_sort_work);
+        s->ref_order = s->ref_sort_work = nullptr;
+        for (void*& b : s->ref_cost) HIP_CHECK(hipMalloc(&b, (size_t)tile_count * sizeof(unsigned int)));
+        HIP_CHECK(hipMalloc(&s->ref_order, (size_t)tile_count * sizeof(unsigned int)));
+        HIP_CHECK(hipMalloc(&s->ref_sort_work, ((size_t)tile_count + 128) * sizeof(unsigned int)));
+        s->ref_cost_tiles = tile_count;
+        s->ref_cost_valid = false;
+    }
+    const float max_motion = switches::tile_history_max_motion();
+    const bool follow = s->ref_cost_valid && !f.gc && f.picture_kept(s->ref_cost_program, s->ref_cost_camera, max_motion);
+    std::swap(s->ref_cost[0], s->ref_cost[1]);
+    if (follow) {
+        GR_CHECK(gr_sort_tiles_by_cost(f.p, f.stream, s->ref_cost[1], tiles_x, tiles_y, s->ref_order, s->ref_sort_work));
+        s->history_followed++;
+    }
+    s->history_recorded++;
+    GR_CHECK(gr_do_generic_rays_scheduled(f.p, f.stream, s->rays_in, s->rays_count_in, tile_count, s->cfg, s->dfg, f.attempts,
+                                          follow ? s->ref_order : nullptr, s->ref_cost[0]));
+    s->ref_cost_valid = true;
+    s->ref_cost_camera = *f.camera;
+    s->ref_cost_program = gr_program_serial(f.p);
+    return GR_OK;
+}
+
+static int render_reference_shaped(frame_context& f) {
+    gr_render_state* s = f.s;
+    gr_program* p = f.p;
+    hipStream_t stream = f.stream;
+    const int width = f.width, height = f.height, prepass_width = f.prepass_width, prepass_height = f.prepass_height;
+    const int tiled = (f.opt.tiled && !f.adaptive) ? 1 : 0;
+    const size_t slots = tiled ? (size_t)gr_tiled_slot_count(width, height) : (size_t)width * height;
+    GR_CHECK(ensure_rays(s, slots, f.adaptive));
+
+    if (f.use_prepass) {
+        GR_CHECK(f.begin(GR_STAGE_PREPASS));
         GR_CHECK(gr_clear_termination_buffer(p, stream, s->termination_buffer, prepass_width, prepass_height));
         HIP_CHECK(hipMemsetAsync(s->rays_count_in, 0, 4, stream));
         GR_CHECK(gr_init_rays_generic(p, stream, s->camera_pos_generic, s->camera_quat, s->rays_in, s->rays_count_in,
@@ -1491,80 +1482,108 @@ static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metri
                                     s->cfg, s->dfg, width, height, 0, 0, nullptr, nullptr, 0, nullptr));
         GR_CHECK(gr_calculate_singularities(p, stream, s->rays_in, s->rays_count_in, prepass_width * prepass_height,
                                             s->termination_buffer, prepass_width, prepass_height));
-        GR_CHECK(end(GR_STAGE_PREPASS));
+        GR_CHECK(f.end(GR_STAGE_PREPASS));
     }
-    int pw = use_prepass ? prepass_width : width, ph = use_prepass ? prepass_height : height;
 
-    GR_CHECK(begin(GR_STAGE_INIT));
+    GR_CHECK(f.begin(GR_STAGE_INIT));
     GR_CHECK(gr_init_rays_generic(p, stream, s->camera_pos_generic, s->camera_quat, s->rays_in, s->rays_count_in, width, height,
-                                  s->termination_buffer, pw, ph, 0, s->tetrad[0], s->tetrad[1], s->tetrad[2], s->tetrad[3],
+                                  s->termination_buffer, f.grid_width(), f.grid_height(), 0, s->tetrad[0], s->tetrad[1], s->tetrad[2], s->tetrad[3],
                                   s->cfg, s->dfg, 0, tiled));
-    GR_CHECK(end(GR_STAGE_INIT));
+    GR_CHECK(f.end(GR_STAGE_INIT));
 
-    GR_CHECK(begin(GR_STAGE_TRACE));
-    // Rays in tile slot order are traced the way the fused kernel's tiles are: the device filled once, tiles by ticket, dearest first by
-    // what they cost in this state's frame before while the picture has moved little since (round 5: in slot order, a workgroup to a tile,
-    // the 4K Kerr launch took 6.1 ms against the fused trace's 4.8 - the difference was the tail).  GR_REFERENCE_SCHEDULED=0: the
-    // reference's own launch shape, one work item per record.  The records are the same either way.
-    static const bool scheduled_default = [] { const char* e = getenv("GR_REFERENCE_SCHEDULED"); return !(e && e[0] == '0'); }();
-    if (tiled && scheduled_default) {
-        const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8, tile_count = tiles_x * tiles_y;
-        if (s->ref_cost_tiles != tile_count) {
-            for (void*& b : s->ref_cost) { if (b) (void)hipFree(b); b = nullptr; }
-            if (s->ref_order) (void)hipFree(s->ref_order);
-            if (s->ref_sort_work) (void)hipFree(s->ref_sort_work);
-            s->ref_order = s->ref_sort_work = nullptr;
-            for (void*& b : s->ref_cost) HIP_CHECK(hipMalloc(&b, (size_t)tile_count * sizeof(unsigned int)));
-            HIP_CHECK(hipMalloc(&s->ref_order, (size_t)tile_count * sizeof(unsigned int)));
-            HIP_CHECK(hipMalloc(&s->ref_sort_work, ((size_t)tile_count + 128) * sizeof(unsigned int)));
-            s->ref_cost_tiles = tile_count;
-            s->ref_cost_valid = false;
-        }
-        static const float max_motion = [] { const char* e = getenv("GR_TILE_HISTORY_MAX_MOTION"); return e ? (float)atof(e) : 48.f; }();
-        const bool follow = s->ref_cost_valid && !cfg_jumped && !features_changed && s->ref_cost_program == gr_program_serial(p) && !gc &&
-                            picture_motion(s->ref_cost_camera, *camera, features.field_of_view, width) <= max_motion;
-        std::swap(s->ref_cost[0], s->ref_cost[1]);
-        if (follow) {
-            GR_CHECK(gr_sort_tiles_by_cost(p, stream, s->ref_cost[1], tiles_x, tiles_y, s->ref_order, s->ref_sort_work));
-            s->history_followed++;
-        }
-        s->history_recorded++;
-        GR_CHECK(gr_do_generic_rays_scheduled(p, stream, s->rays_in, s->rays_count_in, tile_count, s->cfg, s->dfg, attempts,
-                                              follow ? s->ref_order : nullptr, s->ref_cost[0]));
-        s->ref_cost_valid = true;
-        s->ref_cost_camera = *camera;
-        s->ref_cost_program = gr_program_serial(p);
-    } else {
+    GR_CHECK(f.begin(GR_STAGE_TRACE));
+    const bool scheduled_default = switches::reference_scheduled();
+    if (tiled && scheduled_default)
+        GR_CHECK(reference_trace_scheduled(f));
+    else
         GR_CHECK(gr_do_generic_rays(p, stream, s->rays_in, s->rays_count_in, (int)slots, nullptr, nullptr, s->cfg, s->dfg, width,
-                                    height, 0, 0, nullptr, nullptr, 0, attempts));
-    }
-    GR_CHECK(end(GR_STAGE_TRACE));
+                                    height, 0, 0, nullptr, nullptr, 0, f.attempts));
+    GR_CHECK(f.end(GR_STAGE_TRACE));
 
     HIP_CHECK(hipMemsetAsync(s->render_data_count, 0, 4, stream));
-    GR_CHECK(begin(GR_STAGE_RENDER_DATA));
+    GR_CHECK(f.begin(GR_STAGE_RENDER_DATA));
     GR_CHECK(gr_calculate_render_data(p, stream, s->rays_in, s->rays_count_in, (int)slots, s->render_data, s->render_data_count,
                                       width, height, s->cfg, s->dfg));
-    GR_CHECK(end(GR_STAGE_RENDER_DATA));
+    GR_CHECK(f.end(GR_STAGE_RENDER_DATA));
 
-    if (adaptive) {
-        GR_CHECK(begin(GR_STAGE_ADAPTIVE));
+    if (f.adaptive) {
+        GR_CHECK(f.begin(GR_STAGE_ADAPTIVE));
         HIP_CHECK(hipMemsetAsync(s->rays_adaptive_count, 0, 4, stream));
         GR_CHECK(gr_handle_adaptive_sampling(p, stream, s->rays_in, s->rays_count_in, s->render_data, s->render_data_count,
                                              s->rays_adaptive, s->rays_adaptive_count, s->camera_pos_generic, s->camera_quat,
                                              s->tetrad[0], s->tetrad[1], s->tetrad[2], s->tetrad[3], width, height, s->cfg,
                                              s->dfg));
         GR_CHECK(gr_do_generic_rays(p, stream, s->rays_adaptive, s->rays_adaptive_count, width * height, nullptr, nullptr, s->cfg,
-                                    s->dfg, width, height, 0, 0, nullptr, nullptr, 0, attempts));
+                                    s->dfg, width, height, 0, 0, nullptr, nullptr, 0, f.attempts));
         GR_CHECK(gr_calculate_render_data(p, stream, s->rays_adaptive, s->rays_adaptive_count, width * height, s->render_data,
                                           s->render_data_count, width, height, s->cfg, s->dfg));
-        GR_CHECK(end(GR_STAGE_ADAPTIVE));
+        GR_CHECK(f.end(GR_STAGE_ADAPTIVE));
     }
 
-    if (out) {
-        GR_CHECK(begin(GR_STAGE_RENDER));
-        GR_CHECK(gr_render(p, stream, s->render_data, s->render_data_count, width * height, out, bg1, bg2, bg_width, bg_height,
-                           bg_levels, width, height, opt.max_probes, s->cfg, s->dfg));
-        GR_CHECK(end(GR_STAGE_RENDER));
+    if (f.out) {
+        GR_CHECK(f.begin(GR_STAGE_RENDER));
+        GR_CHECK(gr_render(p, stream, s->render_data, s->render_data_count, width * height, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height,
+                           f.bg_levels, width, height, f.opt.max_probes, s->cfg, s->dfg));
+        GR_CHECK(f.end(GR_STAGE_RENDER));
+    }
+    return GR_OK;
+}
+
+// one frame at the state's traced size: out is float4[s->width * s->height] (gr_render_frame below for a state of factor 1, and what a
+// supersampled state shades into its own traced frame)
+static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream_v, const gr_camera* camera,
+                               const gr_features* features_in, const float* cfg_values, int num_cfg_values, const void* bg1,
+                               const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* opt_in) {
+    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out));
+    HIP_CHECK(hipSetDevice(s->device));
+    frame_context f{s, p, (hipStream_t)stream_v, camera, bg1, bg2, bg_width, bg_height, bg_levels, out};
+    GR_CHECK(resolve_inputs(f, m, features_in, cfg_values, num_cfg_values, opt_in));
+    note_parameter_changes(f);
+    GR_CHECK(apply_prepass_policy(f));
+    GR_CHECK(upload_parameters(f));
+    GR_CHECK(take_prepared_setup(f));
+    GR_CHECK(begin_frame(f));
+    return f.opt.mode == GR_MODE_FUSED ? render_fused(f) : render_reference_shaped(f);
+}
+
+// What the three entry points below deliver: the frame as render_traced_frame renders it, at the traced size, into the state's own traced
+// frame (at factor 1 too: the encoders read float4 and the caller has only bytes), and ONE launch from there into the caller's memory -
+// the box average as float4 (gr_resolve_supersampled), or resolve and encode in one pass as 8-bit sRGB (gr_present_rgba8) or as BT.709
+// Y'CbCr 4:2:0 planes (gr_present_yuv420; whole frames only).  A device's share of a split frame is traced in blocks of factor x as many
+// rows, so that they cover the rows its output blocks average.  `name`: the entry point's, for its refusals.
+enum delivery { DELIVER_FLOAT4, DELIVER_RGBA8, DELIVER_YUV420 };
+static int deliver_frame(delivery what, int layout, const char* name, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream,
+                         const gr_camera* camera, const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1,
+                         const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* options) {
+    gr_frame_options opt;
+    gr_frame_options_default(&opt);
+    if (options) opt = *options;
+    const int factor = s->supersample, block_rows = opt.block_rows;
+    if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": block_rows").c_str());
+    opt.block_rows *= factor;
+    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out));
+    if (!s->traced_frame) {   // a factor-1 state's first encoded frame (nothing is allocated for a call that is refused)
+        HIP_CHECK(hipSetDevice(s->device));
+        HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
+        for (auto& ev : s->ev_resolve)
+            if (!ev) HIP_CHECK(hipEventCreate(&ev));
+    }
+    GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
+                                 s->traced_frame, &opt));
+    const bool strips = opt.mode == GR_MODE_FUSED && opt.strip_count > 1;   // (as the fused path reads them; the reference-shaped sequence renders whole frames)
+    const int rows = strips ? block_rows : s->out_height, rank = strips ? opt.strip_rank : 0, count = strips ? opt.strip_count : 1,
+              compact_out = strips ? opt.compact_out : 0;
+    const bool timed = opt.time_kernels == 1;
+    if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
+    if (what == DELIVER_FLOAT4)
+        GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, rows, rank, count, compact_out));
+    else if (what == DELIVER_RGBA8)
+        GR_CHECK(gr_present_rgba8(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, rows, rank, count, compact_out));
+    else
+        GR_CHECK(gr_present_yuv420(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, layout));
+    if (timed) {
+        HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
+        s->resolve_timed = true;
     }
     return GR_OK;
 }
@@ -1576,67 +1595,21 @@ int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void*
     // (out == NULL stops after the records: nothing was shaded, nothing to resolve)
     if (!s || s->supersample == 1 || !out)
         return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out, options);
-    // A supersampled state: the frame as ever, at the traced size, into the state's own traced frame - a device's share of a split frame
-    // in blocks of factor x as many traced rows, so that they cover the rows its output blocks average - and from there into the
-    // caller's frame, laid out as the caller asked.
-    gr_frame_options opt;
-    gr_frame_options_default(&opt);
-    if (options) opt = *options;
-    const int factor = s->supersample, block_rows = opt.block_rows;
-    if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame: block_rows");
-    opt.block_rows *= factor;
-    GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
-                                 s->traced_frame, &opt));
-    const bool strips = opt.mode == GR_MODE_FUSED && opt.strip_count > 1;   // (as the fused path reads them; the reference-shaped sequence renders whole frames)
-    const bool timed = opt.time_kernels == 1;
-    if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
-    GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, strips ? block_rows : s->out_height,
-                                     strips ? opt.strip_rank : 0, strips ? opt.strip_count : 1, strips ? opt.compact_out : 0));
-    if (timed) {
-        HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
-        s->resolve_timed = true;
-    }
-    return GR_OK;
+    return deliver_frame(DELIVER_FLOAT4, 0, "gr_render_frame", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width,
+                         bg_height, bg_levels, out, options);
 }
 
-// The frame as gr_render_frame renders it, at the traced size, into the state's own traced frame (at factor 1 too: the encode reads
-// float4 and the caller has only bytes), and one gr_present_rgba8 launch from there into the caller's out_rgba8 - resolve and encode in
-// one pass, no w x h float4 in between.
 int gr_render_frame_rgba8(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
                           const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height,
                           int bg_levels, void* out_rgba8, const gr_frame_options* options) {
     if (!s || !out_rgba8) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_rgba8: null argument");
     s->resolve_timed = false;
-    gr_frame_options opt;
-    gr_frame_options_default(&opt);
-    if (options) opt = *options;
-    const int factor = s->supersample, block_rows = opt.block_rows;
-    if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_rgba8: block_rows");
-    opt.block_rows *= factor;
-    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out_rgba8));
-    if (!s->traced_frame) {   // a factor-1 state's first 8-bit frame (nothing is allocated for a call that is refused)
-        HIP_CHECK(hipSetDevice(s->device));
-        HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
-        for (auto& ev : s->ev_resolve)
-            if (!ev) HIP_CHECK(hipEventCreate(&ev));
-    }
-    GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
-                                 s->traced_frame, &opt));
-    const bool strips = opt.mode == GR_MODE_FUSED && opt.strip_count > 1;
-    const bool timed = opt.time_kernels == 1;
-    if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
-    GR_CHECK(gr_present_rgba8(p, stream, s->traced_frame, out_rgba8, s->out_width, s->out_height, factor, strips ? block_rows : s->out_height,
-                              strips ? opt.strip_rank : 0, strips ? opt.strip_count : 1, strips ? opt.compact_out : 0));
-    if (timed) {
-        HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
-        s->resolve_timed = true;
-    }
-    return GR_OK;
+    return deliver_frame(DELIVER_RGBA8, 0, "gr_render_frame_rgba8", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width,
+                         bg_height, bg_levels, out_rgba8, options);
 }
 
-// gr_render_frame_rgba8 with gr_present_yuv420 as the one launch after the frame: the state's traced frame -> BT.709 Y'CbCr 4:2:0 planes
-// in the caller's memory.  Whole frames only.  Everything the launch itself would refuse is refused here, before the frame is rendered
-// (and before a factor-1 state allocates its traced frame).
+// Everything the gr_present_yuv420 launch itself would refuse is refused here, before the frame is rendered (and before a factor-1 state
+// allocates its traced frame).
 int gr_render_frame_yuv420(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
                            const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height,
                            int bg_levels, void* out_yuv420, int layout, const gr_frame_options* options) {
@@ -1644,33 +1617,12 @@ int gr_render_frame_yuv420(gr_render_state* s, gr_program* p, const gr_metric* m
     if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: layout (GR_YUV420_I420 or GR_YUV420_NV12)");
     if ((uintptr_t)out_yuv420 % 4) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: out_yuv420 must be aligned to 4 bytes");
-    gr_frame_options opt;
-    gr_frame_options_default(&opt);
-    if (options) opt = *options;
-    if (opt.strip_count > 1)
+    if (options && options->strip_count > 1)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: whole frames only (strip_count > 1); a split frame travels as float4 or "
                                                            "RGBA8: gr_render_frame_tiled_as");
     s->resolve_timed = false;
-    const int factor = s->supersample;
-    if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: block_rows");
-    opt.block_rows *= factor;
-    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out_yuv420));
-    if (!s->traced_frame) {   // a factor-1 state's first encoded frame (nothing is allocated for a call that is refused)
-        HIP_CHECK(hipSetDevice(s->device));
-        HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
-        for (auto& ev : s->ev_resolve)
-            if (!ev) HIP_CHECK(hipEventCreate(&ev));
-    }
-    GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
-                                 s->traced_frame, &opt));
-    const bool timed = opt.time_kernels == 1;
-    if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
-    GR_CHECK(gr_present_yuv420(p, stream, s->traced_frame, out_yuv420, s->out_width, s->out_height, factor, layout));
-    if (timed) {
-        HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
-        s->resolve_timed = true;
-    }
-    return GR_OK;
+    return deliver_frame(DELIVER_YUV420, layout, "gr_render_frame_yuv420", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2,
+                         bg_width, bg_height, bg_levels, out_yuv420, options);
 }
 
 }  // extern "C"

@@ -161,6 +161,23 @@ class Program:
             self.handle = None
 
 
+def _frame_arguments(metric, features, cfg_values, background=None):
+    """what a frame or a snapshot hands the library for `features`, `cfg_values` and `background` ((device_ptr, width, height, levels) or
+    ((ptr1, ptr2), width, height, levels)) -> (features, cfg array or None, its length, sky 1, sky 2, width, height, levels)"""
+    arr, n = None, 0
+    if cfg_values is not None:
+        n = len(cfg_values)
+        arr = (c_float * n)(*cfg_values)
+    bg1 = bg2 = None
+    bw = bh = bl = 0
+    if background is not None:
+        ptrs, bw, bh, bl = background
+        bg1, bg2 = ptrs if isinstance(ptrs, tuple) else (ptrs, ptrs)
+    if features is None:
+        features = metric.features()
+    return features, arr, n, bg1, bg2, bw, bh, bl
+
+
 class TiledFrame:
     """One participant of a frame split over several GPUs through the C ABI (gr_tiled_*, csrc/tiled.cpp): renders this
     participant's share of the rows and ships the finished float4 blocks straight to their place in participant 0's frame.
@@ -213,17 +230,7 @@ class TiledFrame:
         self._render(FRAME_RGBA8 if rgba8 else FRAME_F32, state, program, metric, camera, frame_ptr, background, features, cfg_values, options, stream, rotation)
 
     def _render(self, frame_format, state, program, metric, camera, frame_ptr, background, features, cfg_values, options, stream, rotation):
-        arr, n = None, 0
-        if cfg_values is not None:
-            n = len(cfg_values)
-            arr = (c_float * n)(*cfg_values)
-        bg1 = bg2 = None
-        bw = bh = bl = 0
-        if background is not None:
-            ptrs, bw, bh, bl = background
-            bg1, bg2 = ptrs if isinstance(ptrs, tuple) else (ptrs, ptrs)
-        if features is None:
-            features = metric.features()
+        features, arr, n, bg1, bg2, bw, bh, bl = _frame_arguments(metric, features, cfg_values, background)
         args = (self.handle, state.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n, bg1, bg2, bw, bh, bl,
                 frame_ptr, ctypes.byref(options) if options is not None else None, rotation)
         check(lib.gr_render_frame_tiled(*args) if frame_format is None else lib.gr_render_frame_tiled_as(*args, frame_format))
@@ -400,17 +407,7 @@ class RenderState:
                yuv420=None):
         """Enqueue one frame. `out_ptr`: device pointer to float4[width*height] (or None to stop after render-data);
         `background`: (device_ptr, width, height, levels) or ((ptr1, ptr2), width, height, levels).  yuv420 = a layout: render_yuv420."""
-        arr, n = None, 0
-        if cfg_values is not None:
-            n = len(cfg_values)
-            arr = (c_float * n)(*cfg_values)
-        bg1 = bg2 = None
-        bw = bh = bl = 0
-        if background is not None:
-            ptrs, bw, bh, bl = background
-            bg1, bg2 = ptrs if isinstance(ptrs, tuple) else (ptrs, ptrs)
-        if features is None:
-            features = metric.features()
+        features, arr, n, bg1, bg2, bw, bh, bl = _frame_arguments(metric, features, cfg_values, background)
         options = ctypes.byref(options) if options is not None else None
         if yuv420 is not None:
             check(lib.gr_render_frame_yuv420(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n,
@@ -515,12 +512,7 @@ class GeodesicCamera:
             self.handle = None
 
     def snapshot(self, program, metric, camera, geodesic_basis_speed, features=None, cfg_values=None, stream=None):
-        arr, n = None, 0
-        if cfg_values is not None:
-            n = len(cfg_values)
-            arr = (c_float * n)(*cfg_values)
-        if features is None:
-            features = metric.features()
+        features, arr, n = _frame_arguments(metric, features, cfg_values)[:3]
         steps, tau = ctypes.c_int(), c_float()
         check(lib.gr_geodesic_camera_snapshot(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera),
                                               (c_float * 3)(*geodesic_basis_speed), ctypes.byref(features), arr, n,
