@@ -9,7 +9,6 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
 #include <hip/hiprtc.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <chrono>
@@ -20,12 +19,10 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <map>
 #include <memory>
 #include <condition_variable>
 #include <mutex>
-#include <sstream>
 #include <string>
 #include <system_error>
 #include <thread>
@@ -35,6 +32,7 @@
 #include "codeobject.hpp"
 #include "jsfront.hpp"
 #include "metric_codegen.hpp"
+#include "program_build.hpp"
 
 namespace {
 
@@ -72,27 +70,6 @@ std::string library_dir() {
     return ".";
 }
 
-bool read_file(const std::string& path, std::string& out) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return false;
-    std::stringstream ss;
-    ss << f.rdbuf();
-    out = ss.str();
-    return true;
-}
-
-uint64_t fnv1a(const std::string& s, uint64_t h = 1469598103934665603ull) {
-    for (unsigned char c : s) {
-        h ^= c;
-        h *= 1099511628211ull;
-    }
-    return h;
-}
-
-#ifndef GR_DEFAULT_VECTOR_RUN_LIMIT
-#define GR_DEFAULT_VECTOR_RUN_LIMIT 8
-#endif
-
 const char* const KERNEL_NAMES[] = {
     "gr_cart_to_generic", "gr_init_basis_vectors", "gr_clear_termination_buffer", "gr_init_rays_generic",
     "gr_do_generic_rays", "gr_calculate_singularities", "gr_calculate_render_data",
@@ -114,153 +91,9 @@ bool is_setup_kernel(int k) {
            k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420;
 }
 
-std::vector<std::string> split_arguments(const std::string& s) {
-    std::vector<std::string> out;
-    std::istringstream iss(s);
-    std::string tok;
-    while (iss >> tok) out.push_back(tok);
-    return out;
-}
-
-// gr_trace_pair (two rays per lane, packed fp32) is built when
-//  * the expressions evaluated inside the Verlet loop can be instantiated on pairs of floats - no `?:` (the comparison /
-//    select forms of CMath.lt, CMath.select, csqrt) - and are small enough that two rays' temporaries fit the register
-//    file (the complex-valued double-Kerr family already needs 170-260 VGPRs for one ray), and
-//  * the program steps with the fixed heuristic step (no ADAPTIVE_PRECISION).  Measured on MI355X, 4K frames, substituted
-//    programs: Schwarzschild 1.96 -> 1.38 ms, Minkowski 1.80 -> 1.16, wormhole 1.83 -> 1.42; with the adaptive controller
-//    Kerr 7.9 -> 9.3 ms, Alcubierre 3.0 -> 3.3: the controller (sqrt, rsq, clamps, compares, the per-ray commit) has no
-//    packed form, costs twice per lane what it costs the one-ray kernel per lane, and at 133 instead of 92 VGPRs only three
-//    waves per SIMD are left to hide its serial tail - that outweighs what the packed multiplies save (EXPERIMENTS.md C.2).
-// GR_TRACE_PAIR_BUILD=0 never builds it, =1 builds it for adaptive programs too (it is correct there, only slower).
-bool pair_kernel_applies(const std::vector<std::string>& opts) {
-    int mode = -1;
-    if (const char* e = getenv("GR_TRACE_PAIR_BUILD")) mode = e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;
-    if (mode == 0) return false;
-    static const char* const LOOP_MACROS[] = {"-DGEO_ACCEL", "-DTEMPORARIES0=", "-DTO_COORD", "-DDISTANCE_FUNC="};
-    size_t total = 0;
-    for (auto& o : opts) {
-        if (mode != 1 && o == "-DADAPTIVE_PRECISION") return false;
-        for (const char* m : LOOP_MACROS)
-            if (o.rfind(m, 0) == 0) {
-                if (o.find('?') != std::string::npos) return false;
-                total += o.size();
-            }
-    }
-    return total > 0 && total < 16384;
-}
-
-// Do the expressions the Verlet loop evaluates call the range-limited sin / cos (kernels/metric.hip GR_ACCEL_TRIG: the bare polynomials,
-// which answer an argument of 8 192 or more with a NaN so that the ray leaves the fast loop for the one that calls libm)?  A program whose
-// accelerations hold none - every Cartesian chart: Kerr-Schild, Alcubierre, Krasnikov ... - can never see such a NaN: its loop then treats
-// a non-finite rejected attempt the reference's way (retried with the smaller step in the same loop: -DGR_ACCEL_WITHOUT_TRIG,
-// integrator.hip) instead of leaving for the slow loop at the first overshoot into a singularity.
-bool accelerations_without_trig(const std::vector<std::string>& opts) {
-    static const char* const CALLS[] = {"sin(", "cos(", "gr_sin2(", "gr_cos2(", "gr_sincos("};
-    bool any = false;
-    for (auto& o : opts) {
-        const size_t eq = o.find('=');
-        if (o.rfind("-D", 0) != 0 || eq == std::string::npos) continue;
-        const std::string name = o.substr(2, eq - 2);
-        if (name.find("ACCEL") == std::string::npos && name.find("TEMPORARIES") == std::string::npos) continue;
-        any = true;
-        for (const char* call : CALLS)
-            for (size_t at = o.find(call, eq); at != std::string::npos; at = o.find(call, at + 1)) {
-                const char before = o[at - 1];
-                if (!(isalnum((unsigned char)before) || before == '_')) return false;   // ("asin(", "gm_cos(" ... are other functions)
-            }
-    }
-    return any;
-}
-
-// May a wave whose live rays are all inside the precision radius skip the outer boundary test (-DGR_RADIUS_EXITS_ORDERED, kernels/integrator.hip)?
-// Only when both hold for the program as it is built:
-//   * the distance the precision radius is compared with IS the polar radius the boundary tests compare, one float: DISTANCE_FUNC is the
-//     variable v2 itself and, where the generator's composed form stands in for it (GR_DISTANCE_OF_GENERIC), that and TO_COORD2 are both
-//     the bare variable v2 - the chart's own radius (Boyer-Lindquist, Schwarzschild ...), so nothing rests on the compiler evaluating two
-//     copies of one expression to the same bits.  Decided on the expressions, never by sampling.  Macro strings are compared: a string
-//     that writes the same thing another way, or does not say it, merely loses the shortcut.  Two holes' distance is not the chart radius;
-//   * SINGULAR_TERMINATOR < max_precision_radius < universe_size, as the floats the kernel compares with - which a substituted program
-//     (-DKERNEL_IS_STATIC, -DFEATURE_*) knows and a program whose features arrive at run time does not.
-// Then "inside the radius" excludes "at the outer boundary".  (The lower bound is the issue's condition for the pair of shortcuts; the
-// terminator-side one - no terminator test in a wave with nobody inside - is not built, the kernel tests the terminator in every wave, so
-// here the lower bound only withholds the shortcut.)  Anything else: the outer boundary is tested in every wave.
-bool radius_exits_ordered(const std::vector<std::string>& opts) {
-    bool is_static = false, singular = false;
-    std::string radius, universe, terminator, distance, composed, polar_radius;
-    for (auto& o : opts) {
-        if (o == "-DKERNEL_IS_STATIC") is_static = true;
-        else if (o.rfind("-DDISTANCE_FUNC=", 0) == 0) distance = o.substr(o.find('=') + 1);
-        else if (o.rfind("-DGR_DISTANCE_OF_GENERIC=", 0) == 0) composed = o.substr(o.find('=') + 1);
-        else if (o.rfind("-DTO_COORD2=", 0) == 0) polar_radius = o.substr(o.find('=') + 1);
-        else if (o == "-DSINGULAR") singular = true;
-        else if (o.rfind("-DFEATURE_max_precision_radius=", 0) == 0) radius = o.substr(o.find('=') + 1);
-        else if (o.rfind("-DFEATURE_universe_size=", 0) == 0) universe = o.substr(o.find('=') + 1);
-        else if (o.rfind("-DSINGULAR_TERMINATOR=", 0) == 0) terminator = o.substr(o.find('=') + 1);
-    }
-    // a float literal as the generator writes it (float_literal: "10.0f"); anything else - an expression, a hex float - is not understood
-    auto literal = [](const std::string& text, float& value) {
-        if (text.empty()) return false;
-        char* end = nullptr;
-        value = strtof(text.c_str(), &end);
-        if (end == text.c_str()) return false;
-        if (*end == 'f' || *end == 'F') end++;
-        return *end == '\0' && std::isfinite(value);
-    };
-    const bool distance_is_radius = distance == "v2" && !polar_radius.empty() && (composed.empty() || (composed == "v2" && polar_radius == "v2"));
-    float r = 0, u = 0, t = 0;
-    if (!is_static || !distance_is_radius || !literal(radius, r) || !literal(universe, u)) return false;
-    if (singular && !literal(terminator, t)) return false;
-    return (!singular || t < r) && r < u;
-}
-
-// VGPRs and scratch bytes per lane of one kernel, read from the code object's metadata note (msgpack: the kernel's map holds
-// ".name", later ".private_segment_fixed_size" and ".vgpr_count" - keys are sorted).  false when the note is not understood.
-bool kernel_resources(const std::string& code, const char* kernel, int& vgprs, int& scratch_bytes, int* sgprs = nullptr) {
-    auto msgpack_uint = [&](size_t at, long& value) -> bool {
-        if (at >= code.size()) return false;
-        const unsigned char c = (unsigned char)code[at];
-        if (c < 0x80) { value = c; return true; }
-        if (c == 0xcc && at + 1 < code.size()) { value = (unsigned char)code[at + 1]; return true; }
-        if (c == 0xcd && at + 2 < code.size()) { value = ((unsigned char)code[at + 1] << 8) | (unsigned char)code[at + 2]; return true; }
-        if (c == 0xce && at + 4 < code.size()) {
-            value = ((long)(unsigned char)code[at + 1] << 24) | ((unsigned char)code[at + 2] << 16) | ((unsigned char)code[at + 3] << 8) | (unsigned char)code[at + 4];
-            return true;
-        }
-        return false;
-    };
-    const std::string name_key = std::string(".name") + (char)(0xa0 + strlen(kernel)) + kernel;   // fixstr key, fixstr value (< 32 chars)
-    if (strlen(kernel) >= 32) return false;
-    size_t at = code.find(name_key);
-    if (at == std::string::npos) return false;
-    const std::string scratch_key = ".private_segment_fixed_size", vgpr_key = ".vgpr_count";
-    size_t s = code.find(scratch_key, at), v = code.find(vgpr_key, at);
-    if (s == std::string::npos || v == std::string::npos) return false;
-    long sv = 0, vv = 0;
-    if (!msgpack_uint(s + scratch_key.size(), sv) || !msgpack_uint(v + vgpr_key.size(), vv)) return false;
-    vgprs = (int)vv;
-    scratch_bytes = (int)sv;
-    if (sgprs) {
-        const std::string sgpr_key = ".sgpr_count";
-        const size_t g = code.find(sgpr_key, at);
-        long gv = 0;
-        *sgprs = (g != std::string::npos && g < v && msgpack_uint(g + sgpr_key.size(), gv)) ? (int)gv : 0;
-    }
-    return vgprs > 0 && vgprs <= 512;
-}
-
-// Waves per SIMD a kernel of 256-thread workgroups is resident with on gfx950, by registers.  Vector registers: 512 per lane in
-// granules of 8.  Scalar registers: 800 per SIMD, a wave takes its count + 6 (VCC, flat scratch, XNACK) rounded up to 16, plus 16 -
-// measured with a timeline of tile begin / end stamps (tools/timeline_probe.py): the Kerr kernel at 72 VGPRs and 94 SGPRs holds 6
-// waves per SIMD, not the 7 its vector registers allow; capped to 90 or 78 SGPRs it holds 7; at 64 VGPRs and <= 74 SGPRs 8.
-int resident_waves_per_simd(int vgprs, int sgprs) {
-    int by_vgprs = 512 / (((vgprs + 7) / 8) * 8);
-    int by_sgprs = sgprs > 0 ? 800 / ((((sgprs + 6) + 15) / 16) * 16 + 16) : 8;
-    int w = by_vgprs < by_sgprs ? by_vgprs : by_sgprs;
-    return w > 8 ? 8 : w;
-}
-
-// Compiles (or fetches from the on-disk cache) the code object for one macro string.
-int compile_setup_module(const std::string& argument_string, std::string& code, bool cache_only = false);
+namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files
+using pb::PART_FRAME;
+using pb::PART_REST;
 
 // hiprtc's version (part of every cache key), asked once per process: the first call into hiprtc initialises the HIP runtime behind it,
 // and two threads doing that at the same moment (the two builds of build_frame_path) left one of them without a device on the GPU box
@@ -297,241 +130,69 @@ int build_through_hiprtc(const std::string& source, const char* name, const std:
     return GR_OK;
 }
 
-// A program's ray kernels are two code objects (kernels/program.hip): PART_FRAME - what a fused frame launches - and PART_REST, the
-// reference-shaped sequence and ray compaction.  cache_only: an empty `code` and GR_OK when the part is not in the cache (the caller
-// builds it later, or on another thread).
-enum BuildPart { PART_FRAME = 0, PART_REST = 1 };
-int compile_code_object(const std::string& argument_string, std::string& code, std::string* key_out = nullptr, BuildPart part = PART_FRAME,
+// One build of the ray kernels' source with `options`: through the assembly pass when it is on and the code-object manager is
+// there, else through hiprtc (a source error shows up there with its diagnostics).  pass_not_applied is set where the build goes out
+// as compiled although the pass is on.
+int build_ray_kernels(const std::string& source, const std::vector<std::string>& options, int run_limit, std::string& out, bool& pass_not_applied) {
+    const bool verbose = pb::switches::verbose_build();
+    // (GR_VECTOR_RUN_LIMIT=0 goes the same way without the pass: which code-object manager hiprtc would find depends on
+    // what else the process has loaded, and the copy bundled with PyTorch aborts on these kernels)
+    std::string assembly, log;
+    if (gr::compile_to_assembly(source, options, assembly, log)) {
+        if (run_limit <= 0 && gr::assemble_code_object(assembly, out, log)) return GR_OK;
+        // the kernels that hold a Verlet loop; the others (set-up, shading, tile order ...) are left as compiled
+        static const std::vector<std::string> integrators = {"gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused",
+                                                             "gr_do_generic_rays", "gr_do_generic_rays_scheduled", "gr_trace_fused_parking"};
+        std::string patched = assembly;
+        const gr::vector_run_stats st = gr::break_vector_runs(patched, run_limit, integrators);
+        if (gr::assemble_code_object(patched, out, log)) {
+            if (verbose)
+                fprintf(stderr, "[gr] vector runs: %d longer than %d (longest %d) cut by %d s_nop, longest now %d\n", st.runs_broken,
+                        run_limit, st.longest_before, st.inserted, st.longest_after);
+            return GR_OK;
+        }
+        // The compiler sized its branches for the code it emitted; in a very large function the added instructions can push
+        // one past the 16-bit branch offset ("branch size exceeds simm16").  Then the code as compiled.
+        if (verbose) fprintf(stderr, "[gr] assembly pass not applied (%s)\n", log.c_str());
+        pass_not_applied = true;
+        if (gr::assemble_code_object(assembly, out, log)) return GR_OK;
+    }
+    if (run_limit > 0) pass_not_applied = true;
+    if (verbose) fprintf(stderr, "[gr] building through hiprtc (%s)\n", log.c_str());
+    return build_through_hiprtc(source, "geodesic_kernels_all_parts.hip", options, out);
+}
+
+// Compiles (or fetches from the on-disk cache) one code object of the ray kernels for one macro string (program_build.hpp: the two
+// parts).  cache_only: an empty `code` and GR_OK when the part is not in the cache (the caller builds it later, or on another thread).
+int compile_code_object(const std::string& argument_string, std::string& code, std::string* key_out = nullptr, pb::build_part part = PART_FRAME,
                         bool cache_only = false) {
-    // the kernel source: the parts under csrc/kernels/ in this order, as one translation unit (GR_KERNEL_SOURCE: one file instead)
-    static const char* const KERNEL_PARTS[] = {"program.hip",       // structs of the boundary, build switches
-                                               "probes.inc",        // measurement hooks (all off by default)
-                                               "metric.hip",        // hosts of the generated expressions
-                                               "setup.hip",         // tetrads, ray set-up
-                                               "integrator.hip",    // the Verlet loop, one and two rays per lane
-                                               "trace.hip",         // render-data, the reference-shaped and the fused kernels, prepass, tile order, adaptive sampling
-                                               "shading.hip"};      // texture sampling, gr_render
-    // (camera.hip and geodesic_camera.hip - what runs once per frame on one lane - are the set-up module: compile_setup_module)
     std::string source;
-    if (const char* env = getenv("GR_KERNEL_SOURCE")) {
-        if (!read_file(env, source)) return fail(GR_ERROR_COMPILE, std::string("cannot read kernel source ") + env);
-    } else {
-        for (const char* part : KERNEL_PARTS) {
-            std::string text;
-            const std::string path = library_dir() + "/csrc/kernels/" + part;
-            if (!read_file(path, text)) return fail(GR_ERROR_COMPILE, "cannot read kernel source " + path);
-            source += text;
-            if (!text.empty() && text.back() != '\n') source += '\n';
-        }
-    }
-
-    std::vector<std::string> opts = {
-        "--offload-arch=gfx950", "-O3", "-std=c++17",
-        // the reference builds with -cl-unsafe-math-optimizations (metric_manager.hpp:70): reassociation,
-        // reciprocal division, contraction - but NaN/Inf stay meaningful (IS_DEGENERATE, cl.cl:68)
-        "-ffp-contract=fast", "-fno-math-errno", "-freciprocal-math", "-fassociative-math",
-        "-fno-signed-zeros", "-fno-trapping-math",
-        // OpenCL's default 2.5-ulp fp32 divide/sqrt (the reference does not pass -cl-fp32-correctly-rounded-divide-sqrt):
-        // v_rcp_f32 / v_sqrt_f32 instead of the ~10-instruction correctly rounded sequences
-        "-fno-hip-fp32-correctly-rounded-divide-sqrt",
-        // ... and its "unsafe math": approximate-function semantics for divide/sqrt/libm (a/b = a * v_rcp_f32(b) with no
-        // denormal rescaling) and flushed fp32 denormals.  Measured -18 % on the Kerr Verlet kernel, parity unchanged.
-        "-fapprox-func", "-fgpu-flush-denormals-to-zero",
-        // no SLP vectorisation: packed fp32 (v_pk_mul/fma_f32) is at best ~1.2x the plain rate on gfx950 and needs operand
-        // pairs in adjacent registers - the straight-line metric code paid ~55 v_mov per Verlet step for it.
-        // Measured on the Kerr kernel: 102 -> 80 VGPRs, 12.7 -> 10.1 ms.
-        "-fno-slp-vectorize"};
-    for (auto& tok : split_arguments(argument_string)) {
-        if (tok.rfind("-D", 0) == 0) opts.push_back(tok);
-        else if (tok == "-cl-fp32-correctly-rounded-divide-sqrt") {
-            // OpenCL's own switch for IEEE divide and square root (the reference does not pass it, metric_manager.hpp:70; a caller who
-            // appends it to the argument string gets what it means): the ray kernels without v_rcp_f32 / v_sqrt_f32 arithmetic.
-            // Measured on the frame that shows the difference most (near-extreme double Kerr, tests/golden/soak/): masked pixel RMSE
-            // 1.30e-4 -> 6.4e-5, pixels off 93 -> 9 of 9 216 - the reference's own distance from itself under a one-ulp change of the
-            // camera position; the Verlet loop pays ~10 instructions per division.
-            for (const char* drop : {"-freciprocal-math", "-fapprox-func", "-fno-hip-fp32-correctly-rounded-divide-sqrt"})
-                opts.erase(std::remove(opts.begin(), opts.end(), std::string(drop)), opts.end());
-            opts.push_back("-fhip-fp32-correctly-rounded-divide-sqrt");
-        }
-        else if (tok.rfind("-cl-", 0) == 0 || tok == "-I" || tok == "./") continue;   // OpenCL-only prefix flags
-        else return fail(GR_ERROR_INVALID_ARGUMENT, "unsupported token in argument string: " + tok);
-    }
-    if (pair_kernel_applies(opts)) opts.push_back("-DGR_TWO_RAYS_PER_LANE");
-    if (accelerations_without_trig(opts)) opts.push_back("-DGR_ACCEL_WITHOUT_TRIG");
-    if (radius_exits_ordered(opts)) opts.push_back("-DGR_RADIUS_EXITS_ORDERED");
-    if (const char* extra = getenv("GR_EXTRA_FLAGS"))
-        for (auto& tok : split_arguments(extra)) opts.push_back(tok);
-    opts.push_back(part == PART_FRAME ? "-DGR_BUILD_FRAME_PATH" : "-DGR_BUILD_REST");
-
+    const std::string unreadable = pb::read_source(pb::RAY_KERNELS, library_dir() + "/csrc/kernels", source);
+    if (!unreadable.empty()) return fail(GR_ERROR_COMPILE, unreadable);
+    const pb::option_list made = pb::options(argument_string, pb::RAY_KERNELS, part);
+    if (!made.refusal.empty()) return fail(GR_ERROR_INVALID_ARGUMENT, made.refusal);
+    const std::vector<std::string>& opts = made.options;
     int rtc_major = 0, rtc_minor = 0;
     rtc_version(rtc_major, rtc_minor);
-    uint64_t h = fnv1a(source);
-    for (auto& o : opts) h = fnv1a(o + "\n", h);
-    h = fnv1a("hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor), h);
-    {
-        const char* tuning = getenv("GR_OCCUPANCY_TUNING");   // changes what is built for the same options (see below)
-        if (tuning && tuning[0] == '0') h = fnv1a("no occupancy tuning", h);
-    }
-    // Pass over the compiled code (codeobject.hpp): no more than `run_limit` vector instructions in a row without a scalar one.
-    // GR_VECTOR_RUN_LIMIT=0: no pass (the build still goes through the code-object manager, see below).
-    int run_limit = GR_DEFAULT_VECTOR_RUN_LIMIT;
-    if (const char* e = getenv("GR_VECTOR_RUN_LIMIT")) run_limit = atoi(e);
-    if (run_limit > 0) h = fnv1a("vector runs <= " + std::to_string(run_limit) + " in the integrator kernels, list of round 5", h);   // (the list below is part of what is built)
-    char name[64];
-    snprintf(name, sizeof(name), "%016llx.hsaco", (unsigned long long)h);
-    if (key_out) key_out->assign(name, 16);
+    const int run_limit = pb::switches::vector_run_limit();
+    const bool tuning = pb::switches::occupancy_tuning();
+    const std::string name = pb::code_object_name(source, opts, rtc_major, rtc_minor, run_limit, tuning);
+    if (key_out) key_out->assign(name, 0, 16);
+    const std::string cache_dir = pb::cache_dir(library_dir()), cache_path = cache_dir + "/" + name;
+    if (pb::fetch(cache_path, code) || cache_only) return GR_OK;
 
-    std::string cache_dir;
-    if (const char* env = getenv("GR_CACHE_DIR")) cache_dir = env;
-    else cache_dir = library_dir() + "/_cache";
-    std::string cache_path = cache_dir + "/" + name;
-    if (read_file(cache_path, code) && !code.empty()) return GR_OK;
-    code.clear();
-    if (cache_only) return GR_OK;
-
-    // one build of the kernel source with `options`: through the assembly pass when it is on and the code-object manager is
-    // there, else through hiprtc (a source error shows up there with its diagnostics)
     bool pass_not_applied = false;   // some build of this call went out as compiled although the pass is on
-    auto build = [&](const std::vector<std::string>& options, std::string& out) -> int {
-        {   // (GR_VECTOR_RUN_LIMIT=0 goes the same way without the pass: which code-object manager hiprtc would find depends on
-            // what else the process has loaded, and the copy bundled with PyTorch aborts on these kernels)
-            std::string assembly, log;
-            if (gr::compile_to_assembly(source, options, assembly, log)) {
-                if (run_limit <= 0 && gr::assemble_code_object(assembly, out, log)) return GR_OK;
-                // the kernels that hold a Verlet loop; the others (set-up, shading, tile order ...) are left as compiled
-                static const std::vector<std::string> integrators = {"gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused",
-                                                                     "gr_do_generic_rays", "gr_do_generic_rays_scheduled", "gr_trace_fused_parking"};
-                std::string patched = assembly;
-                const gr::vector_run_stats st = gr::break_vector_runs(patched, run_limit, integrators);
-                if (gr::assemble_code_object(patched, out, log)) {
-                    if (getenv("GR_VERBOSE_BUILD"))
-                        fprintf(stderr, "[gr] vector runs: %d longer than %d (longest %d) cut by %d s_nop, longest now %d\n", st.runs_broken,
-                                run_limit, st.longest_before, st.inserted, st.longest_after);
-                    return GR_OK;
-                }
-                // The compiler sized its branches for the code it emitted; in a very large function the added instructions can push
-                // one past the 16-bit branch offset ("branch size exceeds simm16").  Then the code as compiled.
-                if (getenv("GR_VERBOSE_BUILD")) fprintf(stderr, "[gr] assembly pass not applied (%s)\n", log.c_str());
-                pass_not_applied = true;
-                if (gr::assemble_code_object(assembly, out, log)) return GR_OK;
-            }
-            if (run_limit > 0) pass_not_applied = true;
-            if (getenv("GR_VERBOSE_BUILD")) fprintf(stderr, "[gr] building through hiprtc (%s)\n", log.c_str());
-        }
-        return build_through_hiprtc(source, "geodesic_kernels_all_parts.hip", options, out);
-    };
-    // The occupancy rule below costs up to three more compiler runs.  Its outcome depends on the program's SHAPE - kernel source,
-    // options, the metric's expressions - far more than on the literals a substituted program carries, and a slider move changes only
-    // those: the decision is remembered per shape (the options with every float literal blanked) next to the code objects, and a program
-    // of a known shape is built held to the remembered wave count straight away - one compiler run, the swap of the substituted program
-    // after a parameter change ~20 s -> ~8 s - as long as that build still meets the rule's own conditions.
-    bool tuned_by_caller = false;
-    for (auto& o : opts) tuned_by_caller |= o.rfind("-DGR_FUSED_WAVES", 0) == 0 || o.rfind("-DGR_TRACE_WAVES", 0) == 0;
-    const char* tuning = getenv("GR_OCCUPANCY_TUNING");
-    // (the rule is about gr_trace_fused: the other part is built as the compiler allocates it)
-    const bool rule_applies = part == PART_FRAME && !tuned_by_caller && !(tuning && tuning[0] == '0');
-    std::string shape_path;
-    {
-        uint64_t sh = fnv1a(source);
-        for (auto& o : opts) {
-            // (round 6: the device's own rendering of the accelerations - GR_DEVICE_ACCEL*, GR_DEVICE_TEMPORARIES - shares other
-            // sub-expressions from one parameter set to the next, so its text has another length and another set of temporaries; with it
-            // in the key no two parameter sets of round 5 ever had the same shape and every slider move paid the rule's three builds)
-            if (o.rfind("-DGR_DEVICE_", 0) == 0) continue;
-            std::string blank;
-            for (size_t i = 0; i < o.size();) {
-                const bool starts_number = isdigit((unsigned char)o[i]) && (i == 0 || !(isalnum((unsigned char)o[i - 1]) || o[i - 1] == '_'));
-                if (!starts_number) { blank += o[i++]; continue; }
-                size_t j = i;
-                while (j < o.size() && (isdigit((unsigned char)o[j]) || o[j] == '.' || ((o[j] == 'e' || o[j] == 'E') && j + 1 < o.size() && (isdigit((unsigned char)o[j + 1]) || o[j + 1] == '-' || o[j + 1] == '+')) ||
-                                        ((o[j] == '-' || o[j] == '+') && j > i && (o[j - 1] == 'e' || o[j - 1] == 'E')))) j++;
-                const bool is_float = j < o.size() && o[j] == 'f' && o.substr(i, j - i).find_first_of(".e") != std::string::npos;
-                if (is_float) { blank += '#'; i = j + 1; } else { blank.append(o, i, j - i); i = j; }
-            }
-            // (the generator orders the operands of sums and products by a hash that takes the literals in, and numbers its temporaries as
-            // it meets them: two parameter sets give the same expressions in another order.  What is left after blanking the literals
-            // is therefore taken as a bag of characters, every digit the same - a hint's key may collide, the conditions above decide.)
-            for (char& ch : blank) if (isdigit((unsigned char)ch)) ch = '9';
-            const size_t eq = blank.find('=');
-            if (eq != std::string::npos) std::sort(blank.begin() + (long)eq + 1, blank.end());
-            sh = fnv1a(blank + "\n", sh);
-        }
-        sh = fnv1a("shape, hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) + ", runs " + std::to_string(run_limit), sh);
-        char shape_name[64];
-        snprintf(shape_name, sizeof(shape_name), "%016llx.occupancy", (unsigned long long)sh);
-        shape_path = cache_dir + "/" + shape_name;
-    }
-    bool settled_from_memory = false;
-    if (rule_applies) {
-        std::string note;
-        int waves = 0, free_vgprs = 0, free_scratch = 0;
-        if (read_file(shape_path, note) && sscanf(note.c_str(), "waves=%d free_vgprs=%d free_scratch=%d", &waves, &free_vgprs, &free_scratch) == 3 && waves >= 1 && waves <= 8) {
-            std::vector<std::string> capped = opts;
-            capped.push_back("-DGR_FUSED_WAVES=" + std::to_string(waves));
-            std::string code2;
-            int v2 = 0, s2 = 0, g2 = 0;
-            if (build(capped, code2) == GR_OK && kernel_resources(code2, "gr_trace_fused", v2, s2, &g2) && s2 <= free_scratch + 96 &&
-                resident_waves_per_simd(v2, g2) >= waves) {
-                code.swap(code2);
-                settled_from_memory = true;
-                if (getenv("GR_VERBOSE_BUILD"))
-                    fprintf(stderr, "[gr] gr_trace_fused: held to %d waves as remembered for programs of this shape: %d VGPRs / %d SGPRs / %d B scratch (kept, one compiler run)\n", waves, v2, g2, s2);
-            }
-        }
-    }
-    if (!settled_from_memory) {
-        int rc = build(opts, code);
-        if (rc != GR_OK) return rc;
-    }
-
-    // Occupancy of the fused trace kernel.  Left alone, the register allocator takes what the kernel could use at its widest
-    // point (Kerr, substituted: 97 VGPRs, 5 waves per SIMD), part of which is cold inside the Verlet loop (set-up and epilogue
-    // values).  Measured on MI355X, 4K Kerr, three frames in flight / one launch on its own, with the loop that still kept a
-    // finished ray's state in twelve registers of its own (108 VGPRs free): free build 1 400 Mrays/s / 6.7 ms; held to 96 VGPRs (5
-    // waves, nothing spilled) 1 492 / 6.5; to 80 (6 waves, 60 bytes per lane spilled, none of it inside the loop's attempts)
-    // 1 535 / 6.2; to 72 (7 waves, 84 bytes) 1 530 / 6.2.  With today's loop: 6 waves spill 24 bytes; 7 and 8 waves measure the same.
-    // Rule: rebuild with the register budget of five sixths of what the free build took, rounded down to an occupancy step,
-    // and keep that build unless it spills more than 96 bytes per lane (the same source compiles to a spill that differs by 20 B
-    // from one hiprtc run to the next, and a limit next to the expected number flipped the decision with it) - or unless its waves
-    // would not be resident anyway (round 4): the kernel's ~94 scalar registers admit 6 waves per SIMD, so the "7 waves" build of
-    // rounds 2 and 3 (72 VGPRs, 48 B spilled) ran 6 like the 80-register build that spills 16 B; that one is 3 % faster one frame at
-    // a time (5.46 against 5.65 ms, 4K Kerr) and the same with frames in flight.
-    if (rule_applies && !settled_from_memory) {
-        int vgprs = 0, scratch = 0;
-        if (kernel_resources(code, "gr_trace_fused", vgprs, scratch) && vgprs > 64) {
-            auto waves_of = [](int regs) { int w = 512 / (((regs + 7) / 8) * 8); return w > 8 ? 8 : w; };
-            int target_waves = waves_of(vgprs * 5 / 6);
-            while (target_waves > 1 && (512 / target_waves) / 8 * 8 > vgprs * 5 / 6) target_waves++;   // budget of w waves <= 5/6 of the free build
-            if (target_waves > 8) target_waves = 8;
-            if (target_waves <= waves_of(vgprs) && getenv("GR_VERBOSE_BUILD"))
-                fprintf(stderr, "[gr] gr_trace_fused: free build %d VGPRs / %d B scratch, left alone\n", vgprs, scratch);
-            // from the rule's target down to one wave more than the free build holds: the first budget that does not spill too much
-            // (double Kerr: 172 VGPRs = 2 waves; held to 4 waves it spills 148 B, held to 3 - 168 VGPRs - nothing)
-            for (int waves = target_waves; waves > waves_of(vgprs); waves--) {
-                std::vector<std::string> capped = opts;
-                capped.push_back("-DGR_FUSED_WAVES=" + std::to_string(waves));
-                std::string code2;
-                int v2 = 0, s2 = 0, g2 = 0;
-                const bool built = build(capped, code2) == GR_OK && kernel_resources(code2, "gr_trace_fused", v2, s2, &g2);
-                const bool resident = built && resident_waves_per_simd(v2, g2) >= waves;
-                const bool keep = built && s2 <= scratch + 96 && resident;
-                if (getenv("GR_VERBOSE_BUILD"))
-                    fprintf(stderr, "[gr] gr_trace_fused: free build %d VGPRs / %d B scratch; held to %d waves: %d VGPRs / %d SGPRs / %d B scratch%s\n", vgprs,
-                            scratch, waves, v2, g2, s2, keep ? " (kept)" : resident ? " (dropped)" : " (dropped: its scalar registers admit fewer waves)");
-                if (keep) {
-                    code.swap(code2);
-                    if (!pass_not_applied) {   // remembered for the next program of this shape
-                        mkdir(cache_dir.c_str(), 0755);
-                        std::ofstream f(shape_path + ".tmp" + std::to_string((long)getpid()));
-                        f << "waves=" << waves << " free_vgprs=" << vgprs << " free_scratch=" << scratch << "\n";
-                        f.close();
-                        if (rename((shape_path + ".tmp" + std::to_string((long)getpid())).c_str(), shape_path.c_str()) != 0) remove((shape_path + ".tmp" + std::to_string((long)getpid())).c_str());
-                    }
-                    break;
-                }
-            }
-        }
-    }
+    auto build = [&](const std::vector<std::string>& options, std::string& out) { return build_ray_kernels(source, options, run_limit, out, pass_not_applied); };
+    // free, or held to fewer registers by the occupancy rule - whose decision is remembered per shape of program, next to the code objects
+    const bool rule_applies = pb::occupancy_rule_applies(opts, part, tuning);
+    const std::string shape_path = cache_dir + "/" + pb::shape_name(source, opts, rtc_major, rtc_minor, run_limit);
+    std::string note;
+    const bool remembered = rule_applies && pb::fetch(shape_path, note);
+    const pb::occupancy_outcome built = pb::build_by_occupancy_rule(opts, rule_applies, remembered ? &note : nullptr, build, [&] { return pass_not_applied; }, code);
+    if (pb::switches::verbose_build())
+        for (auto& line : built.lines) fprintf(stderr, "%s\n", line.c_str());
+    if (built.rc != GR_OK) return built.rc;
+    if (!built.note.empty()) pb::publish(shape_path, built.note);
 
     if (pass_not_applied) {
         // The cache key says "vector runs <= N"; this code object does not have them cut (a branch pushed past its 16-bit offset, or
@@ -543,17 +204,7 @@ int compile_code_object(const std::string& argument_string, std::string& code, s
                             "compiled (~20 %% slower Verlet loop) and is not cached.  GR_VERBOSE_BUILD=1 says why.\n", run_limit);
         return GR_OK;
     }
-    mkdir(cache_dir.c_str(), 0755);
-    // unique per writer: a background build (gr_program_create_async) and a foreground build of the same key may run in one
-    // process, and several processes share the cache directory; rename() publishes a complete file atomically
-    static std::atomic<unsigned long> writer{0};
-    std::string tmp = cache_path + ".tmp" + std::to_string((long)getpid()) + "." + std::to_string(writer.fetch_add(1));
-    {
-        std::ofstream f(tmp, std::ios::binary);
-        f.write(code.data(), (std::streamsize)code.size());
-        if (!f) { f.close(); remove(tmp.c_str()); return GR_OK; }   // cache write failed (disk full, read-only): the build still succeeded
-    }
-    if (rename(tmp.c_str(), cache_path.c_str()) != 0) remove(tmp.c_str());
+    pb::publish(cache_path, code);
     return GR_OK;
 }
 
@@ -581,71 +232,34 @@ const std::string& srgb8_tree_source() {
     return text;
 }
 
-int compile_setup_module(const std::string& argument_string, std::string& code, bool cache_only) {
-    static const char* const PARTS[] = {"program.hip", "probes.inc", "metric.hip", "setup.hip", "camera.hip", "geodesic_camera.hip", "resolve.hip",
-                                        "present.hip", "background.hip"};
+int compile_setup_module(const std::string& argument_string, std::string& code, bool cache_only = false) {
     std::string source;
-    // GR_SETUP_KERNEL_SOURCE: one file instead of the parts, as GR_KERNEL_SOURCE is for the ray kernels' module.  (GR_KERNEL_SOURCE
-    // alone replaces the ray kernels only - the tools that use it patch the trace kernel - and this module is then built from the
-    // library's own parts: said once on stderr, so that nobody takes a patched metric.hip to reach the camera kernels.)
-    if (const char* env = getenv("GR_SETUP_KERNEL_SOURCE")) {
-        if (!read_file(env, source)) return fail(GR_ERROR_COMPILE, std::string("cannot read set-up kernel source ") + env);
-    } else {
-        if (getenv("GR_KERNEL_SOURCE")) {
-            static std::atomic<bool> said{false};
-            if (!said.exchange(true))
-                fprintf(stderr, "[gr] note: GR_KERNEL_SOURCE replaces the ray kernels' source only; the set-up module (camera, tetrad, geodesic camera) is built "
-                                "from the library's csrc/kernels - GR_SETUP_KERNEL_SOURCE replaces that\n");
-        }
-        for (const char* part : PARTS) {
-            std::string text;
-            const std::string path = library_dir() + "/csrc/kernels/" + part;
-            if (!read_file(path, text)) return fail(GR_ERROR_COMPILE, "cannot read kernel source " + path);
-            source += text;
-            if (!text.empty() && text.back() != '\n') source += '\n';
-        }
+    const std::string unreadable = pb::read_source(pb::SETUP_MODULE, library_dir() + "/csrc/kernels", source);
+    if (!unreadable.empty()) return fail(GR_ERROR_COMPILE, unreadable);
+    if (!pb::switches::setup_kernel_source() && pb::switches::kernel_source()) {
+        // (so that nobody takes a patched metric.hip to reach the camera kernels)
+        static std::atomic<bool> said{false};
+        if (!said.exchange(true))
+            fprintf(stderr, "[gr] note: GR_KERNEL_SOURCE replaces the ray kernels' source only; the set-up module (camera, tetrad, geodesic camera) is built "
+                            "from the library's csrc/kernels - GR_SETUP_KERNEL_SOURCE replaces that\n");
     }
     source = srgb8_tree_source() + source;
-    std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-math-errno", "-fno-slp-vectorize",
-                                     "-fhip-fp32-correctly-rounded-divide-sqrt", "-DGR_SETUP_MODULE", "-DGR_LIBM_TRIG", "-DGR_LIBM_TANH"};
-    for (auto& tok : split_arguments(argument_string)) {
-        if (tok.rfind("-D", 0) == 0) opts.push_back(tok);
-        else if (tok.rfind("-cl-", 0) == 0 || tok == "-I" || tok == "./") continue;
-        else return fail(GR_ERROR_INVALID_ARGUMENT, "unsupported token in argument string: " + tok);
-    }
-    if (const char* extra = getenv("GR_SETUP_EXTRA_FLAGS"))
-        for (auto& tok : split_arguments(extra)) opts.push_back(tok);
+    const pb::option_list made = pb::options(argument_string, pb::SETUP_MODULE, PART_FRAME);
+    if (!made.refusal.empty()) return fail(GR_ERROR_INVALID_ARGUMENT, made.refusal);
+    const std::vector<std::string>& opts = made.options;
     int rtc_major = 0, rtc_minor = 0;
     rtc_version(rtc_major, rtc_minor);
-    uint64_t h = fnv1a(source);
-    for (auto& o : opts) h = fnv1a(o + "\n", h);
-    h = fnv1a("set-up module, hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor), h);
-    char name[64];
-    snprintf(name, sizeof(name), "%016llx.setup.hsaco", (unsigned long long)h);
-    std::string cache_dir;
-    if (const char* env = getenv("GR_CACHE_DIR")) cache_dir = env;
-    else cache_dir = library_dir() + "/_cache";
-    const std::string cache_path = cache_dir + "/" + name;
-    if (read_file(cache_path, code) && !code.empty()) return GR_OK;
-    code.clear();
-    if (cache_only) return GR_OK;
+    const std::string cache_path = pb::cache_dir(library_dir()) + "/" + pb::setup_module_name(source, opts, rtc_major, rtc_minor);
+    if (pb::fetch(cache_path, code) || cache_only) return GR_OK;
     std::string assembly, log;
     if (!gr::compile_to_assembly(source, opts, assembly, log) || !gr::assemble_code_object(assembly, code, log)) {
         // the code-object manager could not be loaded (or is the copy bundled with another library): hiprtc, as for the ray kernels'
         // module - this module needs no pass over its code, so the result is the same program and is cached like any other
-        if (getenv("GR_VERBOSE_BUILD")) fprintf(stderr, "[gr] set-up module: building through hiprtc (%s)\n", log.c_str());
+        if (pb::switches::verbose_build()) fprintf(stderr, "[gr] set-up module: building through hiprtc (%s)\n", log.c_str());
         const int rc = build_through_hiprtc(source, "geodesic_setup_kernels.hip", opts, code);
         if (rc != GR_OK) return rc;
     }
-    mkdir(cache_dir.c_str(), 0755);
-    static std::atomic<unsigned long> writer{0};
-    const std::string tmp = cache_path + ".tmp" + std::to_string((long)getpid()) + "." + std::to_string(writer.fetch_add(1));
-    {
-        std::ofstream f(tmp, std::ios::binary);
-        f.write(code.data(), (std::streamsize)code.size());
-        if (!f) { f.close(); remove(tmp.c_str()); return GR_OK; }
-    }
-    if (rename(tmp.c_str(), cache_path.c_str()) != 0) remove(tmp.c_str());
+    pb::publish(cache_path, code);
     return GR_OK;
 }
 
@@ -923,18 +537,12 @@ int gr_metric_substituted_op_counts(const gr_metric* m, const float* cfg_values,
 
 int gr_argument_string_accelerations_call_trig(const char* argument_string) {
     if (!argument_string) return -1;
-    std::vector<std::string> opts;
-    for (auto& tok : split_arguments(argument_string))
-        if (tok.rfind("-D", 0) == 0) opts.push_back(tok);
-    return accelerations_without_trig(opts) ? 0 : 1;
+    return pb::accelerations_without_trig(pb::defines_of(argument_string)) ? 0 : 1;
 }
 
 int gr_argument_string_radius_exits_ordered(const char* argument_string) {
     if (!argument_string) return -1;
-    std::vector<std::string> opts;
-    for (auto& tok : split_arguments(argument_string))
-        if (tok.rfind("-D", 0) == 0) opts.push_back(tok);
-    return radius_exits_ordered(opts) ? 1 : 0;
+    return pb::radius_exits_ordered(pb::defines_of(argument_string)) ? 1 : 0;
 }
 
 int gr_program_precompile(const char* argument_string) {
@@ -1045,12 +653,12 @@ int gr_program_create(const char* argument_string, int device, gr_program** out)
         // caller sees (and the committed hardware counters carry) therefore names the outcome too: registers and scratch of the
         // fused trace kernel as loaded.
         int vgprs = 0, scratch = 0;
-        if (kernel_resources(code, "gr_trace_fused", vgprs, scratch)) p->key += "-v" + std::to_string(vgprs) + "s" + std::to_string(scratch);
+        if (pb::kernel_resources(code, "gr_trace_fused", vgprs, scratch)) p->key += "-v" + std::to_string(vgprs) + "s" + std::to_string(scratch);
     }
     p->device = device;
     p->arguments = argument_string;
     {
-        const char* extra = getenv("GR_EXTRA_FLAGS");
+        const char* extra = pb::switches::extra_flags();
         p->tile_shading = p->arguments.find("-DGR_TILE_SHADING") != std::string::npos || (extra && strstr(extra, "-DGR_TILE_SHADING"));
         p->cell_rows = p->arguments.find("-DGR_CELL_BLOCK=0") != std::string::npos || (extra && strstr(extra, "-DGR_CELL_BLOCK=0"));
     }

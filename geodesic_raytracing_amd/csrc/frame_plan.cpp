@@ -11,7 +11,7 @@
 #define GR_DEFAULT_TILE_HISTORY 1
 #endif
 #ifndef GR_DEFAULT_RAYS_PER_LANE
-#define GR_DEFAULT_RAYS_PER_LANE 2   /* where the program has gr_trace_pair (capi.cpp: pair_kernel_applies) */
+#define GR_DEFAULT_RAYS_PER_LANE 2   /* where the program has gr_trace_pair (program_build.cpp: pair_kernel_applies) */
 #endif
 
 namespace frame_plan {

@@ -245,7 +245,7 @@ def test_cpp_example_builds_against_the_header_alone():
 
 
 def test_pair_kernel_is_built_for_fixed_step_programs_only(tmp_path, monkeypatch):
-    """host rule (capi.cpp pair_kernel_applies): gr_trace_pair is compiled into programs that step without the adaptive
+    """host rule (program_build.cpp pair_kernel_applies): gr_trace_pair is compiled into programs that step without the adaptive
     controller and whose loop expressions instantiate on float pairs; adaptive programs get it on request only"""
     import glob
     import os

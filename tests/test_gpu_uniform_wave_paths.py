@@ -1,5 +1,5 @@
 """The one-ray Verlet loop's paths for a wave whose live rays are all inside the precision radius (kernels/integrator.hip,
-GR_UNIFORM_WAVE_PATHS): the step selection, the far step and - where the host says the radii are ordered, capi.cpp
+GR_UNIFORM_WAVE_PATHS): the step selection, the far step and - where the host says the radii are ordered, program_build.cpp
 radius_exits_ordered - the outer boundary test are skipped there.  They are the same values with fewer instructions, so a frame must
 be that of a build with the paths compiled out (-DGR_NO_UNIFORM_WAVE_PATHS) BIT FOR BIT, attempts included.  No tolerance: no value
 may change.  The host-side condition itself is tested without a GPU."""

@@ -393,7 +393,7 @@ def test_an_expression_shared_exponentially_often_is_refused_not_printed(tmp_pat
 
 
 def test_which_programs_are_built_without_the_trigonometric_nan_exit():
-    """-DGR_ACCEL_WITHOUT_TRIG (capi.cpp accelerations_without_trig, kernels/integrator.hip): the Verlet loop's "a NaN leaves the fast loop at
+    """-DGR_ACCEL_WITHOUT_TRIG (program_build.cpp accelerations_without_trig, kernels/integrator.hip): the Verlet loop's "a NaN leaves the fast loop at
     once" exists for the range-limited sin / cos polynomials and is compiled only into programs whose accelerations call them - a Cartesian or
     cylindrical chart's NaN is the metric's own and takes the reference's course in the fast loop (kerr_schild lost 28 % to the other course).
     Decided from the macro strings: which of the shipped scripts fall on which side, dynamic and substituted alike, and what counts as a call."""

@@ -272,11 +272,12 @@ def test_the_launcher_and_the_frame_entry_check_their_arguments_before_any_devic
 
 
 def test_the_kernel_is_part_of_the_setup_modules_source_only():
-    """the two lists of source files the library assembles its two modules from (csrc/capi.cpp): the kernel is in a file of the set-up
-    module's list and in no file of the frame path's"""
+    """the two lists of source files the library assembles its two modules from (csrc/program_build.cpp): the kernel is in a file of the
+    set-up module's list and in no file of the frame path's - and the library looks it up in the set-up module (csrc/capi.cpp)"""
     kernels = os.path.join(os.path.dirname(gra.__file__), "csrc", "kernels")
     capi = open(os.path.join(os.path.dirname(gra.__file__), "csrc", "capi.cpp")).read()
-    lists = {name: re.findall(r'"([a-z_]+\.(?:hip|inc))"', body) for name, body in re.findall(r"const (\w*PARTS)\[\] = \{(.*?)\};", capi, flags=re.S)}
+    program_build = open(os.path.join(os.path.dirname(gra.__file__), "csrc", "program_build.cpp")).read()
+    lists = {name: re.findall(r'"([a-z_]+\.(?:hip|inc))"', body) for name, body in re.findall(r"const (\w*PARTS)\[\] = \{(.*?)\};", program_build, flags=re.S)}
     assert sorted(lists) == ["KERNEL_PARTS", "PARTS"]
     frame_files, setup_files = lists["KERNEL_PARTS"], lists["PARTS"]
     assert "present.hip" in setup_files and "resolve.hip" in setup_files and "present.hip" not in frame_files
