@@ -240,7 +240,9 @@ _SIGNATURES = {
     "gr_resolve_supersampled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "gr_present_rgba8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "gr_present_yuv420": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
+    "gr_present_yuv420p10": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
     "gr_srgb8_thresholds": (c_int, [ctypes.POINTER(c_float)]),
+    "gr_srgb10_thresholds": (c_int, [ctypes.POINTER(c_float)]),
     "gr_mipped_background_scratch_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "gr_build_mipped_background": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t]),
     "gr_render_state_destroy": (None, [c_void_p]),
@@ -253,6 +255,9 @@ _SIGNATURES = {
     "gr_render_frame_yuv420": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
                                        ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
                                        ctypes.POINTER(FrameOptions)]),
+    "gr_render_frame_yuv420p10": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
+                                          ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                          ctypes.POINTER(FrameOptions)]),
     "gr_geodesic_camera_create": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p)]),
     "gr_geodesic_camera_destroy": (None, [c_void_p]),
     "gr_geodesic_camera_snapshot": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(c_float),
@@ -314,6 +319,10 @@ _SIGNATURES = {
     "gr_y4m_open": (c_int, [c_char_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "gr_y4m_write_frame": (c_int, [c_void_p, c_void_p]),
     "gr_y4m_close": (c_int, [c_void_p]),
+    "gr_yuv420p10_bytes": (c_size_t, [c_int, c_int]),
+    "gr_frame_to_rgb10": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "gr_rgb10_to_yuv420p10": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gr_y4m_open_depth": (c_int, [c_char_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():
@@ -336,4 +345,4 @@ def check(rc):
 
 from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, build_background,  # noqa: E402,F401
                        default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background, rgba8_to_yuv420,
-                       yuv420_bytes, Y4MWriter)
+                       yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes)

@@ -75,20 +75,20 @@ const char* const KERNEL_NAMES[] = {
     "gr_do_generic_rays", "gr_calculate_singularities", "gr_calculate_render_data",
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
-    "gr_background_reduce", "gr_background_slices", "gr_present_yuv420"};
+    "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_COUNT
 };
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
-// filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
+// filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and 8- and 10-bit Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
 // (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
-           k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420;
+           k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10;
 }
 
 namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files
@@ -232,6 +232,25 @@ const std::string& srgb8_tree_source() {
     return text;
 }
 
+// The same for gr_present_yuv420p10: gr_srgb10_thresholds' T[1 ... 1023], ten levels
+const std::string& srgb10_tree_source() {
+    static const std::string text = [] {
+        static float sorted[1024];
+        static uint32_t tree[1024] = {};
+        (void)gr_srgb10_thresholds(sorted);
+        for (int level = 0; level < 10; level++)   // entry j of level l is the (2 j + 1) 2^(9 - l)-th threshold in sorted order
+            for (int j = 0; j < (1 << level); j++) memcpy(&tree[(1 << level) + j], &sorted[(2 * j + 1) << (9 - level)], sizeof(uint32_t));
+        std::string t = "__device__ const unsigned int GR_SRGB10_TREE_BITS[1024] = {";
+        char word[32];
+        for (int i = 0; i < 1024; i++) {
+            snprintf(word, sizeof(word), "%s0x%08xu", i ? (i % 8 ? ", " : ",\n    ") : "\n    ", tree[i]);
+            t += word;
+        }
+        return t + "};\n";
+    }();
+    return text;
+}
+
 int compile_setup_module(const std::string& argument_string, std::string& code, bool cache_only = false) {
     std::string source;
     const std::string unreadable = pb::read_source(pb::SETUP_MODULE, library_dir() + "/csrc/kernels", source);
@@ -243,7 +262,7 @@ int compile_setup_module(const std::string& argument_string, std::string& code, 
             fprintf(stderr, "[gr] note: GR_KERNEL_SOURCE replaces the ray kernels' source only; the set-up module (camera, tetrad, geodesic camera) is built "
                             "from the library's csrc/kernels - GR_SETUP_KERNEL_SOURCE replaces that\n");
     }
-    source = srgb8_tree_source() + source;
+    source = srgb8_tree_source() + srgb10_tree_source() + source;
     const pb::option_list made = pb::options(argument_string, pb::SETUP_MODULE, PART_FRAME);
     if (!made.refusal.empty()) return fail(GR_ERROR_INVALID_ARGUMENT, made.refusal);
     const std::vector<std::string>& opts = made.options;
@@ -1145,6 +1164,27 @@ int gr_present_yuv420(gr_program* p, void* stream, const void* src, void* dst, i
     if (gy > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a frame of " + std::to_string(height) + " rows does not fit the grid");
     void* args[] = {&src, &dst, &width, &height, &factor, &layout};
     return launch(p, K_PRESENT_YUV420, stream, gx, gy, 64, 4, args);
+}
+
+// gr_present_yuv420 with ten bits a sample in 16-bit words (kernels/present.hip: gr_present_yuv420p10): the same grid, the same refusals;
+// the fast store path (width % 4 == 0) writes 8 bytes at a time, the other one word at a time
+int gr_present_yuv420p10(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout) {
+    const char* who = "gr_present_yuv420p10";
+    GR_NEED(who, src, dst);
+    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": null program");
+    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": factor " + std::to_string(factor) + " (1 to 4)");
+    if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the frame's size");
+    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": layout " + std::to_string(layout) + " (GR_YUV420_I420 or GR_YUV420_NV12)");
+    const int alignment = width % 4 == 0 ? 8 : 2;
+    if ((uintptr_t)dst % alignment)
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": dst must be aligned to " + std::to_string(alignment) + " bytes at a width of " +
+                                                   std::to_string(width));
+    const unsigned gx = blocks(((long long)width + 3) / 4, 64), gy = blocks(((long long)height + 1) / 2, 4);
+    if (gy > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a frame of " + std::to_string(height) + " rows does not fit the grid");
+    void* args[] = {&src, &dst, &width, &height, &factor, &layout};
+    return launch(p, K_PRESENT_YUV420P10, stream, gx, gy, 64, 4, args);
 }
 
 // ---- the sky's mip slices on the device (kernels/background.hip) ------------------------------------

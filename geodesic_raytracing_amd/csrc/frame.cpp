@@ -1546,12 +1546,13 @@ static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metri
     return f.opt.mode == GR_MODE_FUSED ? render_fused(f) : render_reference_shaped(f);
 }
 
-// What the three entry points below deliver: the frame as render_traced_frame renders it, at the traced size, into the state's own traced
+// What the four entry points below deliver: the frame as render_traced_frame renders it, at the traced size, into the state's own traced
 // frame (at factor 1 too: the encoders read float4 and the caller has only bytes), and ONE launch from there into the caller's memory -
 // the box average as float4 (gr_resolve_supersampled), or resolve and encode in one pass as 8-bit sRGB (gr_present_rgba8) or as BT.709
-// Y'CbCr 4:2:0 planes (gr_present_yuv420; whole frames only).  A device's share of a split frame is traced in blocks of factor x as many
-// rows, so that they cover the rows its output blocks average.  `name`: the entry point's, for its refusals.
-enum delivery { DELIVER_FLOAT4, DELIVER_RGBA8, DELIVER_YUV420 };
+// Y'CbCr 4:2:0 planes of 8-bit (gr_present_yuv420) or 10-bit samples (gr_present_yuv420p10), both whole frames only.  A device's share of
+// a split frame is traced in blocks of factor x as many rows, so that they cover the rows its output blocks average.  `name`: the entry
+// point's, for its refusals.
+enum delivery { DELIVER_FLOAT4, DELIVER_RGBA8, DELIVER_YUV420, DELIVER_YUV420P10 };
 static int deliver_frame(delivery what, int layout, const char* name, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream,
                          const gr_camera* camera, const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1,
                          const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* options) {
@@ -1579,8 +1580,10 @@ static int deliver_frame(delivery what, int layout, const char* name, gr_render_
         GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, rows, rank, count, compact_out));
     else if (what == DELIVER_RGBA8)
         GR_CHECK(gr_present_rgba8(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, rows, rank, count, compact_out));
-    else
+    else if (what == DELIVER_YUV420)
         GR_CHECK(gr_present_yuv420(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, layout));
+    else
+        GR_CHECK(gr_present_yuv420p10(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, layout));
     if (timed) {
         HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
         s->resolve_timed = true;
@@ -1623,6 +1626,25 @@ int gr_render_frame_yuv420(gr_render_state* s, gr_program* p, const gr_metric* m
     s->resolve_timed = false;
     return deliver_frame(DELIVER_YUV420, layout, "gr_render_frame_yuv420", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2,
                          bg_width, bg_height, bg_levels, out_yuv420, options);
+}
+
+// The same with ten bits a sample (geodesic_hip_internal.h, "10-bit video frames"): gr_present_yuv420p10's refusals, before the frame is rendered
+int gr_render_frame_yuv420p10(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
+                              const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
+                              int bg_width, int bg_height, int bg_levels, void* out_yuv420p10, int layout, const gr_frame_options* options) {
+    if (!s || !p || !m || !camera || !out_yuv420p10) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420p10: null argument");
+    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420p10: layout (GR_YUV420_I420 or GR_YUV420_NV12)");
+    // (the state is read only for a pointer that is not aligned to 8 bytes)
+    if ((uintptr_t)out_yuv420p10 % 8 && ((uintptr_t)out_yuv420p10 % 2 || s->out_width % 4 == 0))
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420p10: out_yuv420p10 must be aligned to 8 bytes where the width is a "
+                                                           "multiple of 4, to 2 bytes otherwise");
+    if (options && options->strip_count > 1)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420p10: whole frames only (strip_count > 1); a split frame travels as float4 "
+                                                           "or RGBA8: gr_render_frame_tiled_as");
+    s->resolve_timed = false;
+    return deliver_frame(DELIVER_YUV420P10, layout, "gr_render_frame_yuv420p10", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1,
+                         bg2, bg_width, bg_height, bg_levels, out_yuv420p10, options);
 }
 
 }  // extern "C"

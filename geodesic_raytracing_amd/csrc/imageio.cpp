@@ -1,5 +1,6 @@
 // imageio.cpp — PNG in/out for the headless renderer (host side, not on the hot path), and video frames: the host statement of the
-// 8-bit Y'CbCr 4:2:0 encode (gr_rgba8_to_yuv420, which kernels/present.hip's gr_present_yuv420 is held to) and a YUV4MPEG2 writer.
+// 8-bit Y'CbCr 4:2:0 encode (gr_rgba8_to_yuv420, which kernels/present.hip's gr_present_yuv420 is held to), of the 10-bit one
+// (gr_frame_to_rgb10 and gr_rgb10_to_yuv420p10, which gr_present_yuv420p10 is held to) and a YUV4MPEG2 writer for both depths.
 //
 // Reference counterparts: the screenshot path main.cpp:2762-2808 (read the float4 frame, clamp, linear -> sRGB,
 // clamp, 8-bit, PNG through sf::Image) and the background loader graphics_settings.cpp:214-243 (sf::Image from a
@@ -44,6 +45,14 @@ unsigned char srgb8(float v) {
     const float c = clamp01(v);
     const float s = clamp01(lin_to_srgb(c));
     return (unsigned char)(s * 255.f);
+}
+
+// The 10-bit encode of one value: srgb8's chain with 1 023 for 255 (geodesic_hip_internal.h, "10-bit video frames").  gr_frame_to_rgb10
+// applies it; gr_srgb10_thresholds inverts it into the table gr_present_yuv420p10 searches.  A NaN's code is undefined, as its byte is.
+int code10(float v) {
+    const float c = clamp01(v);
+    const float s = clamp01(lin_to_srgb(c));
+    return (int)(s * 1023.f);
 }
 
 uint32_t get32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
@@ -243,6 +252,78 @@ int gr_rgba8_to_yuv420(const unsigned char* rgba8, int width, int height, int la
     return GR_OK;
 }
 
+// ---- 10-bit video frames (include/geodesic_hip_internal.h, "10-bit video frames", says all of it) ------------------------------------
+
+size_t gr_yuv420p10_bytes(int width, int height) { return 2 * gr_yuv420_bytes(width, height); }
+
+// gr_srgb8_thresholds with code10 for srgb8: out[k] = the smallest float of [0, 1] whose code is >= k, +infinity above code10(1.0f)
+int gr_srgb10_thresholds(float out[1024]) {
+    if (!out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_srgb10_thresholds: null argument");
+    auto of_bits = [](uint32_t bits) { float f; memcpy(&f, &bits, sizeof(f)); return f; };
+    const uint32_t one = 0x3f800000u;
+    const int top = code10(of_bits(one));
+    out[0] = 0.f;
+    for (int k = 1; k < 1024; k++) {
+        if (k > top) { out[k] = INFINITY; continue; }
+        uint32_t lo = 0, hi = one;   // code(lo) < k <= code(hi)
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (code10(of_bits(mid)) >= k) hi = mid; else lo = mid;
+        }
+        out[k] = of_bits(hi);
+    }
+    return GR_OK;
+}
+
+// R, G, B of every pixel as 10-bit codes, [height][width][3]; alpha is not encoded
+int gr_frame_to_rgb10(const float* frame_rgba_f32, int width, int height, unsigned short* out_rgb) {
+    if (!frame_rgba_f32 || !out_rgb) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_frame_to_rgb10: null argument");
+    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_frame_to_rgb10: the frame's size");
+    const size_t n = (size_t)width * height;
+    for (size_t i = 0; i < n; i++)
+        for (size_t c = 0; c < 3; c++) out_rgb[3 * i + c] = (unsigned short)code10(frame_rgba_f32[4 * i + c]);
+    return GR_OK;
+}
+
+// BT.709, limited range, 10 bits: gr_rgba8_to_yuv420's arithmetic with the coefficients of 876 / 1023 and 896 / 1023 (the largest
+// intermediate is 28700 * 4092 + 131072 < 2^27); each chroma row sums to zero, so a grey block gives 512 exactly.  GR_YUV420_I420 keeps a
+// code in the low ten bits of its word (yuv420p10le), GR_YUV420_NV12 in the high ten (P010).
+int gr_rgb10_to_yuv420p10(const unsigned short* rgb10, int width, int height, int layout, unsigned short* out) {
+    if (!rgb10 || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_rgb10_to_yuv420p10: null argument");
+    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_rgb10_to_yuv420p10: the frame's size");
+    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_rgb10_to_yuv420p10: layout (GR_YUV420_I420 or GR_YUV420_NV12)");
+    const size_t w = (size_t)width, h = (size_t)height, cw = (w + 1) / 2, ch = (h + 1) / 2;
+    for (size_t i = 0; i < 3 * w * h; i++)
+        if (rgb10[i] > 1023) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_rgb10_to_yuv420p10: a code above 1023");
+    const int shift = layout == GR_YUV420_NV12 ? 6 : 0;
+    for (size_t i = 0; i < w * h; i++) {
+        const int32_t r = rgb10[3 * i], g = rgb10[3 * i + 1], b = rgb10[3 * i + 2];
+        out[i] = (unsigned short)((64 + ((11931 * r + 40136 * g + 4052 * b + 32768) >> 16)) << shift);
+    }
+    unsigned short* chroma = out + w * h;
+    for (size_t cy = 0; cy < ch; cy++)
+        for (size_t cx = 0; cx < cw; cx++) {
+            int32_t sr = 0, sg = 0, sb = 0;
+            for (size_t j = 0; j < 2; j++)
+                for (size_t i = 0; i < 2; i++) {
+                    const size_t x = std::min(2 * cx + i, w - 1), y = std::min(2 * cy + j, h - 1);
+                    const unsigned short* px = rgb10 + 3 * (y * w + x);
+                    sr += px[0]; sg += px[1]; sb += px[2];
+                }
+            const unsigned short cb = (unsigned short)((512 + ((-6576 * sr - 22124 * sg + 28700 * sb + 131072) >> 18)) << shift);
+            const unsigned short cr = (unsigned short)((512 + ((28700 * sr - 26068 * sg - 2632 * sb + 131072) >> 18)) << shift);
+            if (layout == GR_YUV420_NV12) {
+                chroma[2 * (cy * cw + cx)] = cb;
+                chroma[2 * (cy * cw + cx) + 1] = cr;
+            } else {
+                chroma[cy * cw + cx] = cb;
+                chroma[cw * ch + cy * cw + cx] = cr;
+            }
+        }
+    return GR_OK;
+}
+
 struct gr_y4m {
     FILE* file;          // NULL after a short write: the handle then only waits for gr_y4m_close
     size_t frame_bytes;
@@ -257,20 +338,37 @@ static int y4m_put(gr_y4m* y, const void* data, size_t bytes, const char* what) 
     return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string("gr_y4m: short write of ") + what + " to " + y->path).c_str());
 }
 
-int gr_y4m_open(const char* path, int width, int height, int fps_num, int fps_den, gr_y4m** out) {
+// gr_y4m_open and gr_y4m_open_depth: `who` names the caller in a refusal, `sample_bytes` is 1 (C420jpeg) or 2 (C420p10)
+static int y4m_open(const char* who, const char* path, int width, int height, int fps_num, int fps_den, size_t sample_bytes, gr_y4m** out) {
+    const std::string name = who;
     if (out) *out = nullptr;
-    if (!path || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_y4m_open: null argument");
-    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_y4m_open: the frame's size");
-    if (fps_num < 1 || fps_den < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_y4m_open: the frame rate fps_num / fps_den needs both parts >= 1");
+    if (!path || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (name + ": null argument").c_str());
+    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (name + ": the frame's size").c_str());
+    if (fps_num < 1 || fps_den < 1)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (name + ": the frame rate fps_num / fps_den needs both parts >= 1").c_str());
     FILE* f = fopen(path, "wb");
-    if (!f) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string("gr_y4m_open: cannot write ") + path).c_str());
-    gr_y4m* y = new gr_y4m{f, gr_yuv420_bytes(width, height), path};
+    if (!f) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (name + ": cannot write " + path).c_str());
+    gr_y4m* y = new gr_y4m{f, sample_bytes * gr_yuv420_bytes(width, height), path};
     const std::string header = "YUV4MPEG2 W" + std::to_string(width) + " H" + std::to_string(height) + " F" + std::to_string(fps_num) + ":" +
-                               std::to_string(fps_den) + " Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n";
+                               std::to_string(fps_den) + " Ip A1:1 " + (sample_bytes == 2 ? "C420p10" : "C420jpeg") + " XCOLORRANGE=LIMITED\n";
     const int rc = y4m_put(y, header.data(), header.size(), "the header");
     if (rc != GR_OK) { delete y; return rc; }
     *out = y;
     return GR_OK;
+}
+
+int gr_y4m_open(const char* path, int width, int height, int fps_num, int fps_den, gr_y4m** out) {
+    return y4m_open("gr_y4m_open", path, width, height, fps_num, fps_den, 1, out);
+}
+
+// bit_depth 10: the frames gr_y4m_write_frame takes are gr_yuv420p10_bytes long - GR_YUV420_I420 planes of 16-bit little-endian words, which
+// is the order this library's hosts keep an unsigned short in
+int gr_y4m_open_depth(const char* path, int width, int height, int fps_num, int fps_den, int bit_depth, gr_y4m** out) {
+    if (bit_depth != 8 && bit_depth != 10) {
+        if (out) *out = nullptr;
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_y4m_open_depth: bit_depth " + std::to_string(bit_depth) + " (8 or 10)").c_str());
+    }
+    return y4m_open("gr_y4m_open_depth", path, width, height, fps_num, fps_den, bit_depth == 10 ? 2 : 1, out);
 }
 
 int gr_y4m_write_frame(gr_y4m* y, const unsigned char* i420) {

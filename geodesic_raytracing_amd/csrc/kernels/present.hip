@@ -162,3 +162,113 @@ extern "C" __global__ void __launch_bounds__(256) gr_present_yuv420(const float4
         default: return;
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// gr_present_yuv420p10 - gr_present_yuv420 with ten bits a sample: resolve -> 10-bit sRGB codes -> BT.709 Y'CbCr, limited range
+// (Y' 64 ... 940, Cb and Cr 64 ... 960), chroma sited and subsampled as above, every sample a 16-bit word.  The host states it in
+// csrc/imageio.cpp (gr_frame_to_rgb10, gr_rgb10_to_yuv420p10); the formulas and layouts are in include/geodesic_hip_internal.h
+// ("10-bit video frames").  GR_YUV420_I420 is yuv420p10le - planes Y, Cb, Cr, the code in the low ten bits of its word; GR_YUV420_NV12 is
+// P010 - the Y plane, then rows of (Cb, Cr) pairs, the code in the HIGH ten bits (code << 6).
+//
+// The code of a value is found as its byte is above, in a table of the same kind: GR_SRGB10_TREE_BITS (written in front of this
+// module's source next to the 8-bit one) holds gr_srgb10_thresholds' T[1 ... 1023] in the breadth-first order of the perfect search
+// tree, entry 0 unused.  A search is  i = 1;  10 x  i = 2 i + (tree[i] <= c);  code = i - 1024  - no branch, 10 LDS reads, a NaN gives 0.
+// Levels 0 to 5 are as conflict-free as the 8-bit tree's; levels 6 to 9 (64 to 512 consecutive entries) conflict as far as the
+// picture's values scatter.  The table is 4 KiB of LDS: every lane of the 64 x 4 workgroup copies four entries, 256 apart, so that
+// each of the four copies reads and writes 1 KiB contiguously, and all lanes meet at one barrier BEFORE any of them leaves.
+//
+// Shape and edges: gr_present_yuv420's - a lane owns 2 rows x 4 columns and forms its two chroma samples in registers, x and y are
+// clamped BEFORE the read, what lies past the edge is not stored.  Where width % 4 == 0 (dst is aligned to 8 bytes, the launcher
+// refuses anything else) a lane's stores are 8 bytes a luma row, 4 bytes a chroma plane or 8 bytes of P010's pairs.  Their alignment
+// follows from width % 4 == 0 for every plane offset: x0 is a multiple of 4 words, a luma row of 4 words, the luma plane (width * height
+// words) therefore too; the chroma width is even, so x0 / 2 and a chroma row are multiples of 2 words and so is the Cb plane; a P010
+// chroma row is width words and 2 (x0 / 2) a multiple of 4.  Any other width stores word by word (dst aligned to 2 bytes).
+// No claim about its speed is made here: tools/present_yuv_probe.py times it against gr_present_yuv420 on the same source.
+
+__device__ __forceinline__ int srgb10_of(const float* tree, float v) {
+    const float c = v > 1.0f ? 1.0f : v;   // (not fminf: a NaN stays a NaN)
+    unsigned int i = 1;
+#pragma unroll
+    for (int level = 0; level < 10; level++) i = 2u * i + (tree[i] <= c ? 1u : 0u);
+    return (int)(i - 1024u);
+}
+
+template <int F>
+__device__ __forceinline__ void present_yuv420p10_lane(const float* tree, const float4* __restrict__ source, unsigned short* __restrict__ out,
+                                                       int width, int height, int layout, int x0, int y0) {
+    const size_t source_width = (size_t)width * F;
+    const int shift = layout == GR_YUV420_NV12 ? 6 : 0;   // P010 keeps a code in the high ten bits of its word
+    unsigned int luma[2][4];
+    int sum_r[2] = {0, 0}, sum_g[2] = {0, 0}, sum_b[2] = {0, 0};   // of the 2 x 2 block behind chroma sample 0 and 1 of this lane
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int y = min(y0 + j, height - 1);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int x = min(x0 + i, width - 1);
+            const float4 pixel = box_average<F>(source + (size_t)y * F * source_width + (size_t)x * F, source_width);
+            const int r = srgb10_of(tree, pixel.x), g = srgb10_of(tree, pixel.y), b = srgb10_of(tree, pixel.z);
+            luma[j][i] = (unsigned int)(64 + ((11931 * r + 40136 * g + 4052 * b + 32768) >> 16)) << shift;
+            sum_r[i / 2] += r;
+            sum_g[i / 2] += g;
+            sum_b[i / 2] += b;
+        }
+    }
+    unsigned int cb[2], cr[2];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        cb[k] = (unsigned int)(512 + ((-6576 * sum_r[k] - 22124 * sum_g[k] + 28700 * sum_b[k] + 131072) >> 18)) << shift;
+        cr[k] = (unsigned int)(512 + ((28700 * sum_r[k] - 26068 * sum_g[k] - 2632 * sum_b[k] + 131072) >> 18)) << shift;
+    }
+    const size_t chroma_width = (size_t)((width + 1) / 2), chroma_height = (size_t)((height + 1) / 2);
+    unsigned short* chroma = out + (size_t)width * height;   // both layouts: the chroma follows the luma plane
+    const size_t cx = (size_t)(x0 / 2), cy = (size_t)(y0 / 2);
+    if ((width & 3) == 0) {   // (uniform) x0 + 3 < width, every plane offset below is a multiple of its store's size
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+            if (y0 + j < height)
+                *(uint2*)(out + (size_t)(y0 + j) * width + x0) = make_uint2(luma[j][0] | (luma[j][1] << 16), luma[j][2] | (luma[j][3] << 16));
+        if (layout == GR_YUV420_NV12) {
+            *(uint2*)(chroma + cy * 2 * chroma_width + 2 * cx) = make_uint2(cb[0] | (cr[0] << 16), cb[1] | (cr[1] << 16));
+        } else {
+            *(unsigned int*)(chroma + cy * chroma_width + cx) = cb[0] | (cb[1] << 16);
+            *(unsigned int*)(chroma + chroma_width * chroma_height + cy * chroma_width + cx) = cr[0] | (cr[1] << 16);
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (y0 + j < height && x0 + i < width) out[(size_t)(y0 + j) * width + x0 + i] = (unsigned short)luma[j][i];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        if (x0 + 2 * k >= width) continue;
+        if (layout == GR_YUV420_NV12) {
+            chroma[cy * 2 * chroma_width + 2 * (cx + k)] = (unsigned short)cb[k];
+            chroma[cy * 2 * chroma_width + 2 * (cx + k) + 1] = (unsigned short)cr[k];
+        } else {
+            chroma[cy * chroma_width + cx + k] = (unsigned short)cb[k];
+            chroma[chroma_width * chroma_height + cy * chroma_width + cx + k] = (unsigned short)cr[k];
+        }
+    }
+}
+
+extern "C" __global__ void __launch_bounds__(256) gr_present_yuv420p10(const float4* __restrict__ source, unsigned short* __restrict__ out, int width,
+                                                                       int height, int factor, int layout) {
+    __shared__ float tree[1024];
+    const unsigned int lane = threadIdx.y * 64u + threadIdx.x;   // the launcher's workgroup is 64 x 4: four entries per lane
+#pragma unroll
+    for (unsigned int k = 0; k < 4u; k++) tree[lane + 256u * k] = __uint_as_float(GR_SRGB10_TREE_BITS[lane + 256u * k]);
+    __syncthreads();
+    const long long column = 4ll * ((long long)blockIdx.x * blockDim.x + threadIdx.x), row = 2ll * ((long long)blockIdx.y * blockDim.y + threadIdx.y);
+    if (column >= width || row >= height) return;
+    const int x0 = (int)column, y0 = (int)row;
+    switch (factor) {
+        case 1: present_yuv420p10_lane<1>(tree, source, out, width, height, layout, x0, y0); break;
+        case 2: present_yuv420p10_lane<2>(tree, source, out, width, height, layout, x0, y0); break;
+        case 3: present_yuv420p10_lane<3>(tree, source, out, width, height, layout, x0, y0); break;
+        case 4: present_yuv420p10_lane<4>(tree, source, out, width, height, layout, x0, y0); break;
+        default: return;
+    }
+}

@@ -404,11 +404,18 @@ class RenderState:
             self.handle = None
 
     def render(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None, rgba8=False,
-               yuv420=None):
+               yuv420=None, bit_depth=8):
         """Enqueue one frame. `out_ptr`: device pointer to float4[width*height] (or None to stop after render-data);
-        `background`: (device_ptr, width, height, levels) or ((ptr1, ptr2), width, height, levels).  yuv420 = a layout: render_yuv420."""
+        `background`: (device_ptr, width, height, levels) or ((ptr1, ptr2), width, height, levels).  yuv420 = a layout: render_yuv420, or
+        with bit_depth = 10 render_yuv420p10."""
+        if bit_depth not in (8, 10) or (bit_depth == 10 and yuv420 is None):
+            raise ValueError(f"RenderState.render: bit_depth={bit_depth!r} (8, or 10 with a yuv420 layout)")
         features, arr, n, bg1, bg2, bw, bh, bl = _frame_arguments(metric, features, cfg_values, background)
         options = ctypes.byref(options) if options is not None else None
+        if yuv420 is not None and bit_depth == 10:
+            check(lib.gr_render_frame_yuv420p10(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr,
+                                                n, bg1, bg2, bw, bh, bl, out_ptr, int(yuv420), options))
+            return
         if yuv420 is not None:
             check(lib.gr_render_frame_yuv420(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n,
                                              bg1, bg2, bw, bh, bl, out_ptr, int(yuv420), options))
@@ -428,6 +435,14 @@ class RenderState:
         yuv420_bytes(width, height) bytes, aligned to 4, in `layout` (YUV420_I420: planes Y, Cb, Cr; YUV420_NV12: Y, then Cb Cr pairs);
         every byte is rgba8_to_yuv420's of the frame render_rgba8() writes.  Whole frames only."""
         self.render(program, metric, camera, out_ptr, background, features, cfg_values, options, stream, yuv420=layout)
+
+    def render_yuv420p10(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None,
+                         layout=YUV420_I420):
+        """render(), delivered as 10-bit BT.709 Y'CbCr 4:2:0 in 16-bit words (gr_render_frame_yuv420p10): `out_ptr` is a device pointer to
+        yuv420p10_bytes(width, height) bytes, aligned to 8 where the width is a multiple of 4 and to 2 otherwise, in `layout` (YUV420_I420:
+        yuv420p10le, planes Y, Cb, Cr; YUV420_NV12: P010, Y then Cb Cr pairs, codes in the high ten bits); every word is
+        rgb10_to_yuv420p10(frame_to_rgb10(...))'s of the float frame render() writes (a NaN gives code 0).  Whole frames only."""
+        self.render(program, metric, camera, out_ptr, background, features, cfg_values, options, stream, yuv420=layout, bit_depth=10)
 
     def prepass_policy(self):
         """(frames rendered with a prepass, frames the policy rendered without, fraction of cells the last inspected prepass marked)"""
@@ -576,20 +591,63 @@ def rgba8_to_yuv420(pixels, layout=YUV420_I420):
     return out
 
 
-class Y4MWriter:
-    """An uncompressed YUV4MPEG2 file (gr_y4m_open / _write_frame / _close): one header line, then "FRAME\\n" + the I420 bytes per frame.
-    fps: an int, or (numerator, denominator).  Use as a context manager, or call close()."""
+def yuv420p10_bytes(width, height):
+    """the bytes of a width x height frame in 10-bit Y'CbCr 4:2:0 (16-bit words), either layout: 2 * yuv420_bytes(width, height)"""
+    return int(lib.gr_yuv420p10_bytes(int(width), int(height)))
 
-    def __init__(self, path, width, height, fps=24):
+
+def srgb10_thresholds():
+    """gr_srgb10_thresholds: float32 [1024], T[k] = the smallest float of [0, 1] whose 10-bit sRGB code is >= k (T[0] = 0, +inf above the code
+    of 1.0); the code of c is the number of k in 1 ... 1023 with T[k] <= c.  The table gr_present_yuv420p10 searches."""
+    out = np.empty(1024, dtype=np.float32)
+    check(lib.gr_srgb10_thresholds(out.ctypes.data_as(ctypes.POINTER(c_float))))
+    return out
+
+
+def frame_to_rgb10(frame):
+    """The host statement of the 10-bit encode (gr_frame_to_rgb10): float [H, W, 4] in linear light -> uint16 [H, W, 3], every value of R, G,
+    B clamped to [0, 1], through lin_to_srgb, clamped, times 1023 and truncated; alpha is not encoded (a NaN is undefined here, 0 on the device)."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.ndim != 3 or frame.shape[2] != 4 or frame.size == 0:
+        raise ValueError(f"frame_to_rgb10: a frame of shape {frame.shape} is not [H, W, 4]")
+    h, w = frame.shape[:2]
+    out = np.empty((h, w, 3), dtype=np.uint16)
+    check(lib.gr_frame_to_rgb10(frame.ctypes.data_as(c_void_p), w, h, out.ctypes.data_as(c_void_p)))
+    return out
+
+
+def rgb10_to_yuv420p10(codes, layout=YUV420_I420):
+    """The host statement of the 10-bit video encode (gr_rgb10_to_yuv420p10; include/geodesic_hip_internal.h gives the integer formulas):
+    uint16 [H, W, 3] codes of at most 1023 -> uint16 [yuv420p10_bytes(W, H) / 2], BT.709 limited range, one chroma pair per 2 x 2 block (an
+    odd edge counts twice).  YUV420_I420: yuv420p10le; YUV420_NV12: P010 (code << 6).  What gr_present_yuv420p10 computes on the device."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint16)
+    if codes.ndim != 3 or codes.shape[2] != 3 or codes.size == 0:
+        raise ValueError(f"rgb10_to_yuv420p10: codes of shape {codes.shape} are not [H, W, 3]")
+    h, w = codes.shape[:2]
+    out = np.empty(yuv420p10_bytes(w, h) // 2, dtype=np.uint16)
+    check(lib.gr_rgb10_to_yuv420p10(codes.ctypes.data_as(c_void_p), w, h, int(layout), out.ctypes.data_as(c_void_p)))
+    return out
+
+
+class Y4MWriter:
+    """An uncompressed YUV4MPEG2 file (gr_y4m_open / _open_depth / _write_frame / _close): one header line, then "FRAME\\n" + the I420 planes
+    per frame.  fps: an int, or (numerator, denominator).  bit_depth 8: frames of yuv420_bytes uint8; 10: frames of yuv420p10_bytes / 2
+    uint16 (written as little-endian words).  Use as a context manager, or call close()."""
+
+    def __init__(self, path, width, height, fps=24, bit_depth=8):
         num, den = fps if isinstance(fps, tuple) else (fps, 1)
-        self.frame_bytes = yuv420_bytes(width, height)
+        self.sample = np.dtype(np.uint8) if bit_depth == 8 else np.dtype("<u2")
+        self.frame_bytes = yuv420_bytes(width, height) * self.sample.itemsize
         self.handle = c_void_p()
-        check(lib.gr_y4m_open(os.fsencode(path), int(width), int(height), int(num), int(den), ctypes.byref(self.handle)))
+        if bit_depth == 8:
+            check(lib.gr_y4m_open(os.fsencode(path), int(width), int(height), int(num), int(den), ctypes.byref(self.handle)))
+        else:
+            check(lib.gr_y4m_open_depth(os.fsencode(path), int(width), int(height), int(num), int(den), int(bit_depth), ctypes.byref(self.handle)))
 
     def write(self, i420):
-        i420 = np.ascontiguousarray(i420, dtype=np.uint8)
-        if i420.size != self.frame_bytes:
-            raise ValueError(f"Y4MWriter: a frame of {i420.size} bytes, {self.frame_bytes} expected")
+        i420 = np.ascontiguousarray(i420, dtype=self.sample)
+        if i420.nbytes != self.frame_bytes:
+            raise ValueError(f"Y4MWriter: a frame of {i420.nbytes} bytes, {self.frame_bytes} expected")
         check(lib.gr_y4m_write_frame(self.handle, i420.ctypes.data_as(c_void_p)))
 
     def close(self):

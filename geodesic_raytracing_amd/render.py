@@ -14,6 +14,8 @@
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --geodesic-speed 0,0.3,0 --frames 24 --out fall.y4m
     # a camera that rides no geodesic: position and orientation interpolated from --camera / --quat to --camera-to / --quat-to over --frames
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --fps 30000/1001 --out pan.y4m
+    # ... as a 10-bit master (C420p10: 16-bit little-endian words, 3 bytes a pixel come back) for a Main10 / AV1 / ProRes encode
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --bit-depth 10 --out pan10.y4m
 """
 import argparse
 import ctypes
@@ -23,7 +25,7 @@ import sys
 import numpy as np
 
 import geodesic_raytracing_amd as gra
-from geodesic_raytracing_amd.pipeline import DeviceBuffer, PinnedBuffer, ProgramManager, Y4MWriter, yuv420_bytes
+from geodesic_raytracing_amd.pipeline import DeviceBuffer, PinnedBuffer, ProgramManager, Y4MWriter, yuv420_bytes, yuv420p10_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -88,7 +90,7 @@ def camera_path(position, quat, position_to=None, quat_to=None, frames=1):
 
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
-           parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None):
+           parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
@@ -96,12 +98,16 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     pixel through pinned memory - the bytes pipeline.encode_srgb8 makes of the float frame.
     yuv420: the frames are uint8 [yuv420_bytes(W, H)] instead: 8-bit BT.709 Y'CbCr 4:2:0 in I420 order (planes Y, Cb, Cr), made on the device in
     the launch that resolves and encodes (RenderState.render_yuv420) and fetched at 1.5 bytes a pixel through pinned memory - the bytes
-    pipeline.rgba8_to_yuv420 makes of the rgba8 frame.
+    pipeline.rgba8_to_yuv420 makes of the rgba8 frame.  With bit_depth=10 they are uint16 [yuv420p10_bytes(W, H) / 2]: 10-bit samples in
+    yuv420p10le order (RenderState.render_yuv420p10), 3 bytes a pixel through pinned memory - the words
+    pipeline.rgb10_to_yuv420p10(pipeline.frame_to_rgb10(...)) makes of the float frame.
     cameras: [(position, quat)] (camera_path) - a list of frames, one per pose, of a camera that rides no geodesic (not with geodesic_speed).
     mips: where the sky's mip slices are made - "host" (pack_background, all slices uploaded) or "device" (build_background: the image is
     uploaded and the slices are built there, the same bytes)."""
     if mips not in ("host", "device"):
         raise ValueError(f"render: mips={mips!r} (host or device)")
+    if bit_depth not in (8, 10) or (bit_depth == 10 and not yuv420):
+        raise ValueError(f"render: bit_depth={bit_depth!r} (8, or 10 with yuv420=True)")
     if cameras is not None and geodesic_speed is not None:
         raise ValueError("render: cameras (interpolated poses) and geodesic_speed (a camera on its geodesic) exclude each other")
     metric = gra.Metric(metric_name, scripts or os.path.join(HERE, "scripts"))
@@ -116,7 +122,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     else:
         packed, levels = gra.pack_background(rgba)
         dbg = DeviceBuffer.from_numpy(device, packed)
-    out_bytes = yuv420_bytes(width, height) if yuv420 else width * height * (4 if rgba8 else 16)
+    deep = bool(yuv420) and bit_depth == 10
+    out_bytes = yuv420p10_bytes(width, height) if deep else yuv420_bytes(width, height) if yuv420 else width * height * (4 if rgba8 else 16)
     out = DeviceBuffer(device, out_bytes)
     pinned = PinnedBuffer(out_bytes) if rgba8 or yuv420 else None
     cam = gra.default_camera(camera_pos, camera_quat)
@@ -124,7 +131,9 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     bg = (dbg.ptr, rgba.shape[1], rgba.shape[0], levels)
 
     def one_frame(options, cam=cam):
-        if yuv420:
+        if deep:
+            state.render_yuv420p10(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
+        elif yuv420:
             state.render_yuv420(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
         elif rgba8:
             state.render_rgba8(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
@@ -134,6 +143,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
             return out.to_numpy(np.float32, (height, width, 4))
         pinned.download_async(None, out.ptr, out_bytes)   # the frame's stream: copies queue behind its launches
         gra.check(gra.lib.gr_stream_synchronize(None))
+        if deep:
+            return pinned.view(np.uint16, (out_bytes // 2,)).copy()
         return pinned.view(np.uint8, (out_bytes,) if yuv420 else (height, width, 4)).copy()
 
     def frames_of_the_call():
@@ -248,6 +259,8 @@ def main(argv=None):
     ap.add_argument("--devices", default=None, help="0,1,2,3: deal the rows of every frame to these GPUs (one process, peer copies; a device may "
                     "repeat); each traces, resolves and - with --encode device - encodes its share, the share rotating over --frames")
     ap.add_argument("--fps", default="24", help="frame rate of a .y4m file: N or N/D (24; 30000/1001)")
+    ap.add_argument("--bit-depth", type=int, choices=[8, 10], default=8, help="bits a sample of a .y4m file: 8 (C420jpeg, 1.5 bytes a pixel) or 10 "
+                    "(C420p10: 16-bit little-endian words, 3 bytes a pixel - the master for a 10-bit encode).  Only with --out NAME.y4m")
     ap.add_argument("--out", required=True, help="NAME.png: one PNG, or NAME_000.png ... for a sequence.  NAME.y4m: all frames in one uncompressed "
                     "YUV4MPEG2 file of 8-bit BT.709 Y'CbCr 4:2:0 frames, converted on the device")
     a = ap.parse_args(argv)
@@ -256,6 +269,8 @@ def main(argv=None):
         fps = parse_fps(a.fps)
     except ValueError as e:
         ap.error(f"--fps: {e}")
+    if a.bit_depth != 8 and not video:
+        ap.error("--bit-depth 10 is a depth of video frames: it needs --out NAME.y4m (a PNG is 8-bit sRGB)")
     if video and a.devices is not None:
         ap.error("--out NAME.y4m with --devices: a split frame travels as float4 or RGBA8, not as 4:2:0 planes; render the video on one device")
     if (a.camera_to or a.quat_to) and a.geodesic_speed:
@@ -298,14 +313,14 @@ def main(argv=None):
     result = render(a.metric, w, h, a.scripts, cfg, position, quat, a.redshift, a.adaptive,
                     read_png(a.background) if a.background else None, a.device, a.fov, a.universe, geodesic_speed=speed,
                     geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
-                    rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras)
+                    rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth)
     if speed is None and cameras is None:
         result = [result]
     if video:
-        with Y4MWriter(a.out, w, h, fps) as stream:
+        with Y4MWriter(a.out, w, h, fps, bit_depth=a.bit_depth) as stream:
             for frame in result:
                 stream.write(frame)
-        print(f"wrote {a.out} ({w}x{h}, {len(result)} frames at {fps[0]}/{fps[1]} a second, BT.709 Y'CbCr 4:2:0)")
+        print(f"wrote {a.out} ({w}x{h}, {len(result)} frames at {fps[0]}/{fps[1]} a second, {'10-bit ' if a.bit_depth == 10 else ''}BT.709 Y'CbCr 4:2:0)")
         return 0
     stem, ext = os.path.splitext(a.out)
     for i, frame in enumerate(result):

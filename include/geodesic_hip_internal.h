@@ -149,6 +149,59 @@ int gr_host_alloc(size_t bytes, void** out);
 int gr_host_free(void* ptr);
 int gr_device_download_async(void* stream, void* host_dst, const void* device_src, size_t bytes);
 
+/* ---- 10-bit video frames ------------------------------------------------------------------------------------------------------
+ * The video frames of geodesic_hip.h with ten bits a sample: BT.709 Y'CbCr 4:2:0, limited range, every sample a 16-bit little-endian word.
+ *
+ * The 10-bit sRGB code of one linear value is the 8-bit chain of gr_frame_to_rgba8 with 1 023 for 255:
+ *   code10(v) = (int)(clamp01(lin_to_srgb(clamp01(v))) * 1023.f), truncated, in float arithmetic with the library's own powf.
+ * A NaN's code is undefined on the host and 0 on the device, as for bytes; values above 1, +infinity included, are clamped to 1 first;
+ * negative values and -0 give 0.
+ *
+ * Matrix (int32 arithmetic on the codes R, G, B in 0 ... 1023, >> arithmetic): Y' = 64 + 876 E'y, Cb = 512 + 896 E'pb, Cr = 512 + 896 E'pr as
+ *   per pixel:        Y  =  64 + (( 11931*R  + 40136*G  +  4052*B  +  32768) >> 16)
+ *   per 2 x 2 block:  Cb = 512 + (( -6576*SR - 22124*SG + 28700*SB + 131072) >> 18)
+ *                     Cr = 512 + (( 28700*SR - 26068*SG -  2632*SB + 131072) >> 18)      SR, SG, SB: the sums of its four pixels' codes
+ * The coefficients are 876/1023 * 2^16 and 896/1023 * 2^16 times BT.709's weights, rounded; the luma row sums to 56 119 = round(876/1023 *
+ * 2^16), each chroma row to 0.  So Y is in 64 ... 940 (black 64, white 940), Cb and Cr in 64 ... 960, a grey gives Cb = Cr = 512 exactly, and
+ * every sample is within 0.51 of a code of the real-valued formula; the largest intermediate is about 1.2e8.
+ *
+ * Chroma siting and edges are the 8-bit rules: cw = (width+1)/2, ch = (height+1)/2; a sample is the mean of its four ENCODED pixels
+ * (C420jpeg siting); an odd width or height counts the edge column or row twice.
+ *
+ * Layouts: a frame is gr_yuv420p10_bytes(width, height) = 2 * gr_yuv420_bytes(width, height) bytes, no padding.  GR_YUV420_I420 is
+ * yuv420p10le: planes Y, Cb, Cr, the code in the LOW ten bits of each word.  GR_YUV420_NV12 is P010: the Y plane, then ch rows of cw
+ * (Cb, Cr) word pairs, the code in the HIGH ten bits (code << 6, the low six bits zero).
+ *
+ * File: .y4m with the header "YUV4MPEG2 W<w> H<h> F<n>:<d> Ip A1:1 C420p10 XCOLORRANGE=LIMITED\n"; per frame "FRAME\n" and the
+ * GR_YUV420_I420 planes.
+ *
+ * Every function below refuses, before it writes anything, with GR_ERROR_INVALID_ARGUMENT and a message that names it: a NULL, a size
+ * below 1, an unknown layout or depth, a code above 1 023 in rgb10. */
+/* out[0] = 0; out[k] = the smallest float of [0, 1] whose code is >= k, found by bisection over the bit patterns 0 ... 0x3f800000 with
+ * code10 itself; +infinity for every k above code10(1.0f), which need not be 1 023.  code10(c) = the number of k in 1 ... 1023 with
+ * out[k] <= c: the device searches this table, so it agrees with the host's powf by construction. */
+int gr_srgb10_thresholds(float out[1024]);
+/* out_rgb: [height][width][3] codes of the frame's R, G, B; alpha is not encoded */
+int gr_frame_to_rgb10(const float* frame_rgba_f32, int width, int height, unsigned short* out_rgb);
+/* rgb10: [height][width][3] codes; out: gr_yuv420p10_bytes(width, height) bytes in `layout` - the definition above */
+int gr_rgb10_to_yuv420p10(const unsigned short* rgb10, int width, int height, int layout, unsigned short* out);
+/* 2 * gr_yuv420_bytes(width, height); 0 for a size below 1 */
+size_t gr_yuv420p10_bytes(int width, int height);
+/* gr_y4m_open with a depth: bit_depth 8 is gr_y4m_open byte for byte, 10 writes the C420p10 header and takes frames of
+ * gr_yuv420p10_bytes in GR_YUV420_I420 order.  gr_y4m_write_frame and gr_y4m_close serve both (the handle knows its frame's size), with
+ * the same rules for a short write. */
+int gr_y4m_open_depth(const char* path, int width, int height, int fps_num, int fps_den, int bit_depth, gr_y4m** out);
+/* gr_present_yuv420 with ten bits a sample (kernels/present.hip, set-up module): dst (device, gr_yuv420p10_bytes(width, height) bytes) holds
+ * exactly gr_rgb10_to_yuv420p10(gr_frame_to_rgb10(the frame gr_resolve_supersampled would have written)) but for a NaN, whose code is 0.
+ * Refused before any device call: what gr_present_yuv420 refuses, with dst aligned to 8 bytes where width % 4 == 0 (8-byte stores) and to
+ * 2 bytes at any other width (stores of one word). */
+int gr_present_yuv420p10(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout);
+/* gr_render_frame_yuv420 with gr_present_yuv420p10 as its one launch after the frame.  Whole frames only: strip_count > 1 is refused before
+ * anything is rendered, as a NULL, an unknown layout or a misaligned out_yuv420p10 (gr_present_yuv420p10's rule at the state's width) is. */
+int gr_render_frame_yuv420p10(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
+                              const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
+                              int bg_width, int bg_height, int bg_levels, void* out_yuv420p10, int layout, const gr_frame_options* options);
+
 /* ---- fused MI355X path (no reference counterpart) ------------------------------------------- */
 
 /* Prepass termination flags from one fused trace at prepass resolution (replaces the sequence

@@ -7,6 +7,9 @@ At 3840x2160, factors 1 and 2:
  (2) the pinned download (gr_device_download_async + a stream synchronise, host clock) of 1.5, 4 and 16 bytes a pixel;
  (3) a sequence of 24 frames through gr_render_frame_yuv420 + the pinned download of each, against the same sequence through
      gr_render_frame_rgba8 + its download + the host conversion (gr_rgba8_to_yuv420), host clock around each whole sequence, in turn.
+ (4) gr_present_yuv420p10 (10-bit samples in 16-bit words: yuv420p10le and P010) against gr_present_yuv420 on the same source, the 8-bit
+     launch twice in every round as in (1); the shader clock the driver reports (read, never set) before and after is noted.
+     Section "launch10"; alone:  python tools/present_yuv_probe.py --section launch10
 Kerr (scripts/kerr_boyer.js, a = 0.45, substituted program, fused path, one frame at a time); the sources of (1) are rendered frames.
 Every section is a child process of its own under a time limit of its own, started only if the one before it ended well: a fault, an
 abort or a time limit ends the probe there, and what was measured until then is on file.  HIP events on a stream of the library's own
@@ -24,14 +27,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import geodesic_raytracing_amd as gra  # noqa: E402
 from geodesic_raytracing_amd import check, lib  # noqa: E402
-from geodesic_raytracing_amd.pipeline import DeviceBuffer, PinnedBuffer, rgba8_to_yuv420, yuv420_bytes  # noqa: E402
+from geodesic_raytracing_amd.pipeline import DeviceBuffer, PinnedBuffer, rgba8_to_yuv420, yuv420_bytes, yuv420p10_bytes  # noqa: E402
 from tools.supersample_probe import Timer, hip_runtime, say  # noqa: E402
 
 SIZE = (3840, 2160)
 FACTORS = (1, 2)
 WARMUP, STEPS = 5, 30
 SEQUENCE, SEQUENCE_ROUNDS = 24, 3
-SECTIONS = {"launch": 240, "download": 120, "sequence": 420}   # name: seconds the child may take
+SECTIONS = {"launch": 240, "download": 120, "sequence": 420, "launch10": 240}   # name: seconds the child may take
 
 
 def alternating(timer, works):
@@ -115,6 +118,64 @@ def section_launch(stream):
     return lines
 
 
+def shader_clock():
+    """the shader clock levels the driver reports for the first card that has them, the current one starred (read only)"""
+    import glob
+    for path in sorted(glob.glob("/sys/class/drm/card*/device/pp_dpm_sclk")):
+        try:
+            with open(path) as fh:
+                levels = [line.strip() for line in fh if line.strip()]
+        except OSError:
+            continue
+        if levels:
+            return ", ".join(levels)
+    return "not readable"
+
+
+def section_launch10(stream):
+    hip = hip_runtime()
+    timer = Timer(hip, stream)
+    metric, cfgv, feats, prog, _sky, bg = kerr()
+    opts = gra.frame_options(mode=gra.MODE_FUSED, reuse_still_camera=0)
+    w, h = SIZE
+    lines = [f"(4) 10-bit against 8-bit, the launch alone, {w}x{h} output; substituted program {prog.build_key}; {WARMUP} warm-up + {STEPS} timed launches "
+             f"each, in turn, HIP events, median (min, p90)", f"    shader clock before: {shader_clock()}"]
+    for f in FACTORS:
+        tw, th = w * f, h * f
+        read_bytes, bytes8, bytes10 = tw * th * 16, yuv420_bytes(w, h), yuv420p10_bytes(w, h)
+        plain = gra.RenderState(tw, th, 0)
+        traced = DeviceBuffer(0, read_bytes)
+        out8, out10 = DeviceBuffer(0, bytes8), DeviceBuffer(0, bytes10)
+        plain.render(prog, metric, gra.default_camera(), traced.ptr, bg, feats, cfgv, opts, stream)
+        check(lib.gr_stream_synchronize(stream))
+        del plain
+
+        def planar10():
+            check(lib.gr_present_yuv420p10(prog.handle, stream, traced.ptr, out10.ptr, w, h, f, gra.YUV420_I420))
+
+        def p010():
+            check(lib.gr_present_yuv420p10(prog.handle, stream, traced.ptr, out10.ptr, w, h, f, gra.YUV420_NV12))
+
+        def i420():
+            check(lib.gr_present_yuv420(prog.handle, stream, traced.ptr, out8.ptr, w, h, f, gra.YUV420_I420))
+
+        def i420_again():   # the same launch a second time in every round: the spread between two equal launches in this session
+            i420()
+
+        t = alternating(timer, {"planar10": planar10, "i420": i420, "p010": p010, "i420 again": i420_again})
+        m = {k: float(np.median(v)) for k, v in t.items()}
+        lines += ["", f"    factor {f} (source {tw}x{th}): both launches read {read_bytes / 1e6:.0f} MB; 8 bits write {bytes8 / 1e6:.1f} MB, 10 bits {bytes10 / 1e6:.1f} MB",
+                  f"    gr_present_yuv420p10, yuv420p10le  {say(t['planar10'])}   {(read_bytes + bytes10) / m['planar10'] / 1e6:7.0f} GB/s read + written",
+                  f"    gr_present_yuv420p10, P010         {say(t['p010'])}   {(read_bytes + bytes10) / m['p010'] / 1e6:7.0f} GB/s read + written",
+                  f"    gr_present_yuv420, I420            {say(t['i420'])}   {(read_bytes + bytes8) / m['i420'] / 1e6:7.0f} GB/s read + written",
+                  f"    gr_present_yuv420, I420 again      {say(t['i420 again'])}   (|again - first| = {abs(m['i420 again'] - m['i420']):.4f} ms: the session's spread)",
+                  f"    yuv420p10le - I420 = {m['planar10'] - m['i420']:+.4f} ms, P010 - I420 = {m['p010'] - m['i420']:+.4f} ms;  yuv420p10le / I420 = "
+                  f"{m['planar10'] / m['i420']:.3f}, P010 / I420 = {m['p010'] / m['i420']:.3f}"]
+        del traced, out8, out10
+    lines.append(f"    shader clock after:  {shader_clock()}")
+    return lines
+
+
 def section_download(stream):
     w, h = SIZE
     lines = [f"(2) pinned download of a {w}x{h} frame (gr_device_download_async + gr_stream_synchronize), host clock, {WARMUP} warm-up + 12 timed"]
@@ -181,7 +242,7 @@ def child(section):
         raise SystemExit("present_yuv_probe: no GPU (there is nothing to measure without one)")
     stream = ctypes.c_void_p()
     check(lib.gr_stream_create(0, 0, ctypes.byref(stream)))
-    lines = {"launch": section_launch, "download": section_download, "sequence": section_sequence}[section](stream)
+    lines = {"launch": section_launch, "download": section_download, "sequence": section_sequence, "launch10": section_launch10}[section](stream)
     check(lib.gr_stream_destroy(stream))
     print("\n".join(lines), flush=True)
 
