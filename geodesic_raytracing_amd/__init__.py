@@ -122,6 +122,7 @@ class Transport(ctypes.Structure):
 
 MODE_REFERENCE, MODE_FUSED = 0, 1
 FRAME_F32, FRAME_RGBA8 = 0, 1
+FRAME_YUV420, FRAME_YUV420P10 = 2, 3   # GR_FRAME_YUV420 / _YUV420P10: the video formats of gr_deliver_accumulated (include/geodesic_hip_internal.h)
 YUV420_I420, YUV420_NV12 = 0, 1   # GR_YUV420_*: the layouts of an 8-bit Y'CbCr 4:2:0 frame (include/geodesic_hip.h, "video frames")
 EVAL_METRIC_TENSOR, EVAL_METRIC_DERIVATIVES, EVAL_ACCELERATION, EVAL_TO_POLAR, EVAL_FROM_POLAR, EVAL_ORIGIN_DISTANCE = range(6)
 (STAGE_CAMERA, STAGE_PREPASS, STAGE_INIT, STAGE_TRACE, STAGE_RENDER_DATA, STAGE_ADAPTIVE, STAGE_RENDER) = range(7)
@@ -323,6 +324,12 @@ _SIGNATURES = {
     "gr_frame_to_rgb10": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "gr_rgb10_to_yuv420p10": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "gr_y4m_open_depth": (c_int, [c_char_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "gr_accumulate_frame": (c_int, [c_void_p, c_void_p, c_size_t, c_float, c_int]),
+    "gr_shutter_accumulate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int]),
+    "gr_render_subframe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Camera), ctypes.POINTER(Features),
+                                   ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                                   ctypes.POINTER(FrameOptions)]),
+    "gr_deliver_accumulated": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():
@@ -345,4 +352,4 @@ def check(rc):
 
 from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, build_background,  # noqa: E402,F401
                        default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background, rgba8_to_yuv420,
-                       yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes)
+                       yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes, accumulate_frame)

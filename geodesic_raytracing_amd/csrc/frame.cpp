@@ -82,6 +82,10 @@ struct gr_render_state {
     int supersample = 1;
     int out_width = 0, out_height = 0;
     void* traced_frame = nullptr;
+    // gr_render_subframe: the sum of the shutter's sub-frames so far, float4[out_width * out_height], allocated with the state's first
+    // sub-frame; accumulated: sub-frames in it since the last one with `first` (0: nothing to add to, nothing to deliver)
+    void* accumulation = nullptr;
+    unsigned long long accumulated = 0;
     hipEvent_t ev_resolve[2] = {};   // time_kernels = 1: around the resolve launch (gr_render_state_resolve_ms)
     bool resolve_timed = false;
     upload_ring uploads;
@@ -583,7 +587,7 @@ void gr_render_state_destroy(gr_render_state* s) {
                                s->tetrad[3], s->rays_count_in, s->rays_adaptive_count, s->render_data_count, s->cfg, s->dfg,
                                s->attempts, s->rays_in, s->rays_adaptive, s->render_data, s->termination_buffer, s->tile_order,
                                s->tile_cost, s->lattice_rays, s->guessed[0], s->guessed[1], s->pending_list, s->block_cost, s->block_cost_before, s->ref_cost[0], s->ref_cost[1], s->ref_order, s->ref_sort_work, s->parking_records, s->parking_words,
-                               s->traced_frame};
+                               s->traced_frame, s->accumulation};
     for (auto& slot : s->pre) {
         if (slot.stream) { (void)hipStreamSynchronize(slot.stream); (void)hipStreamDestroy(slot.stream); }
         if (slot.ready) (void)hipEventDestroy(slot.ready);
@@ -1645,6 +1649,76 @@ int gr_render_frame_yuv420p10(gr_render_state* s, gr_program* p, const gr_metric
     s->resolve_timed = false;
     return deliver_frame(DELIVER_YUV420P10, layout, "gr_render_frame_yuv420p10", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1,
                          bg2, bg_width, bg_height, bg_levels, out_yuv420p10, options);
+}
+
+// ---- motion-blurred frames (geodesic_hip_internal.h, "Motion-blurred frames") -------------------------------------------------------
+// One sub-frame of a shutter: the frame as render_traced_frame renders it, into the state's traced frame as deliver_frame does, and ONE
+// launch of gr_shutter_accumulate from there into the state's accumulation frame.  A sub-frame is a frame: nothing in frame_plan.cpp knows
+// of it, and consecutive sub-frames are consecutive frames of the state (tile history, look-ahead, still-camera reuse).  Everything that
+// needs no device is refused first; nothing is allocated for a call that is refused.
+int gr_render_subframe(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
+                       const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height, int bg_levels,
+                       float weight, int first, const gr_frame_options* options) {
+    if (!s || !p || !m || !camera || !bg1 || !bg2) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: null argument");
+    if (!std::isfinite(weight)) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: a weight that is not finite");
+    if (options && options->strip_count > 1)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: whole frames only (strip_count > 1); a share of a split frame is not accumulated");
+    // (the three refusals above need no device and look at no object; without a device the answer from here on is GR_ERROR_DEVICE, as
+    // the creation of every object this call takes would have been)
+    int devices = 0;
+    HIP_CHECK(hipGetDeviceCount(&devices));
+    if (!first && !s->accumulated)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: first = 0 on a state that holds no accumulation (a shutter's first sub-frame has first = 1)");
+    s->resolve_timed = false;
+    gr_frame_options opt;   // (as deliver_frame hands them on: a supersampled state's frame is this frame, options and all)
+    gr_frame_options_default(&opt);
+    if (options) opt = *options;
+    if (opt.block_rows > 0x7fffffff / s->supersample) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: block_rows");
+    opt.block_rows *= s->supersample;
+    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, s));   // (s: any non-NULL out)
+    HIP_CHECK(hipSetDevice(s->device));
+    if (!s->traced_frame) {   // a factor-1 state's first frame that does not go straight to the caller
+        HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
+        for (auto& ev : s->ev_resolve)
+            if (!ev) HIP_CHECK(hipEventCreate(&ev));
+    }
+    if (!s->accumulation) HIP_CHECK(hipMalloc(&s->accumulation, (size_t)s->out_width * s->out_height * 4 * sizeof(float)));
+    if (first) s->accumulated = 0;   // (a sub-frame that fails below leaves nothing to deliver)
+    GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
+                                 s->traced_frame, &opt));
+    const bool timed = opt.time_kernels == 1;
+    if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
+    GR_CHECK(gr_shutter_accumulate(p, stream, s->traced_frame, s->accumulation, s->out_width, s->out_height, s->supersample, weight, first));
+    if (timed) {
+        HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
+        s->resolve_timed = true;
+    }
+    s->accumulated++;
+    return GR_OK;
+}
+
+// The accumulation frame through one of the four existing kernels at factor 1 - the launch gr_render_frame* ends with, from another source.
+int gr_deliver_accumulated(gr_render_state* s, gr_program* p, void* stream, int format, int layout, void* out) {
+    if (!s || !p || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: null argument");
+    if (format != GR_FRAME_F32 && format != GR_FRAME_RGBA8 && format != GR_FRAME_YUV420 && format != GR_FRAME_YUV420P10)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_deliver_accumulated: unknown frame format " + std::to_string(format) +
+                                                            " (GR_FRAME_F32, GR_FRAME_RGBA8, GR_FRAME_YUV420 or GR_FRAME_YUV420P10)").c_str());
+    const bool video = format == GR_FRAME_YUV420 || format == GR_FRAME_YUV420P10;
+    if (video && layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: layout (GR_YUV420_I420 or GR_YUV420_NV12)");
+    if (format == GR_FRAME_YUV420 && (uintptr_t)out % 4)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: out must be aligned to 4 bytes for GR_FRAME_YUV420");
+    if (format == GR_FRAME_YUV420P10 && (uintptr_t)out % 8 && ((uintptr_t)out % 2 || s->out_width % 4 == 0))
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: out must be aligned to 8 bytes for GR_FRAME_YUV420P10 where the width is a "
+                                                           "multiple of 4, to 2 bytes otherwise");
+    if (!s->accumulated || !s->accumulation)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: the state holds no accumulation (gr_render_subframe first)");
+    HIP_CHECK(hipSetDevice(s->device));
+    const int w = s->out_width, h = s->out_height;
+    if (format == GR_FRAME_F32) return gr_resolve_supersampled(p, stream, s->accumulation, out, w, h, 1, h, 0, 1, 0);
+    if (format == GR_FRAME_RGBA8) return gr_present_rgba8(p, stream, s->accumulation, out, w, h, 1, h, 0, 1, 0);
+    if (format == GR_FRAME_YUV420) return gr_present_yuv420(p, stream, s->accumulation, out, w, h, 1, layout);
+    return gr_present_yuv420p10(p, stream, s->accumulation, out, w, h, 1, layout);
 }
 
 }  // extern "C"

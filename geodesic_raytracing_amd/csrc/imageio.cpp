@@ -390,4 +390,33 @@ int gr_y4m_close(gr_y4m* y) {
     return complete ? GR_OK : gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_y4m_close: " + path + " is incomplete (a write failed)").c_str());
 }
 
+// ---- the shutter of a motion-blurred frame: the host statement of one accumulation step (geodesic_hip_internal.h, "Motion-blurred frames";
+// kernels/shutter.hip's gr_shutter_accumulate is held to it at factor 1).  accum = [accum +] weight * frame, one fp32 multiply and one fp32
+// add per value, EACH ROUNDED: a fused multiply-add rounds once and gives other bits.  How the compiler is kept from contracting them: the
+// function is compiled with fp-contract=off whatever the command line says (the attribute below for GCC, which this library is built
+// with; the pragma for a clang build), and the product is a float object of its own.  The library's x86-64 baseline build has no fma
+// instruction to contract to either, but -march=native would: tests/test_shutter_abi.py holds it to a triple where the two roundings differ.
+#if defined(__clang__)
+#define GR_NO_CONTRACTION
+#pragma clang fp contract(off)
+#elif defined(__GNUC__)
+#define GR_NO_CONTRACTION __attribute__((optimize("fp-contract=off")))
+#else
+#define GR_NO_CONTRACTION
+#endif
+GR_NO_CONTRACTION int gr_accumulate_frame(float* accum, const float* frame, size_t count_floats, float weight, int first) {
+    if (!accum || !frame) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_accumulate_frame: null argument");
+    if (!std::isfinite(weight)) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_accumulate_frame: a weight that is not finite");
+    if (first) {
+        // (not 0 + weight * frame[i]: a weight of 1 hands every value through as it is, the sign of a zero included)
+        for (size_t i = 0; i < count_floats; i++) accum[i] = weight * frame[i];
+    } else {
+        for (size_t i = 0; i < count_floats; i++) {
+            const float product = weight * frame[i];
+            accum[i] = accum[i] + product;
+        }
+    }
+    return GR_OK;
+}
+
 }  // extern "C"

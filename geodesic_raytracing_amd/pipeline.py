@@ -444,6 +444,23 @@ class RenderState:
         rgb10_to_yuv420p10(frame_to_rgb10(...))'s of the float frame render() writes (a NaN gives code 0).  Whole frames only."""
         self.render(program, metric, camera, out_ptr, background, features, cfg_values, options, stream, yuv420=layout, bit_depth=10)
 
+    def render_subframe(self, program, metric, camera, weight, first, background=None, features=None, cfg_values=None, options=None, stream=None):
+        """One sub-frame of a shutter (gr_render_subframe): the frame render() would write for these arguments is rendered into the state's own
+        traced frame and added on the device, times `weight`, to an accumulation frame the state keeps: accum = weight * frame with `first`,
+        accum = accum + weight * frame otherwise (accumulate_frame says what that means, bit for bit).  The weights are the caller's and
+        are not normalised; `options` are render()'s, next_camera for the next sub-frame's pose included.  Whole frames only."""
+        features, arr, n, bg1, bg2, bw, bh, bl = _frame_arguments(metric, features, cfg_values, background)
+        options = ctypes.byref(options) if options is not None else None
+        check(lib.gr_render_subframe(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n,
+                                     bg1, bg2, bw, bh, bl, float(weight), int(bool(first)), options))
+
+    def deliver_accumulated(self, program, out_ptr, frame_format=FRAME_F32, layout=YUV420_I420, stream=None):
+        """The accumulation of the sub-frames since the last `first` one, delivered by one launch (gr_deliver_accumulated) into the device
+        pointer `out_ptr` as FRAME_F32 (float4[width*height]), FRAME_RGBA8 (what render_rgba8 would make of it), FRAME_YUV420 (render_yuv420;
+        yuv420_bytes, aligned to 4) or FRAME_YUV420P10 (render_yuv420p10; yuv420p10_bytes, aligned to 8 where the width is a multiple of 4) in
+        `layout`.  The accumulation stays: it can be delivered again in another format."""
+        check(lib.gr_deliver_accumulated(self.handle, program.handle, stream, int(frame_format), int(layout), out_ptr))
+
     def prepass_policy(self):
         """(frames rendered with a prepass, frames the policy rendered without, fraction of cells the last inspected prepass marked)"""
         a, b, f = ctypes.c_ulonglong(), ctypes.c_ulonglong(), c_float()
@@ -589,6 +606,18 @@ def rgba8_to_yuv420(pixels, layout=YUV420_I420):
     out = np.empty(yuv420_bytes(w, h), dtype=np.uint8)
     check(lib.gr_rgba8_to_yuv420(pixels.ctypes.data_as(c_void_p), w, h, int(layout), out.ctypes.data_as(c_void_p)))
     return out
+
+
+def accumulate_frame(accum, frame, weight, first):
+    """The host statement of one step of a shutter's accumulation (gr_accumulate_frame): float32 arrays of one shape, `accum` updated in
+    place and returned - with `first` accum = weight * frame, otherwise accum = accum + weight * frame; one float32 multiply and one
+    float32 add per value, each rounded (never a fused multiply-add).  What RenderState.render_subframe computes on the device, bit for
+    bit, of the frames render() delivers.  The weights are not normalised."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if not (isinstance(accum, np.ndarray) and accum.dtype == np.float32 and accum.flags.c_contiguous and accum.flags.writeable and accum.shape == frame.shape):
+        raise ValueError("accumulate_frame: accum is a writeable C-contiguous float32 array of the frame's shape")
+    check(lib.gr_accumulate_frame(accum.ctypes.data_as(c_void_p), frame.ctypes.data_as(c_void_p), frame.size, float(weight), int(bool(first))))
+    return accum
 
 
 def yuv420p10_bytes(width, height):

@@ -16,6 +16,8 @@
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --fps 30000/1001 --out pan.y4m
     # ... as a 10-bit master (C420p10: 16-bit little-endian words, 3 bytes a pixel come back) for a Main10 / AV1 / ProRes encode
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --bit-depth 10 --out pan10.y4m
+    # ... with motion blur: a 180-degree shutter (open for half the frame interval), every frame the average of 8 sub-frames, summed on the device
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --shutter 0.5 --out pan_blur.y4m
 """
 import argparse
 import ctypes
@@ -88,9 +90,49 @@ def camera_path(position, quat, position_to=None, quat_to=None, frames=1):
     return poses
 
 
+def shutter_times(frames, shutter, samples):
+    """When the sub-frames of a shutter are rendered, in frame numbers: a float64 array [frames, samples] whose entry [k, j] is
+    k + shutter * (j + 0.5) / samples.  The shutter of frame k opens at the frame's own time k and stays open for the fraction `shutter`
+    (0 < shutter <= 1; 0.5 is the 180-degree film shutter) of the frame interval; sub-frame j sits at the midpoint of the j-th of `samples`
+    equal parts of that.  The box weight of every sub-frame is np.float32(1) / np.float32(samples)."""
+    frames, samples, shutter = int(frames), int(samples), float(shutter)
+    if frames < 1 or samples < 1:
+        raise ValueError(f"shutter_times: {frames} frames of {samples} sub-frames (both at least 1)")
+    if not 0.0 < shutter <= 1.0:
+        raise ValueError(f"shutter_times: a shutter of {shutter!r} (the open fraction of the frame interval: above 0, at most 1)")
+    return np.array([[k + shutter * (j + 0.5) / samples for j in range(samples)] for k in range(frames)], dtype=np.float64)
+
+
+def camera_path_at(position, quat, position_to=None, quat_to=None, frames=1, times=(0.0,)):
+    """camera_path's poses at the frame numbers `times`, which need not be whole: u = t / (frames - 1) in camera_path's own expressions (the
+    position linear, the quaternion a normalised slerp along the shorter arc), so a whole t gives camera_path's pose exactly and u > 1
+    (the sub-frames of the last frame's shutter) continues the same line and the same arc.  Returns [(position, quat)], one per time."""
+    p0 = np.array(position if position is not None else gra.default_camera().position[:], dtype=np.float64)
+    q0 = np.array(quat if quat is not None else gra.default_camera().quat[:], dtype=np.float64)
+    p1 = p0 if position_to is None else np.array(position_to, dtype=np.float64)
+    q1 = q0 if quat_to is None else np.array(quat_to, dtype=np.float64)
+    if p0.shape != (4,) or p1.shape != (4,) or q0.shape != (4,) or q1.shape != (4,):
+        raise ValueError("camera_path_at: a position is t,x,y,z and a quaternion x,y,z,w")
+    if not np.linalg.norm(q0) > 0 or not np.linalg.norm(q1) > 0:
+        raise ValueError("camera_path_at: a quaternion of length zero")
+    q0, q1 = q0 / np.linalg.norm(q0), q1 / np.linalg.norm(q1)
+    if np.dot(q0, q1) < 0:
+        q1 = -q1
+    angle = np.arccos(min(1.0, float(np.dot(q0, q1))))
+    poses = []
+    for t in np.asarray(times, dtype=np.float64).ravel():
+        u = float(t) / (frames - 1) if frames > 1 else 0.0
+        if angle < 1e-6:
+            q = (1 - u) * q0 + u * q1
+        else:
+            q = (np.sin((1 - u) * angle) * q0 + np.sin(u * angle) * q1) / np.sin(angle)
+        poses.append(([float(v) for v in (1 - u) * p0 + u * p1], [float(v) for v in q / np.linalg.norm(q)]))
+    return poses
+
+
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
-           parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8):
+           parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
@@ -102,6 +144,10 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     yuv420p10le order (RenderState.render_yuv420p10), 3 bytes a pixel through pinned memory - the words
     pipeline.rgb10_to_yuv420p10(pipeline.frame_to_rgb10(...)) makes of the float frame.
     cameras: [(position, quat)] (camera_path) - a list of frames, one per pose, of a camera that rides no geodesic (not with geodesic_speed).
+    shutter_samples = T > 0 (motion blur): `cameras`, or `geodesic_times`, holds T entries per delivered frame, consecutive ones (shutter_times
+    and camera_path_at make them); every frame returned is the sum of its T sub-frames with the box weight np.float32(1) / np.float32(T),
+    accumulated on the device in linear light (RenderState.render_subframe: pipeline.accumulate_frame of the frames render() returns
+    without it, bit for bit) and delivered in the format asked for (RenderState.deliver_accumulated).  Fused path only (not with adaptive).
     mips: where the sky's mip slices are made - "host" (pack_background, all slices uploaded) or "device" (build_background: the image is
     uploaded and the slices are built there, the same bytes)."""
     if mips not in ("host", "device"):
@@ -110,6 +156,12 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
         raise ValueError(f"render: bit_depth={bit_depth!r} (8, or 10 with yuv420=True)")
     if cameras is not None and geodesic_speed is not None:
         raise ValueError("render: cameras (interpolated poses) and geodesic_speed (a camera on its geodesic) exclude each other")
+    shutter_samples = int(shutter_samples)
+    if shutter_samples:
+        moving = cameras if cameras is not None else geodesic_times if geodesic_speed is not None else None
+        if shutter_samples < 0 or adaptive or moving is None or len(moving) == 0 or len(moving) % shutter_samples:
+            raise ValueError(f"render: shutter_samples={shutter_samples} needs the fused path (no adaptive) and cameras or geodesic_times with that many "
+                             "entries per frame")
     metric = gra.Metric(metric_name, scripts or os.path.join(HERE, "scripts"))
     feats = metric.features(adaptive_sampling=int(adaptive), redshift=int(redshift), field_of_view=fov, universe_size=universe)
     cfg_values = metric.cfg_values(**(cfg or {}))
@@ -130,7 +182,27 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
     bg = (dbg.ptr, rgba.shape[1], rgba.shape[0], levels)
 
+    def fetch():
+        pinned.download_async(None, out.ptr, out_bytes)   # the frame's stream: copies queue behind its launches
+        gra.check(gra.lib.gr_stream_synchronize(None))
+        if deep:
+            return pinned.view(np.uint16, (out_bytes // 2,)).copy()
+        return pinned.view(np.uint8, (out_bytes,) if yuv420 else (height, width, 4)).copy()
+
+    weight = np.float32(1) / np.float32(shutter_samples) if shutter_samples else None
+    subframe = [0]   # sub-frames of the current shutter rendered so far
+
     def one_frame(options, cam=cam):
+        if shutter_samples:   # a sub-frame: accumulated on the device; the last one of a shutter delivers
+            state.render_subframe(program, metric, cam, weight, subframe[0] == 0, bg, feats, cfg_values, options)
+            subframe[0] = (subframe[0] + 1) % shutter_samples
+            if subframe[0]:
+                return None
+            state.deliver_accumulated(program, out.ptr, gra.FRAME_YUV420P10 if deep else gra.FRAME_YUV420 if yuv420 else gra.FRAME_RGBA8 if rgba8 else gra.FRAME_F32)
+            if pinned is not None:
+                return fetch()
+            state.synchronize()
+            return out.to_numpy(np.float32, (height, width, 4))
         if deep:
             state.render_yuv420p10(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
         elif yuv420:
@@ -141,13 +213,13 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
             state.render(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
             state.synchronize()
             return out.to_numpy(np.float32, (height, width, 4))
-        pinned.download_async(None, out.ptr, out_bytes)   # the frame's stream: copies queue behind its launches
-        gra.check(gra.lib.gr_stream_synchronize(None))
-        if deep:
-            return pinned.view(np.uint16, (out_bytes // 2,)).copy()
-        return pinned.view(np.uint8, (out_bytes,) if yuv420 else (height, width, 4)).copy()
+        return fetch()
 
     def frames_of_the_call():
+        made = rendered()
+        return [frame for frame in made if frame is not None] if shutter_samples else made   # (a sub-frame that delivers nothing gives None)
+
+    def rendered():
         if cameras is not None:
             return [one_frame(gra.frame_options(mode=mode), gra.default_camera(position, quat)) for position, quat in cameras]
         if geodesic_speed is None:
@@ -261,6 +333,11 @@ def main(argv=None):
     ap.add_argument("--fps", default="24", help="frame rate of a .y4m file: N or N/D (24; 30000/1001)")
     ap.add_argument("--bit-depth", type=int, choices=[8, 10], default=8, help="bits a sample of a .y4m file: 8 (C420jpeg, 1.5 bytes a pixel) or 10 "
                     "(C420p10: 16-bit little-endian words, 3 bytes a pixel - the master for a 10-bit encode).  Only with --out NAME.y4m")
+    ap.add_argument("--shutter", type=float, default=None, help="motion blur: the fraction of the frame interval the shutter is open, above 0 and at "
+                    "most 1 (0.5: the 180-degree film shutter; default: no shutter, every frame one instantaneous pose).  Every frame is the "
+                    "average of --shutter-samples sub-frames rendered at equally spaced moments of that interval and summed on the device in "
+                    "linear light.  Needs a camera that moves: --camera-to / --quat-to or --geodesic-speed")
+    ap.add_argument("--shutter-samples", type=int, default=None, help="sub-frames a frame of --shutter, 2 ... 64 (8)")
     ap.add_argument("--out", required=True, help="NAME.png: one PNG, or NAME_000.png ... for a sequence.  NAME.y4m: all frames in one uncompressed "
                     "YUV4MPEG2 file of 8-bit BT.709 Y'CbCr 4:2:0 frames, converted on the device")
     a = ap.parse_args(argv)
@@ -271,16 +348,31 @@ def main(argv=None):
         ap.error(f"--fps: {e}")
     if a.bit_depth != 8 and not video:
         ap.error("--bit-depth 10 is a depth of video frames: it needs --out NAME.y4m (a PNG is 8-bit sRGB)")
+    if a.shutter_samples is not None and a.shutter is None:
+        ap.error("--shutter-samples without --shutter: the sub-frames are those of a shutter; give its open fraction, e.g. --shutter 0.5")
+    if a.shutter is not None:
+        if not 0.0 < a.shutter <= 1.0:
+            ap.error(f"--shutter {a.shutter}: the fraction of the frame interval the shutter is open, above 0 and at most 1")
+        if a.shutter_samples is not None and not 2 <= a.shutter_samples <= 64:
+            ap.error(f"--shutter-samples {a.shutter_samples}: 2 to 64 sub-frames a frame")
+        if a.devices is not None:
+            ap.error("--shutter with --devices: a share of a split frame is not accumulated; render the blurred sequence on one device")
+        if a.adaptive:
+            ap.error("--shutter with --adaptive: the sub-frames of a shutter are rendered on the fused path, adaptive sampling runs in reference mode")
+        if not (a.camera_to or a.quat_to or a.geodesic_speed):
+            ap.error("--shutter on a camera that does not move: there is no motion to blur; give --camera-to / --quat-to or --geodesic-speed")
     if video and a.devices is not None:
         ap.error("--out NAME.y4m with --devices: a split frame travels as float4 or RGBA8, not as 4:2:0 planes; render the video on one device")
     if (a.camera_to or a.quat_to) and a.geodesic_speed:
         ap.error("--camera-to / --quat-to with --geodesic-speed: the camera either follows the interpolated poses or rides its geodesic")
     if (a.camera_to or a.quat_to) and a.devices is not None:
         ap.error("--camera-to / --quat-to with --devices: a split sequence renders one camera")
+    samples = (a.shutter_samples or 8) if a.shutter is not None else 0
     w, h = (int(v) for v in a.size.lower().split("x"))
     cfg = {k: float(v) for k, v in (kv.split("=") for kv in a.cfg)}
     speed = [float(v) for v in a.geodesic_speed.split(",")] if a.geodesic_speed else None
     times = [a.geodesic_time + i * a.geodesic_dt for i in range(max(a.frames, 1))]
+    moments = shutter_times(max(a.frames, 1), a.shutter, samples).ravel() if samples else None   # frame numbers, `samples` a frame
     write = write_rgba8_png if a.encode == "device" else write_frame_png
     if a.devices is not None:
         try:
@@ -306,14 +398,15 @@ def main(argv=None):
     cameras = None
     if a.camera_to or a.quat_to:
         try:
-            cameras = camera_path(position, quat, [float(v) for v in a.camera_to.split(",")] if a.camera_to else None,
-                                  [float(v) for v in a.quat_to.split(",")] if a.quat_to else None, max(a.frames, 1))
+            ends = ([float(v) for v in a.camera_to.split(",")] if a.camera_to else None, [float(v) for v in a.quat_to.split(",")] if a.quat_to else None)
+            cameras = camera_path_at(position, quat, *ends, max(a.frames, 1), moments) if samples else camera_path(position, quat, *ends, max(a.frames, 1))
         except ValueError as e:
             ap.error(f"--camera-to / --quat-to: {e}")
     result = render(a.metric, w, h, a.scripts, cfg, position, quat, a.redshift, a.adaptive,
                     read_png(a.background) if a.background else None, a.device, a.fov, a.universe, geodesic_speed=speed,
-                    geodesic_times=times, parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
-                    rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth)
+                    geodesic_times=[a.geodesic_time + float(t) * a.geodesic_dt for t in moments] if samples else times,
+                    parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
+                    rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples)
     if speed is None and cameras is None:
         result = [result]
     if video:

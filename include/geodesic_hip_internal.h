@@ -202,6 +202,55 @@ int gr_render_frame_yuv420p10(gr_render_state* s, gr_program* p, const gr_metric
                               const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
                               int bg_width, int bg_height, int bg_levels, void* out_yuv420p10, int layout, const gr_frame_options* options);
 
+/* ---- Motion-blurred frames --------------------------------------------------------------------------------------------------------
+ * A shutter: a delivered frame is the weighted sum of T sub-frames rendered at T poses inside the frame's shutter interval, summed in linear
+ * light (float4, before any encode) on the device; only the finished frame leaves it, in one of the four formats a plain frame leaves in.
+ * (Declared here and not in geodesic_hip.h only because the contract header keeps to 80 names and 350 lines; all of this is public.)
+ *
+ * Definition, per float of the frame (all four channels, alpha included), with w the sub-frame's weight and r its resolved value - the
+ * value gr_render_frame would have delivered for that pose, box average of a supersampled state included:
+ *   the first sub-frame:   accum = w * r                one fp32 multiply, rounded to nearest even
+ *   every later one:       accum = accum + (w * r)      that multiply, rounded, then one fp32 add, rounded - NEVER a fused multiply-add
+ * in the order the sub-frames are submitted.  The first is not 0 + w * r: with w == 1.0f every value passes bit for bit, the sign of a zero
+ * included.  NaN and infinity propagate as IEEE arithmetic has them (0 * inf is a NaN).  The library does NOT normalise weights: the caller's
+ * weights are expected to sum to 1 (box weights: w = 1.0f / (float)T for every sub-frame; the sum of T of them need not be exactly 1).
+ * The delivered frame is the encode of the final accum by the format's own definition: the float4 itself, gr_frame_to_rgba8,
+ * gr_rgba8_to_yuv420(gr_frame_to_rgba8), or gr_rgb10_to_yuv420p10(gr_frame_to_rgb10) - a NaN's byte or code is 0 on the device. */
+/* The host statement of one accumulation step over count_floats floats: with first != 0 accum[i] = weight * frame[i] (accum is not read),
+ * otherwise accum[i] = accum[i] + weight * frame[i], as defined above; compiled so that the product and the sum are not contracted.
+ * Refuses, with GR_ERROR_INVALID_ARGUMENT and a message that names it, a NULL accum or frame and a weight that is NaN or infinite;
+ * count_floats == 0 does nothing.  accum and frame may be the same array. */
+int gr_accumulate_frame(float* accum, const float* frame, size_t count_floats, float weight, int first);
+/* The formats of gr_deliver_accumulated that GR_FRAME_F32 = 0 and GR_FRAME_RGBA8 = 1 (geodesic_hip.h) do not name; gr_render_frame_tiled_as
+ * takes neither. */
+enum { GR_FRAME_YUV420 = 2, GR_FRAME_YUV420P10 = 3 };
+/* One accumulation step on the device (kernels/shutter.hip, set-up module: IEEE arithmetic, no contraction): src is a traced sub-frame,
+ * float4 of width*factor x height*factor; accum is float4 of width x height; per pixel r = the value gr_resolve_supersampled would write
+ * (the same function in the same compilation; factor 1..4, 1 takes src as it is) and accum = [accum +] weight * r as defined above.
+ * With first != 0 accum is written and not read: no memset in front of a shutter, and whatever accum held - a NaN included - is gone.
+ * Whole frames only.  Refused before any device call: a NULL (the program included), src == accum, a factor outside 1..4, a size below 1
+ * or with more than 2^31 - 1 source pixels or more than 262 140 rows, a weight that is not finite. */
+int gr_shutter_accumulate(gr_program* p, void* stream, const void* src, void* accum, int width, int height, int factor, float weight, int first);
+/* One sub-frame of a shutter: renders the frame gr_render_frame would render for these arguments (same options: geodesic / geodesic_time,
+ * next_camera ..., tuning - consecutive sub-frames are consecutive frames of the state, and a caller may announce the next sub-frame's camera)
+ * into the state's traced frame and adds it with ONE gr_shutter_accumulate launch to an accumulation frame the state owns (float4, the
+ * state's output size; allocated with the first sub-frame that is not refused, freed with the state).  first != 0 starts a new accumulation.
+ * With time_kernels = 1 the accumulate launch is what gr_render_state_resolve_ms reports, beside the GR_STAGE_* times of the sub-frame.
+ * Refused with GR_ERROR_INVALID_ARGUMENT and a message that names it - these three before any device call and before any object is looked
+ * at: a NULL state, program, metric, camera or background; a weight that is not finite; options->strip_count > 1 (whole frames only) - and:
+ * first == 0 on a state that holds no accumulation (none was started, or the last one's first sub-frame failed); what gr_render_frame
+ * refuses.  Without a device: GR_ERROR_DEVICE. */
+int gr_render_subframe(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
+                       const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height, int bg_levels,
+                       float weight, int first, const gr_frame_options* options);
+/* The state's accumulation frame in `format`, by ONE launch of the format's existing kernel at factor 1 (gr_resolve_supersampled,
+ * gr_present_rgba8, gr_present_yuv420, gr_present_yuv420p10): out (device) holds width x height float4 (GR_FRAME_F32), RGBA8 pixels
+ * (GR_FRAME_RGBA8), gr_yuv420_bytes (GR_FRAME_YUV420) or gr_yuv420p10_bytes (GR_FRAME_YUV420P10) in `layout`, which the first two formats
+ * ignore.  The accumulation stays as it is: it may be delivered again in another format, or added to.  Refused, with a message that names
+ * it: a NULL; an unknown format; for the video formats an unknown layout, out not aligned to 4 bytes (8-bit) or to 8 bytes where the
+ * state's width is a multiple of 4 and 2 bytes otherwise (10-bit); a state that holds no accumulation. */
+int gr_deliver_accumulated(gr_render_state* s, gr_program* p, void* stream, int format, int layout, void* out);
+
 /* ---- fused MI355X path (no reference counterpart) ------------------------------------------- */
 
 /* Prepass termination flags from one fused trace at prepass resolution (replaces the sequence
