@@ -123,6 +123,9 @@ class Transport(ctypes.Structure):
 MODE_REFERENCE, MODE_FUSED = 0, 1
 FRAME_F32, FRAME_RGBA8 = 0, 1
 FRAME_YUV420, FRAME_YUV420P10 = 2, 3   # GR_FRAME_YUV420 / _YUV420P10: the video formats of gr_deliver_accumulated (include/geodesic_hip_internal.h)
+FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN, FILTER_MITCHELL = 0, 1, 2, 3   # GR_FILTER_*: the reconstruction filter of a state's frames (include/geodesic_hip_internal.h, "Filtered frames")
+FILTER_NAMES = {"box": FILTER_BOX, "tent": FILTER_TENT, "gaussian": FILTER_GAUSSIAN, "mitchell": FILTER_MITCHELL}
+FILTER_MAX_TAPS = 16
 YUV420_I420, YUV420_NV12 = 0, 1   # GR_YUV420_*: the layouts of an 8-bit Y'CbCr 4:2:0 frame (include/geodesic_hip.h, "video frames")
 EVAL_METRIC_TENSOR, EVAL_METRIC_DERIVATIVES, EVAL_ACCELERATION, EVAL_TO_POLAR, EVAL_FROM_POLAR, EVAL_ORIGIN_DISTANCE = range(6)
 (STAGE_CAMERA, STAGE_PREPASS, STAGE_INIT, STAGE_TRACE, STAGE_RENDER_DATA, STAGE_ADAPTIVE, STAGE_RENDER) = range(7)
@@ -330,6 +333,11 @@ _SIGNATURES = {
                                    ctypes.POINTER(c_float), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
                                    ctypes.POINTER(FrameOptions)]),
     "gr_deliver_accumulated": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gr_filter_taps": (c_int, [c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_int)]),
+    "gr_filter_frame": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "gr_resolve_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
+    "gr_render_state_set_filter": (c_int, [c_void_p, c_int]),
+    "gr_render_state_filter": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():
@@ -352,4 +360,5 @@ def check(rc):
 
 from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, build_background,  # noqa: E402,F401
                        default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background, rgba8_to_yuv420,
-                       yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes, accumulate_frame)
+                       yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes, accumulate_frame, filter_taps,
+                       filter_frame)

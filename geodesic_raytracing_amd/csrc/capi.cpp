@@ -75,11 +75,11 @@ const char* const KERNEL_NAMES[] = {
     "gr_do_generic_rays", "gr_calculate_singularities", "gr_calculate_render_data",
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
-    "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate"};
+    "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_COUNT
 };
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
@@ -88,7 +88,7 @@ enum KernelId {
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
-           k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE;
+           k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE || k == K_RESOLVE_FILTERED;
 }
 
 namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files
@@ -1203,6 +1203,26 @@ int gr_shutter_accumulate(gr_program* p, void* stream, const void* src, void* ac
     first = first ? 1 : 0;
     void* args[] = {&src, &accum, &width, &height, &factor, &weight, &first};
     return launch(p, K_SHUTTER_ACCUMULATE, stream, blocks(width, 64), gy, 64, 4, args);
+}
+
+// a filtered frame (kernels/filter.hip; geodesic_hip_internal.h, "Filtered frames"): one workgroup of 256 lanes per tile of 32 x 8 output
+// pixels (the kernel's GR_FILTER_TX x GR_FILTER_TY), the taps - host memory - copied into the argument block.  gr_filter_frame's refusals
+// (imageio.cpp) and the grid's, all before the first device call.
+extern "C" const char* gr_internal_filter_table_error(int factor, const float* taps, int count);
+int gr_resolve_filtered(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, const float* taps, int count) {
+    const std::string who = "gr_resolve_filtered: ";
+    if (!src || !dst || !taps) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required buffer is NULL");
+    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
+    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
+    if (const char* wrong = gr_internal_filter_table_error(factor, taps, count)) return fail(GR_ERROR_INVALID_ARGUMENT, who + wrong);
+    if (src == dst) return fail(GR_ERROR_INVALID_ARGUMENT, who + "src and dst are one buffer");
+    if ((long long)width * factor * height * factor > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, who + "more than 2^31 - 1 source pixels");
+    const unsigned gy = blocks(height, 8);
+    if (gy > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a frame of " + std::to_string(height) + " rows does not fit the grid");
+    struct { float tap[GR_FILTER_MAX_TAPS]; } table = {};
+    std::copy(taps, taps + count, table.tap);
+    void* args[] = {&src, &dst, &width, &height, &factor, &count, &table};
+    return launch(p, K_RESOLVE_FILTERED, stream, blocks(width, 32), gy, 256, 1, args);
 }
 
 // ---- the sky's mip slices on the device (kernels/background.hip) ------------------------------------

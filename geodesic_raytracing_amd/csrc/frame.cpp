@@ -86,6 +86,10 @@ struct gr_render_state {
     // sub-frame; accumulated: sub-frames in it since the last one with `first` (0: nothing to add to, nothing to deliver)
     void* accumulation = nullptr;
     unsigned long long accumulated = 0;
+    // gr_render_state_set_filter: GR_FILTER_BOX is the box average of resolve.hip, launch for launch as before; any other filter goes
+    // through gr_resolve_filtered into filtered_frame (float4[out_width * out_height], allocated with the first frame that is not refused)
+    int filter = GR_FILTER_BOX;
+    void* filtered_frame = nullptr;
     hipEvent_t ev_resolve[2] = {};   // time_kernels = 1: around the resolve launch (gr_render_state_resolve_ms)
     bool resolve_timed = false;
     upload_ring uploads;
@@ -569,6 +573,21 @@ int gr_render_state_supersample(const gr_render_state* s, int* factor, int* trac
     return GR_OK;
 }
 
+int gr_render_state_set_filter(gr_render_state* s, int filter) {
+    if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_filter: null render state");
+    if (filter != GR_FILTER_BOX && filter != GR_FILTER_TENT && filter != GR_FILTER_GAUSSIAN && filter != GR_FILTER_MITCHELL)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_render_state_set_filter: unknown filter " + std::to_string(filter) +
+                                                            " (GR_FILTER_BOX, GR_FILTER_TENT, GR_FILTER_GAUSSIAN or GR_FILTER_MITCHELL)").c_str());
+    s->filter = filter;
+    return GR_OK;
+}
+
+int gr_render_state_filter(const gr_render_state* s, int* filter) {
+    if (!s || !filter) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_filter: null argument");
+    *filter = s->filter;
+    return GR_OK;
+}
+
 int gr_render_state_resolve_ms(gr_render_state* s, float* ms) {
     if (!s || !ms) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
     *ms = 0;
@@ -587,7 +606,7 @@ void gr_render_state_destroy(gr_render_state* s) {
                                s->tetrad[3], s->rays_count_in, s->rays_adaptive_count, s->render_data_count, s->cfg, s->dfg,
                                s->attempts, s->rays_in, s->rays_adaptive, s->render_data, s->termination_buffer, s->tile_order,
                                s->tile_cost, s->lattice_rays, s->guessed[0], s->guessed[1], s->pending_list, s->block_cost, s->block_cost_before, s->ref_cost[0], s->ref_cost[1], s->ref_order, s->ref_sort_work, s->parking_records, s->parking_words,
-                               s->traced_frame, s->accumulation};
+                               s->traced_frame, s->accumulation, s->filtered_frame};
     for (auto& slot : s->pre) {
         if (slot.stream) { (void)hipStreamSynchronize(slot.stream); (void)hipStreamDestroy(slot.stream); }
         if (slot.ready) (void)hipEventDestroy(slot.ready);
@@ -1557,6 +1576,13 @@ static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metri
 // a split frame is traced in blocks of factor x as many rows, so that they cover the rows its output blocks average.  `name`: the entry
 // point's, for its refusals.
 enum delivery { DELIVER_FLOAT4, DELIVER_RGBA8, DELIVER_YUV420, DELIVER_YUV420P10 };
+// the frame a state with a filter resolves into (geodesic_hip_internal.h, "Filtered frames"): allocated once, freed with the state
+static int allocate_filtered_frame(gr_render_state* s) {
+    if (s->filtered_frame) return GR_OK;
+    HIP_CHECK(hipSetDevice(s->device));
+    HIP_CHECK(hipMalloc(&s->filtered_frame, (size_t)s->out_width * s->out_height * 4 * sizeof(float)));
+    return GR_OK;
+}
 static int deliver_frame(delivery what, int layout, const char* name, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream,
                          const gr_camera* camera, const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1,
                          const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* options) {
@@ -1566,12 +1592,22 @@ static int deliver_frame(delivery what, int layout, const char* name, gr_render_
     const int factor = s->supersample, block_rows = opt.block_rows;
     if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": block_rows").c_str());
     opt.block_rows *= factor;
+    const bool filtered = s->filter != GR_FILTER_BOX;
+    if (filtered && opt.strip_count > 1)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": a state with a filter renders whole frames only (strip_count > 1): a filter "
+                                                                                "wider than a pixel reads across strip borders").c_str());
     GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out));
     if (!s->traced_frame) {   // a factor-1 state's first encoded frame (nothing is allocated for a call that is refused)
         HIP_CHECK(hipSetDevice(s->device));
         HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
         for (auto& ev : s->ev_resolve)
             if (!ev) HIP_CHECK(hipEventCreate(&ev));
+    }
+    float taps[GR_FILTER_MAX_TAPS];
+    int tap_count = 0;
+    if (filtered) {
+        GR_CHECK(gr_filter_taps(s->filter, factor, taps, &tap_count));
+        GR_CHECK(allocate_filtered_frame(s));
     }
     GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
                                  s->traced_frame, &opt));
@@ -1580,7 +1616,18 @@ static int deliver_frame(delivery what, int layout, const char* name, gr_render_
               compact_out = strips ? opt.compact_out : 0;
     const bool timed = opt.time_kernels == 1;
     if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
-    if (what == DELIVER_FLOAT4)
+    if (filtered) {
+        // the filtered frame - straight into the caller's memory where that is float4 - and from it the format's own kernel at factor 1,
+        // as gr_deliver_accumulated runs it from the accumulation frame
+        const int w = s->out_width, h = s->out_height;
+        GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, what == DELIVER_FLOAT4 ? out : s->filtered_frame, w, h, factor, taps, tap_count));
+        if (what == DELIVER_RGBA8)
+            GR_CHECK(gr_present_rgba8(p, stream, s->filtered_frame, out, w, h, 1, h, 0, 1, 0));
+        else if (what == DELIVER_YUV420)
+            GR_CHECK(gr_present_yuv420(p, stream, s->filtered_frame, out, w, h, 1, layout));
+        else if (what == DELIVER_YUV420P10)
+            GR_CHECK(gr_present_yuv420p10(p, stream, s->filtered_frame, out, w, h, 1, layout));
+    } else if (what == DELIVER_FLOAT4)
         GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, rows, rank, count, compact_out));
     else if (what == DELIVER_RGBA8)
         GR_CHECK(gr_present_rgba8(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, rows, rank, count, compact_out));
@@ -1600,7 +1647,7 @@ int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void*
                     int bg_levels, void* out, const gr_frame_options* options) {
     if (s) s->resolve_timed = false;
     // (out == NULL stops after the records: nothing was shaded, nothing to resolve)
-    if (!s || s->supersample == 1 || !out)
+    if (!s || (s->supersample == 1 && s->filter == GR_FILTER_BOX) || !out)
         return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out, options);
     return deliver_frame(DELIVER_FLOAT4, 0, "gr_render_frame", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width,
                          bg_height, bg_levels, out, options);
@@ -1683,12 +1730,23 @@ int gr_render_subframe(gr_render_state* s, gr_program* p, const gr_metric* m, vo
             if (!ev) HIP_CHECK(hipEventCreate(&ev));
     }
     if (!s->accumulation) HIP_CHECK(hipMalloc(&s->accumulation, (size_t)s->out_width * s->out_height * 4 * sizeof(float)));
+    const bool filtered = s->filter != GR_FILTER_BOX;
+    float taps[GR_FILTER_MAX_TAPS];
+    int tap_count = 0;
+    if (filtered) {
+        GR_CHECK(gr_filter_taps(s->filter, s->supersample, taps, &tap_count));
+        GR_CHECK(allocate_filtered_frame(s));
+    }
     if (first) s->accumulated = 0;   // (a sub-frame that fails below leaves nothing to deliver)
     GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
                                  s->traced_frame, &opt));
     const bool timed = opt.time_kernels == 1;
     if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
-    GR_CHECK(gr_shutter_accumulate(p, stream, s->traced_frame, s->accumulation, s->out_width, s->out_height, s->supersample, weight, first));
+    if (filtered) {   // the filtered frame, accumulated from there at factor 1
+        GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, s->filtered_frame, s->out_width, s->out_height, s->supersample, taps, tap_count));
+        GR_CHECK(gr_shutter_accumulate(p, stream, s->filtered_frame, s->accumulation, s->out_width, s->out_height, 1, weight, first));
+    } else
+        GR_CHECK(gr_shutter_accumulate(p, stream, s->traced_frame, s->accumulation, s->out_width, s->out_height, s->supersample, weight, first));
     if (timed) {
         HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
         s->resolve_timed = true;

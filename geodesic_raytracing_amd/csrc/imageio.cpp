@@ -419,4 +419,93 @@ GR_NO_CONTRACTION int gr_accumulate_frame(float* accum, const float* frame, size
     return GR_OK;
 }
 
+// ---- separable reconstruction filters of a supersampled frame: the host statement (geodesic_hip_internal.h, "Filtered frames";
+// kernels/filter.hip's gr_resolve_filtered is held to gr_filter_frame bit for bit).
+// The taps of the named filters: k(d) in double from |d|, normalised by their sum in double (ascending t), each rounded to fp32 once; not
+// renormalised after rounding.
+int gr_filter_taps(int filter, int factor, float taps[GR_FILTER_MAX_TAPS], int* count) {
+    if (!taps || !count) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_filter_taps: null argument");
+    if (factor < 1 || factor > 4) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_filter_taps: factor " + std::to_string(factor) + " (1 to 4)").c_str());
+    if (filter == GR_FILTER_BOX)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_filter_taps: GR_FILTER_BOX has no table: the box average of a pixel's own samples is "
+                                                           "gr_resolve_supersampled");
+    if (filter != GR_FILTER_TENT && filter != GR_FILTER_GAUSSIAN && filter != GR_FILTER_MITCHELL)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_filter_taps: unknown filter " + std::to_string(filter) +
+                                                            " (GR_FILTER_TENT, GR_FILTER_GAUSSIAN or GR_FILTER_MITCHELL)").c_str());
+    const int radius = filter == GR_FILTER_TENT ? 1 : 2;
+    const int n = 2 * radius * factor - (factor % 2);   // the taps with |d_t| < radius
+    double k[GR_FILTER_MAX_TAPS], sum = 0.0;
+    for (int t = 0; t < n; t++) {
+        const double d = std::fabs((t + 0.5 - n / 2.0) / factor);
+        if (filter == GR_FILTER_TENT) {
+            k[t] = 1.0 - d;
+        } else if (filter == GR_FILTER_GAUSSIAN) {
+            k[t] = std::exp(-2.0 * d * d) - std::exp(-8.0);
+        } else {
+            const double B = 1.0 / 3.0, C = 1.0 / 3.0;
+            k[t] = d < 1.0 ? ((12.0 - 9.0 * B - 6.0 * C) * d * d * d + (-18.0 + 12.0 * B + 6.0 * C) * d * d + (6.0 - 2.0 * B)) / 6.0
+                           : ((-B - 6.0 * C) * d * d * d + (6.0 * B + 30.0 * C) * d * d + (-12.0 * B - 48.0 * C) * d + (8.0 * B + 24.0 * C)) / 6.0;
+        }
+        sum += k[t];
+    }
+    for (int t = 0; t < n; t++) taps[t] = (float)(k[t] / sum);
+    *count = n;
+    return GR_OK;
+}
+
+// what gr_filter_frame and the launcher gr_resolve_filtered (capi.cpp) both refuse about a table; NULL: nothing wrong
+extern "C" const char* gr_internal_filter_table_error(int factor, const float* taps, int count) {
+    if (factor < 1 || factor > 4) return "a factor outside 1 to 4";
+    if (count < 1 || count > GR_FILTER_MAX_TAPS) return "a count of taps outside 1 to 16";
+    if ((count - factor) % 2) return "a count of taps of the wrong parity (count = factor mod 2: the table is centred on the pixel)";
+    for (int t = 0; t < count; t++)
+        if (!std::isfinite(taps[t])) return "a tap that is not finite";
+    return nullptr;
+}
+
+// The rows pass into an intermediate of width x (height * factor) float4, rounded to fp32, then the columns pass; every product a float
+// object of its own and the function compiled without contraction, as gr_accumulate_frame is.
+GR_NO_CONTRACTION int gr_filter_frame(const float* src, int width, int height, int factor, const float* taps, int count, float* dst) {
+    const std::string who = "gr_filter_frame: ";
+    if (!src || !taps || !dst) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "null argument").c_str());
+    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "a size below 1").c_str());
+    if (const char* wrong = gr_internal_filter_table_error(factor, taps, count)) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + wrong).c_str());
+    if (src == dst) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "src and dst are one buffer").c_str());
+    const long long sw = (long long)width * factor, sh = (long long)height * factor;
+    const long long first = (factor - count) / 2;   // (even: exact)
+    std::vector<float> rows;
+    try {
+        rows.resize((size_t)sh * (size_t)width * 4);
+    } catch (const std::exception&) {
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "no memory for the intermediate frame").c_str());
+    }
+    for (long long y = 0; y < sh; y++) {
+        for (long long X = 0; X < width; X++) {
+            float* h = &rows[((size_t)y * width + X) * 4];
+            for (int t = 0; t < count; t++) {
+                const long long cx = std::min(std::max(X * factor + first + t, 0ll), sw - 1);
+                const float* s = src + ((size_t)y * sw + cx) * 4;
+                for (int c = 0; c < 4; c++) {
+                    const float product = taps[t] * s[c];
+                    h[c] = t ? h[c] + product : product;
+                }
+            }
+        }
+    }
+    for (long long Y = 0; Y < height; Y++) {
+        for (long long X = 0; X < width; X++) {
+            float* o = dst + ((size_t)Y * width + X) * 4;
+            for (int t = 0; t < count; t++) {
+                const long long cy = std::min(std::max(Y * factor + first + t, 0ll), sh - 1);
+                const float* h = &rows[((size_t)cy * width + X) * 4];
+                for (int c = 0; c < 4; c++) {
+                    const float product = taps[t] * h[c];
+                    o[c] = t ? o[c] + product : product;
+                }
+            }
+        }
+    }
+    return GR_OK;
+}
+
 }  // extern "C"

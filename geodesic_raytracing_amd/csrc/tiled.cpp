@@ -570,6 +570,12 @@ int gr_render_frame_tiled_as(gr_tiled* t, gr_render_state* s, gr_program* p, con
     if (t->transport == GR_TRANSPORT_PEER && !frame_on_root) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "peer transport: every participant is given the root's frame buffer");
     if (!s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
     if (t->device < 0) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "this participant was created without a device (schedule tests): nothing to render with");
+    {   // (a filter wider than a pixel reads across strip borders: halo rows and their exchange are a change of their own)
+        int filter = GR_FILTER_BOX;
+        gr_render_state_filter(s, &filter);
+        if (filter != GR_FILTER_BOX)
+            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled_as: a render state with a filter (gr_render_state_set_filter) renders whole frames only; a split frame takes GR_FILTER_BOX");
+    }
     {   // (the staging buffers and the blocks' places in the root's frame are those of the participant's frame size: the size of the
         // state's frames, which a supersampled state traces at factor x that)
         int factor = 1, tw = 0, th = 0;
@@ -628,8 +634,11 @@ int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const 
                           const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
                           int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation) {
     if (!t || !s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
-    int factor = 1;
+    int factor = 1, filter = GR_FILTER_BOX;
     gr_render_state_supersample(s, &factor, nullptr, nullptr);
+    gr_render_state_filter(s, &filter);
+    if (filter != GR_FILTER_BOX)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a render state with a filter (gr_render_state_set_filter) renders whole frames only; a split frame takes GR_FILTER_BOX");
     if (factor != 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a supersampled render state (gr_render_state_create_supersampled) renders its split frames through gr_render_frame_tiled_as; this entry point takes a state of factor 1");
     return gr_render_frame_tiled_as(t, s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
                                     frame_on_root, options, rotation, GR_FRAME_F32);

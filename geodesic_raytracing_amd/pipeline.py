@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from . import (Camera, Features, FrameOptions, FRAME_F32, FRAME_RGBA8, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
+from . import (Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
                c_size_t, c_void_p, check, lib)
 
 LIGHTRAY_DTYPE = np.dtype([("position", "<f4", 4), ("velocity", "<f4", 4), ("initial_quat", "<f4", 4),
@@ -384,10 +384,12 @@ class PinnedBuffer:
 class RenderState:
     """Per-frame device buffers + the frame sequence (render_state.hpp:97-197, main.cpp:2244-2526)."""
 
-    def __init__(self, width, height, device=0, supersample=1):
+    def __init__(self, width, height, device=0, supersample=1, filter=FILTER_BOX):
         """supersample = f > 1 (gr_render_state_create_supersampled; 2, 3 or 4): frames are still width x height, traced at f x that per
         axis and box-averaged on the device (box_resolve says what that means).  Everything else about the state - buffer(), the
-        prepass grid, tile history - is of traced_size."""
+        prepass grid, tile history - is of traced_size.  filter (gr_render_state_set_filter): FILTER_BOX, or FILTER_TENT / _GAUSSIAN /
+        _MITCHELL or their names - every frame of the state is then filter_frame of the traced frame with filter_taps' table, at
+        factor 1 too, whole frames only."""
         self.width, self.height, self.device = width, height, device
         self.handle = c_void_p()
         if supersample == 1:
@@ -397,6 +399,22 @@ class RenderState:
         f, tw, th = c_int(), c_int(), c_int()
         check(lib.gr_render_state_supersample(self.handle, ctypes.byref(f), ctypes.byref(tw), ctypes.byref(th)))
         self.supersample, self.traced_size = f.value, (tw.value, th.value)
+        if filter != FILTER_BOX:
+            self.set_filter(filter)
+
+    def set_filter(self, filter):
+        """the reconstruction filter of the frames from here on: a FILTER_* value or a name (box, tent, gaussian, mitchell)"""
+        if isinstance(filter, str):
+            if filter not in FILTER_NAMES:
+                raise ValueError(f"RenderState.set_filter: filter={filter!r} ({', '.join(FILTER_NAMES)})")
+            filter = FILTER_NAMES[filter]
+        check(lib.gr_render_state_set_filter(self.handle, int(filter)))
+
+    @property
+    def filter(self):
+        value = c_int()
+        check(lib.gr_render_state_filter(self.handle, ctypes.byref(value)))
+        return value.value
 
     def __del__(self):
         if getattr(self, "handle", None):
@@ -434,6 +452,8 @@ class RenderState:
         """render(), delivered as 8-bit BT.709 Y'CbCr 4:2:0 (gr_render_frame_yuv420): `out_ptr` is a device pointer to
         yuv420_bytes(width, height) bytes, aligned to 4, in `layout` (YUV420_I420: planes Y, Cb, Cr; YUV420_NV12: Y, then Cb Cr pairs);
         every byte is rgba8_to_yuv420's of the frame render_rgba8() writes.  Whole frames only."""
+        if layout is None:   # (render() would take that for "no video format" and deliver float4 into a buffer of 1.5 bytes a pixel)
+            raise ValueError("RenderState.render_yuv420: layout=None (YUV420_I420 or YUV420_NV12)")
         self.render(program, metric, camera, out_ptr, background, features, cfg_values, options, stream, yuv420=layout)
 
     def render_yuv420p10(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None,
@@ -442,6 +462,8 @@ class RenderState:
         yuv420p10_bytes(width, height) bytes, aligned to 8 where the width is a multiple of 4 and to 2 otherwise, in `layout` (YUV420_I420:
         yuv420p10le, planes Y, Cb, Cr; YUV420_NV12: P010, Y then Cb Cr pairs, codes in the high ten bits); every word is
         rgb10_to_yuv420p10(frame_to_rgb10(...))'s of the float frame render() writes (a NaN gives code 0).  Whole frames only."""
+        if layout is None:
+            raise ValueError("RenderState.render_yuv420p10: layout=None (YUV420_I420 or YUV420_NV12)")
         self.render(program, metric, camera, out_ptr, background, features, cfg_values, options, stream, yuv420=layout, bit_depth=10)
 
     def render_subframe(self, program, metric, camera, weight, first, background=None, features=None, cfg_values=None, options=None, stream=None):
@@ -618,6 +640,35 @@ def accumulate_frame(accum, frame, weight, first):
         raise ValueError("accumulate_frame: accum is a writeable C-contiguous float32 array of the frame's shape")
     check(lib.gr_accumulate_frame(accum.ctypes.data_as(c_void_p), frame.ctypes.data_as(c_void_p), frame.size, float(weight), int(bool(first))))
     return accum
+
+
+def filter_taps(filter, factor):
+    """The table of a named filter at a supersampling factor (gr_filter_taps): float32 [n] - FILTER_TENT (radius 1), FILTER_GAUSSIAN or
+    FILTER_MITCHELL (radius 2), or their names; n = 2 R f taps for an even f, 2 R f - 1 for an odd one, centred on the output pixel,
+    normalised in float64 and rounded once (so they need not sum to exactly 1).  FILTER_BOX has no table."""
+    if isinstance(filter, str):
+        if filter not in FILTER_NAMES:
+            raise ValueError(f"filter_taps: filter={filter!r} ({', '.join(FILTER_NAMES)})")
+        filter = FILTER_NAMES[filter]
+    taps, count = (c_float * FILTER_MAX_TAPS)(), c_int()
+    check(lib.gr_filter_taps(int(filter), int(factor), taps, ctypes.byref(count)))
+    return np.array(taps[:count.value], dtype=np.float32)
+
+
+def filter_frame(frame, factor, taps):
+    """The host statement of a filtered frame (gr_filter_frame): float32 [H*f, W*f, 4] -> [H, W, 4], the rows pass then the columns pass
+    with the same table `taps` (1 to 16 values, as many modulo 2 as f), tap t on the sample at offset (f - n)/2 + t from the pixel's own
+    block, samples past an edge taken from the edge; every product and every sum one rounded float32 operation in ascending t.  What a
+    RenderState with a filter delivers, bit for bit, of the frame a plain state of the traced size renders."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    f = int(factor)
+    if f < 1 or frame.ndim != 3 or frame.shape[2] != 4 or frame.shape[0] % f or frame.shape[1] % f or not frame.size:
+        raise ValueError(f"filter_frame: a frame of shape {frame.shape} is not [H*{f}, W*{f}, 4]")
+    taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    out = np.empty((frame.shape[0] // f, frame.shape[1] // f, 4), dtype=np.float32)
+    check(lib.gr_filter_frame(frame.ctypes.data_as(c_void_p), out.shape[1], out.shape[0], f, taps.ctypes.data_as(c_void_p), taps.size,
+                              out.ctypes.data_as(c_void_p)))
+    return out
 
 
 def yuv420p10_bytes(width, height):

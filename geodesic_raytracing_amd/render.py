@@ -18,6 +18,8 @@
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --bit-depth 10 --out pan10.y4m
     # ... with motion blur: a 180-degree shutter (open for half the frame interval), every frame the average of 8 sub-frames, summed on the device
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --shutter 0.5 --out pan_blur.y4m
+    # ... the 16 rays a pixel of --supersample 4 through a Mitchell-Netravali filter of radius 2 instead of a box one pixel wide: less shimmer
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --supersample 4 --filter mitchell --out pan_aa.y4m
 """
 import argparse
 import ctypes
@@ -132,7 +134,7 @@ def camera_path_at(position, quat, position_to=None, quat_to=None, frames=1, tim
 
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
-           parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0):
+           parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box"):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
@@ -148,6 +150,10 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     and camera_path_at make them); every frame returned is the sum of its T sub-frames with the box weight np.float32(1) / np.float32(T),
     accumulated on the device in linear light (RenderState.render_subframe: pipeline.accumulate_frame of the frames render() returns
     without it, bit for bit) and delivered in the format asked for (RenderState.deliver_accumulated).  Fused path only (not with adaptive).
+    filter: "box" (the mean of a pixel's own samples, as ever), "tent", "gaussian" or "mitchell" (or a gra.FILTER_* value) - the traced frame
+    goes through that separable reconstruction filter on the device instead (RenderState(filter=): pipeline.filter_frame with
+    pipeline.filter_taps' table of the frame a plain state of the traced size renders, bit for bit), at any supersample, 1 included, and
+    in every format; sub-frames of a shutter are filtered before they are accumulated.
     mips: where the sky's mip slices are made - "host" (pack_background, all slices uploaded) or "device" (build_background: the image is
     uploaded and the slices are built there, the same bytes)."""
     if mips not in ("host", "device"):
@@ -156,6 +162,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
         raise ValueError(f"render: bit_depth={bit_depth!r} (8, or 10 with yuv420=True)")
     if cameras is not None and geodesic_speed is not None:
         raise ValueError("render: cameras (interpolated poses) and geodesic_speed (a camera on its geodesic) exclude each other")
+    if filter not in gra.FILTER_NAMES and filter not in gra.FILTER_NAMES.values():
+        raise ValueError(f"render: filter={filter!r} ({', '.join(gra.FILTER_NAMES)})")
     shutter_samples = int(shutter_samples)
     if shutter_samples:
         moving = cameras if cameras is not None else geodesic_times if geodesic_speed is not None else None
@@ -167,7 +175,7 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     cfg_values = metric.cfg_values(**(cfg or {}))
     manager = ProgramManager(metric, device, feats, cfg_values)
     program = manager.current(wait=wait_for_static)
-    state = gra.RenderState(width, height, device, supersample=supersample)
+    state = gra.RenderState(width, height, device, supersample=supersample, filter=filter)
     rgba = background if background is not None else gra.synthetic_background(2048, 1024)
     if mips == "device":
         dbg, levels = gra.build_background(program, rgba, device)
@@ -328,6 +336,11 @@ def main(argv=None):
     ap.add_argument("--mips", choices=["host", "device"], default="host", help="where the sky's mip slices are made: host = pack them on the CPU "
                     "and upload all of them; device = upload the image and build the slices on the GPU (the same bytes)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--filter", choices=sorted(gra.FILTER_NAMES, key=gra.FILTER_NAMES.get), default="box", help="the reconstruction filter of "
+                    "--supersample's samples, applied on the device before any encode: box (the mean of the N x N samples behind a pixel), tent "
+                    "(radius 1 pixel), gaussian or mitchell (Mitchell-Netravali, B = C = 1/3; both radius 2) - wider separable filters that fold "
+                    "less of what the extra rays resolved back as aliasing.  Works at --supersample 1 too (gaussian and mitchell are a mild "
+                    "post-filter there, tent changes nothing).  Not with --devices")
     ap.add_argument("--devices", default=None, help="0,1,2,3: deal the rows of every frame to these GPUs (one process, peer copies; a device may "
                     "repeat); each traces, resolves and - with --encode device - encodes its share, the share rotating over --frames")
     ap.add_argument("--fps", default="24", help="frame rate of a .y4m file: N or N/D (24; 30000/1001)")
@@ -361,6 +374,9 @@ def main(argv=None):
             ap.error("--shutter with --adaptive: the sub-frames of a shutter are rendered on the fused path, adaptive sampling runs in reference mode")
         if not (a.camera_to or a.quat_to or a.geodesic_speed):
             ap.error("--shutter on a camera that does not move: there is no motion to blur; give --camera-to / --quat-to or --geodesic-speed")
+    if a.filter != "box" and a.devices is not None:
+        ap.error(f"--filter {a.filter} with --devices: a filter wider than a pixel reads across the strips of a split frame; render filtered "
+                 "frames on one device (a split frame takes --filter box)")
     if video and a.devices is not None:
         ap.error("--out NAME.y4m with --devices: a split frame travels as float4 or RGBA8, not as 4:2:0 planes; render the video on one device")
     if (a.camera_to or a.quat_to) and a.geodesic_speed:
@@ -406,7 +422,8 @@ def main(argv=None):
                     read_png(a.background) if a.background else None, a.device, a.fov, a.universe, geodesic_speed=speed,
                     geodesic_times=[a.geodesic_time + float(t) * a.geodesic_dt for t in moments] if samples else times,
                     parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
-                    rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples)
+                    rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples,
+                    filter=a.filter)
     if speed is None and cameras is None:
         result = [result]
     if video:

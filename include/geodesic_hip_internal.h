@@ -251,6 +251,57 @@ int gr_render_subframe(gr_render_state* s, gr_program* p, const gr_metric* m, vo
  * state's width is a multiple of 4 and 2 bytes otherwise (10-bit); a state that holds no accumulation. */
 int gr_deliver_accumulated(gr_render_state* s, gr_program* p, void* stream, int format, int layout, void* out);
 
+/* ---- Filtered frames ----------------------------------------------------------------------------------------------------------------
+ * Separable reconstruction filters behind a supersampled frame.  gr_resolve_supersampled is the mean of the f x f traced samples that lie
+ * exactly behind a pixel - a box one pixel wide, the weakest filter there is.  A filtered frame weights the samples around the pixel's
+ * centre with a table of n fp32 taps per axis instead (tent, Gaussian, Mitchell-Netravali, or the caller's own), on the device, before
+ * any encode.  (Declared here and not in geodesic_hip.h only because the contract header keeps to 80 names and 350 lines; all of this is
+ * public.)
+ *
+ * Definition.  The traced frame s is float4, W f x H f, f = 1 ... 4; the output is W x H.  A table has n taps, 1 <= n <= 16 and
+ * n = f (mod 2), and is centred on the output pixel: tap t multiplies the traced sample at offset (f - n)/2 + t from the first sample of
+ * the pixel's own block, at distance d_t = (t + 0.5 - n/2) / f output pixels from the pixel's centre.  The same table serves every pixel
+ * and both axes.  The rows pass comes first, the columns pass second; per channel (all four, alpha included):
+ *   h(y, X)   = acc after: acc = taps[0] * s(y, cx(X,0));  for t = 1 ... n-1: acc = acc + (taps[t] * s(y, cx(X,t)))     every traced row y
+ *   out(Y, X) = acc after: acc = taps[0] * h(cy(Y,0), X);  for t = 1 ... n-1: acc = acc + (taps[t] * h(cy(Y,t), X))
+ *   cx(X,t) = clamp(X f + (f - n)/2 + t, 0, W f - 1)        cy(Y,t) = clamp(Y f + (f - n)/2 + t, 0, H f - 1)
+ * Every product and every sum is one fp32 operation rounded to nearest even - NEVER a fused multiply-add - in ascending t, and h is
+ * rounded to fp32 between the passes: the two-pass form with a rounded intermediate is part of the definition.  The first term is
+ * taps[0] * s and not 0 + ...: a single tap of 1.0f passes every value bit for bit, the sign of a zero included.  A sample past an edge
+ * is the edge sample.  Taps of weight 0 are not skipped; NaN and infinity propagate as IEEE arithmetic has them. */
+#define GR_FILTER_MAX_TAPS 16
+/* The named filters.  GR_FILTER_BOX is gr_resolve_supersampled's path and has no table. */
+enum { GR_FILTER_BOX = 0, GR_FILTER_TENT = 1, GR_FILTER_GAUSSIAN = 2, GR_FILTER_MITCHELL = 3 };
+/* The taps of a named filter at factor 1 ... 4: tent (radius R = 1), Gaussian (R = 2) or Mitchell-Netravali with B = C = 1/3 (R = 2).
+ * *count = n = 2 R f for an even f, 2 R f - 1 for an odd one: the taps with |d_t| < R.  k(d), in double from |d|: tent 1 - |d|; Gaussian
+ * exp(-2 d^2) - exp(-8); Mitchell ((12 - 9B - 6C)|d|^3 + (-18 + 12B + 6C)|d|^2 + (6 - 2B)) / 6 below 1 and
+ * ((-B - 6C)|d|^3 + (6B + 30C)|d|^2 + (-12B - 48C)|d| + (8B + 24C)) / 6 from 1 to 2.  taps[t] = (float)(k(d_t) / sum of k(d_t) over
+ * ascending t, in double).  The library does NOT renormalise after rounding: the fp32 taps need not sum to exactly 1 (they are within
+ * n 2^-24 of it).  Tent at factor 1 is {1.0f}; at factor 2 it is {0.125, 0.375, 0.375, 0.125} exactly.  Refused, with
+ * GR_ERROR_INVALID_ARGUMENT and a message that names it: a NULL, a factor outside 1 ... 4, an unknown filter, and GR_FILTER_BOX, which has
+ * no table - its frame is gr_resolve_supersampled's. */
+int gr_filter_taps(int filter, int factor, float taps[GR_FILTER_MAX_TAPS], int* count);
+/* The host statement of the definition above: src is float[4 * width*factor * height*factor], dst float[4 * width * height]; compiled so
+ * that no product and sum are contracted.  Refused before anything is written, with GR_ERROR_INVALID_ARGUMENT and a message that names
+ * it: a NULL; a size below 1; a factor outside 1 ... 4; count outside 1 ... 16 or of the wrong parity; a tap that is not finite;
+ * src == dst. */
+int gr_filter_frame(const float* src, int width, int height, int factor, const float* taps, int count, float* dst);
+/* The same on the device by ONE launch (kernels/filter.hip, set-up module: IEEE arithmetic, no contraction), bit for bit: src and dst
+ * are device memory, taps is HOST memory (the table travels in the kernel's argument block).  Whole frames only.  Refused before any
+ * device call: what gr_filter_frame refuses, a NULL program, more than 2^31 - 1 source pixels, more than 524 280 rows. */
+int gr_resolve_filtered(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, const float* taps, int count);
+/* The filter of a state's frames: GR_FILTER_BOX (the default: every entry point is as it was, launch for launch) or a named filter, at
+ * any factor, 1 included (Mitchell and Gaussian are a mild post-filter there, tent is the identity).  With a filter set,
+ * gr_render_frame, gr_render_frame_rgba8, gr_render_frame_yuv420 and gr_render_frame_yuv420p10 deliver gr_filter_frame of the traced
+ * frame with gr_filter_taps' table: gr_resolve_filtered from the traced frame into a frame the state owns (float4 at the output size,
+ * allocated with the first frame that is not refused, freed with the state; a float4 delivery goes straight into `out`), then the
+ * format's own kernel at factor 1 from it; both launches are what gr_render_state_resolve_ms reports.  gr_render_subframe accumulates the
+ * filtered frame.  A filtered state renders whole frames only: strip_count > 1 and gr_render_frame_tiled / _tiled_as are refused before
+ * anything is rendered (a filter wider than a pixel reads across strip borders).  gr_render_state_set_filter refuses a NULL and an unknown
+ * filter; it may be called between frames. */
+int gr_render_state_set_filter(gr_render_state* s, int filter);
+int gr_render_state_filter(const gr_render_state* s, int* filter);
+
 /* ---- fused MI355X path (no reference counterpart) ------------------------------------------- */
 
 /* Prepass termination flags from one fused trace at prepass resolution (replaces the sequence
