@@ -131,6 +131,21 @@ class OraclePipeline:
                             width, height, max_probes, _p(cfg), _p(dfg), nthreads)
         return pixels
 
+    def render_data(self, rays, width, height, cfg_values, features_bytes, nthreads=1):
+        """ref_calculate_render_data on rays made by hand (tests/render_data_model.py) -> records [height * width], zeros where no ray
+        wrote.  The kernel stores at sy * width + sx unchecked, as the reference does: every ray's sx, sy must lie inside the frame
+        (asserted here; the padding slots of the tiled layout go to the device only)."""
+        rays = np.ascontiguousarray(rays, dtype=LIGHTRAY_DTYPE)
+        assert ((rays["sx"] >= 0) & (rays["sx"] < width) & (rays["sy"] >= 0) & (rays["sy"] < height)).all()
+        cfg = np.array(list(cfg_values) if len(cfg_values) else [0.0], dtype="<f4")
+        dfg = np.frombuffer(features_bytes, dtype=np.uint8).copy()
+        count = np.array([len(rays)], dtype="<i4")
+        rdata = np.zeros(width * height, dtype=RENDER_DATA_DTYPE)
+        rcount = np.zeros(1, dtype="<i4")
+        self.lib.ref_calculate_render_data(_p(rays), _p(count), len(rays), _p(rdata), _p(rcount), width, height, _p(cfg), _p(dfg), nthreads)
+        assert int(rcount[0]) == width * height
+        return rdata
+
     def attempts_per_ray(self, rays_init, cfg_values, features_bytes, nthreads=8):
         """Verlet attempts of every initial ray (restatement back end only; see ref_attempts_per_ray)"""
         cfg = np.array(list(cfg_values) if len(cfg_values) else [0.0], dtype="<f4")

@@ -13,6 +13,7 @@ and libm, and rays near photon orbits amplify 1-ulp differences - SURVEY.md sect
                            the slack and which approximation owns it: profiles/r03_trace_slack_owner.txt); the 90th
                            percentile of all terminated rays is held to the same 1e-3; total attempts within 0.3 %
   render_data              tex_coord abs 2e-6 (periodic), z_shift 1e-4 relative to |1 + z|, flags exact
+                           (the same two on rays made by hand, against a float64 model: tests/test_gpu_render_data.py)
   render (pixels)          RMSE <= 1e-5, max 2e-4 from golden render_data
                            (the same two on records made by hand, against a float64 model: tests/test_gpu_shading.py)
   end to end (pixels)      RMSE <= 1e-4 after masking pixels off by > 1e-3; mask <= 0.5 %
