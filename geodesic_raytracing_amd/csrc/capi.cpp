@@ -30,6 +30,7 @@
 
 #include "builtin_metrics.hpp"
 #include "codeobject.hpp"
+#include "frame_format.hpp"
 #include "jsfront.hpp"
 #include "metric_codegen.hpp"
 #include "program_build.hpp"
@@ -1119,87 +1120,72 @@ int gr_render_seams(gr_program* p, void* stream, const void* rdata, void* out, c
     return launch(p, K_RENDER, stream, blocks(num, 256), 1, 256, 1, args);
 }
 
-// the box filter of a supersampled frame (kernels/resolve.hip): one work item per output pixel of this device's rows, a wave on 64
-// consecutive pixels of one row, four rows to a workgroup
-int gr_resolve_supersampled(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int block_rows,
-                            int strip_rank, int strip_count, int compact_out) {
-    GR_NEED("gr_resolve_supersampled", src, dst);
-    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_resolve_supersampled: factor " + std::to_string(factor) + " (1 to 4)");
+// What the resolve, present and accumulate launchers below refuse alike, before any device call: a NULL buffer; a NULL program where the
+// launcher answers for it under its own name (launch() refuses it for the others); a factor outside 1 ... 4; a size below 1 or with more
+// than 2^31 - 1 source pixels; then grid_rows workgroup rows that the grid does not hold (0: no such check; a caller's blocks() of a bad size is 0 too).
+static int refuse_frame_launch(const char* who, const gr_program* p, bool needs_program, const void* src, const void* dst, int width, int height,
+                               int factor, unsigned grid_rows) {
+    GR_NEED(who, src, dst);
+    if (needs_program && !p) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": null program");
+    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": factor " + std::to_string(factor) + " (1 to 4)");
     if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "gr_resolve_supersampled: the frame's size");
+        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the frame's size");
+    if (grid_rows > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a frame of " + std::to_string(height) + " rows does not fit the grid");
+    return GR_OK;
+}
+
+// one work item per output pixel of this device's rows, a wave on 64 consecutive pixels of one row, four rows to a workgroup: the grid
+// and the row dealing of kernels/resolve.hip and of gr_present_rgba8
+static int launch_dealt_rows(int k, gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int block_rows,
+                             int strip_rank, int strip_count, int compact_out) {
+    const char* who = KERNEL_NAMES[k];
+    if (int rc = refuse_frame_launch(who, p, false, src, dst, width, height, factor, 0)) return rc;
     if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = height; }
-    if (block_rows <= 0 || strip_rank < 0 || strip_rank >= strip_count) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_resolve_supersampled: bad strip parameters");
+    if (block_rows <= 0 || strip_rank < 0 || strip_rank >= strip_count) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": bad strip parameters");
     int local_rows = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_rows;
     void* args[] = {&src, &dst, &width, &height, &factor, &block_rows, &strip_rank, &strip_count, &compact_out, &local_rows};
-    return launch(p, K_RESOLVE_SUPERSAMPLED, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
+    return launch(p, k, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
+}
+
+// the box filter of a supersampled frame (kernels/resolve.hip)
+int gr_resolve_supersampled(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int block_rows,
+                            int strip_rank, int strip_count, int compact_out) {
+    return launch_dealt_rows(K_RESOLVE_SUPERSAMPLED, p, stream, src, dst, width, height, factor, block_rows, strip_rank, strip_count, compact_out);
 }
 
 // gr_resolve_supersampled fused with the 8-bit sRGB encode (kernels/present.hip): the same grid, the same row dealing, one uint32 a pixel
 int gr_present_rgba8(gr_program* p, void* stream, const void* src, void* dst_rgba8, int width, int height, int factor, int block_rows,
                      int strip_rank, int strip_count, int compact_out) {
-    GR_NEED("gr_present_rgba8", src, dst_rgba8);
-    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_present_rgba8: factor " + std::to_string(factor) + " (1 to 4)");
-    if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "gr_present_rgba8: the frame's size");
-    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = height; }
-    if (block_rows <= 0 || strip_rank < 0 || strip_rank >= strip_count) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_present_rgba8: bad strip parameters");
-    int local_rows = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_rows;
-    void* args[] = {&src, &dst_rgba8, &width, &height, &factor, &block_rows, &strip_rank, &strip_count, &compact_out, &local_rows};
-    return launch(p, K_PRESENT_RGBA8, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
+    return launch_dealt_rows(K_PRESENT_RGBA8, p, stream, src, dst_rgba8, width, height, factor, block_rows, strip_rank, strip_count, compact_out);
 }
 
-// gr_present_rgba8's resolve and encode, then BT.709 Y'CbCr 4:2:0 (kernels/present.hip): a lane per 2 rows x 4 columns, a workgroup of
-// 64 x 4 lanes on 256 columns x 8 rows.  Whole frames only.  Everything is refused before the first device call.
+// gr_present_rgba8's resolve and encode, then BT.709 Y'CbCr 4:2:0 (kernels/present.hip: gr_present_yuv420, and gr_present_yuv420p10 with ten
+// bits a sample in 16-bit words): a lane per 2 rows x 4 columns, a workgroup of 64 x 4 lanes on 256 columns x 8 rows.  Whole frames only.
+// The two differ in the kernel and in dst's alignment, which is the format's (frame_format.cpp).  Everything is refused before the first device call.
+static int launch_video(int k, int format, gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout) {
+    const char* who = KERNEL_NAMES[k];
+    const unsigned gx = blocks(((long long)width + 3) / 4, 64), gy = blocks(((long long)height + 1) / 2, 4);
+    if (int rc = refuse_frame_launch(who, p, true, src, dst, width, height, factor, gy)) return rc;
+    const std::string wrong = frame_format::refusal(format, false, layout, (uintptr_t)dst, &width, 1);
+    if (!wrong.empty()) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + wrong);
+    void* args[] = {&src, &dst, &width, &height, &factor, &layout};
+    return launch(p, k, stream, gx, gy, 64, 4, args);
+}
 int gr_present_yuv420(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout) {
-    const char* who = "gr_present_yuv420";
-    GR_NEED(who, src, dst);
-    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": null program");
-    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": factor " + std::to_string(factor) + " (1 to 4)");
-    if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
-        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the frame's size");
-    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
-        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": layout " + std::to_string(layout) + " (GR_YUV420_I420 or GR_YUV420_NV12)");
-    if ((uintptr_t)dst % 4) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": dst must be aligned to 4 bytes");
-    const unsigned gx = blocks(((long long)width + 3) / 4, 64), gy = blocks(((long long)height + 1) / 2, 4);
-    if (gy > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a frame of " + std::to_string(height) + " rows does not fit the grid");
-    void* args[] = {&src, &dst, &width, &height, &factor, &layout};
-    return launch(p, K_PRESENT_YUV420, stream, gx, gy, 64, 4, args);
+    return launch_video(K_PRESENT_YUV420, GR_FRAME_YUV420, p, stream, src, dst, width, height, factor, layout);
 }
-
-// gr_present_yuv420 with ten bits a sample in 16-bit words (kernels/present.hip: gr_present_yuv420p10): the same grid, the same refusals;
-// the fast store path (width % 4 == 0) writes 8 bytes at a time, the other one word at a time
 int gr_present_yuv420p10(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout) {
-    const char* who = "gr_present_yuv420p10";
-    GR_NEED(who, src, dst);
-    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": null program");
-    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": factor " + std::to_string(factor) + " (1 to 4)");
-    if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
-        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the frame's size");
-    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
-        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": layout " + std::to_string(layout) + " (GR_YUV420_I420 or GR_YUV420_NV12)");
-    const int alignment = width % 4 == 0 ? 8 : 2;
-    if ((uintptr_t)dst % alignment)
-        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": dst must be aligned to " + std::to_string(alignment) + " bytes at a width of " +
-                                                   std::to_string(width));
-    const unsigned gx = blocks(((long long)width + 3) / 4, 64), gy = blocks(((long long)height + 1) / 2, 4);
-    if (gy > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a frame of " + std::to_string(height) + " rows does not fit the grid");
-    void* args[] = {&src, &dst, &width, &height, &factor, &layout};
-    return launch(p, K_PRESENT_YUV420P10, stream, gx, gy, 64, 4, args);
+    return launch_video(K_PRESENT_YUV420P10, GR_FRAME_YUV420P10, p, stream, src, dst, width, height, factor, layout);
 }
 
 // one sub-frame of a shutter into the accumulation frame (kernels/shutter.hip): gr_resolve_supersampled's grid over the whole frame; with
 // `first` the accumulation frame is written without being read.  Everything is refused before the first device call.
 int gr_shutter_accumulate(gr_program* p, void* stream, const void* src, void* accum, int width, int height, int factor, float weight, int first) {
     const char* who = "gr_shutter_accumulate";
-    GR_NEED(who, src, accum);
-    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": null program");
-    if (src == accum) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the sub-frame and the accumulation frame are one buffer");
-    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": factor " + std::to_string(factor) + " (1 to 4)");
-    if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
-        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the frame's size");
-    if (!std::isfinite(weight)) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a weight that is not finite");
     const unsigned gy = blocks(height, 4);
-    if (gy > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a frame of " + std::to_string(height) + " rows does not fit the grid");
+    if (int rc = refuse_frame_launch(who, p, true, src, accum, width, height, factor, gy)) return rc;
+    if (src == accum) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the sub-frame and the accumulation frame are one buffer");
+    if (!std::isfinite(weight)) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a weight that is not finite");
     first = first ? 1 : 0;
     void* args[] = {&src, &accum, &width, &height, &factor, &weight, &first};
     return launch(p, K_SHUTTER_ACCUMULATE, stream, blocks(width, 64), gy, 64, 4, args);

@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "../../include/geodesic_hip_internal.h"
+#include "frame_format.hpp"
 #include "frame_plan.hpp"
 
 using frame_plan::origin_on_screen;
@@ -1569,140 +1570,136 @@ static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metri
     return f.opt.mode == GR_MODE_FUSED ? render_fused(f) : render_reference_shaped(f);
 }
 
-// What the four entry points below deliver: the frame as render_traced_frame renders it, at the traced size, into the state's own traced
-// frame (at factor 1 too: the encoders read float4 and the caller has only bytes), and ONE launch from there into the caller's memory -
-// the box average as float4 (gr_resolve_supersampled), or resolve and encode in one pass as 8-bit sRGB (gr_present_rgba8) or as BT.709
-// Y'CbCr 4:2:0 planes of 8-bit (gr_present_yuv420) or 10-bit samples (gr_present_yuv420p10), both whole frames only.  A device's share of
-// a split frame is traced in blocks of factor x as many rows, so that they cover the rows its output blocks average.  `name`: the entry
-// point's, for its refusals.
-enum delivery { DELIVER_FLOAT4, DELIVER_RGBA8, DELIVER_YUV420, DELIVER_YUV420P10 };
-// the frame a state with a filter resolves into (geodesic_hip_internal.h, "Filtered frames"): allocated once, freed with the state
-static int allocate_filtered_frame(gr_render_state* s) {
-    if (s->filtered_frame) return GR_OK;
-    HIP_CHECK(hipSetDevice(s->device));
-    HIP_CHECK(hipMalloc(&s->filtered_frame, (size_t)s->out_width * s->out_height * 4 * sizeof(float)));
-    return GR_OK;
+// ---- frame delivery: a frame, then a sink ---------------------------------------------------------------------------------------
+// What the entry points below deliver: the frame as render_traced_frame renders it, at the traced size, into the state's own traced frame (at factor 1
+// too: the encoders read float4 and the caller has only bytes), and from there into a sink - the caller's memory in one of the formats of frame_format.cpp,
+// or the state's accumulation frame.  A device's share of a split frame is traced in blocks of factor x as many rows: the rows its output blocks average.
+
+// The one launch that makes `out` from a float4 frame of width*factor x height*factor: the format's existing launcher - the box average
+// as float4, or resolve and encode in one pass as 8-bit sRGB or as BT.709 Y'CbCr 4:2:0 planes of 8-bit or 10-bit samples (whole frames only).
+// strips: the options of a share of a split frame with block_rows in output rows, NULL for a whole frame.
+static int encode_frame(gr_program* p, void* stream, int format, int layout, const void* src, int width, int height, int factor,
+                        const gr_frame_options* strips, void* out) {
+    const int rows = strips ? strips->block_rows : 0, rank = strips ? strips->strip_rank : 0, count = strips ? strips->strip_count : 1,
+              compact_out = strips ? strips->compact_out : 0;   // (strip_count 1: every row, whatever the rest says)
+    switch (format) {
+    case GR_FRAME_F32: return gr_resolve_supersampled(p, stream, src, out, width, height, factor, rows, rank, count, compact_out);
+    case GR_FRAME_RGBA8: return gr_present_rgba8(p, stream, src, out, width, height, factor, rows, rank, count, compact_out);
+    case GR_FRAME_YUV420: return gr_present_yuv420(p, stream, src, out, width, height, factor, layout);
+    case GR_FRAME_YUV420P10: return gr_present_yuv420p10(p, stream, src, out, width, height, factor, layout);
+    }
+    return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("unknown frame format " + std::to_string(format)).c_str());
 }
-static int deliver_frame(delivery what, int layout, const char* name, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream,
+
+// frame_format::refusal of an output under the entry point's name.  The state is read only where the answer depends on its width.
+static int refuse_output(const char* name, int format, int layout, const void* out, const gr_render_state* s, int strip_count) {
+    const std::string wrong = frame_format::refusal(format, false, layout, (uintptr_t)out, s ? &s->out_width : nullptr, strip_count);
+    return wrong.empty() ? GR_OK : gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": " + wrong).c_str());
+}
+
+// where a delivered frame goes: encoded as (format, layout) into out, or - accumulate - weight x the frame into the accumulation frame
+struct sink { int format, layout; void* out; bool accumulate; float weight; int first; };
+
+// The delivery core (`name`: the entry point's, for its refusals).  What needs no device is refused first; nothing is allocated for a call that is refused.
+static int deliver_frame(const char* name, const sink& to, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream,
                          const gr_camera* camera, const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1,
-                         const void* bg2, int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* options) {
+                         const void* bg2, int bg_width, int bg_height, int bg_levels, const gr_frame_options* options) {
     gr_frame_options opt;
     gr_frame_options_default(&opt);
     if (options) opt = *options;
-    const int factor = s->supersample, block_rows = opt.block_rows;
+    const int factor = s->supersample, w = s->out_width, h = s->out_height;
     if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": block_rows").c_str());
-    opt.block_rows *= factor;
+    gr_frame_options traced = opt;   // the frame behind it: blocks of factor x as many rows
+    traced.block_rows *= factor;
     const bool filtered = s->filter != GR_FILTER_BOX;
     if (filtered && opt.strip_count > 1)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": a state with a filter renders whole frames only (strip_count > 1): a filter "
                                                                                 "wider than a pixel reads across strip borders").c_str());
-    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out));
-    if (!s->traced_frame) {   // a factor-1 state's first encoded frame (nothing is allocated for a call that is refused)
-        HIP_CHECK(hipSetDevice(s->device));
+    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, to.accumulate ? s : to.out));   // (s: any non-NULL out)
+    const bool allocates = !s->traced_frame || (to.accumulate && !s->accumulation) || (filtered && !s->filtered_frame);
+    if (allocates) HIP_CHECK(hipSetDevice(s->device));   // (render_traced_frame sets it for everything else)
+    if (!s->traced_frame) {   // a factor-1 state's first frame that does not go straight to the caller
         HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
         for (auto& ev : s->ev_resolve)
             if (!ev) HIP_CHECK(hipEventCreate(&ev));
     }
+    if (to.accumulate && !s->accumulation) HIP_CHECK(hipMalloc(&s->accumulation, (size_t)w * h * 4 * sizeof(float)));
     float taps[GR_FILTER_MAX_TAPS];
     int tap_count = 0;
-    if (filtered) {
+    if (filtered) {   // the frame a state with a filter resolves into (geodesic_hip_internal.h, "Filtered frames"): allocated once, freed with the state
         GR_CHECK(gr_filter_taps(s->filter, factor, taps, &tap_count));
-        GR_CHECK(allocate_filtered_frame(s));
+        if (!s->filtered_frame) HIP_CHECK(hipMalloc(&s->filtered_frame, (size_t)w * h * 4 * sizeof(float)));
     }
+    if (to.accumulate && to.first) s->accumulated = 0;   // (a sub-frame that fails below leaves nothing to deliver)
     GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
-                                 s->traced_frame, &opt));
+                                 s->traced_frame, &traced));
     const bool strips = opt.mode == GR_MODE_FUSED && opt.strip_count > 1;   // (as the fused path reads them; the reference-shaped sequence renders whole frames)
-    const int rows = strips ? block_rows : s->out_height, rank = strips ? opt.strip_rank : 0, count = strips ? opt.strip_count : 1,
-              compact_out = strips ? opt.compact_out : 0;
     const bool timed = opt.time_kernels == 1;
     if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
-    if (filtered) {
-        // the filtered frame - straight into the caller's memory where that is float4 - and from it the format's own kernel at factor 1,
-        // as gr_deliver_accumulated runs it from the accumulation frame
-        const int w = s->out_width, h = s->out_height;
-        GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, what == DELIVER_FLOAT4 ? out : s->filtered_frame, w, h, factor, taps, tap_count));
-        if (what == DELIVER_RGBA8)
-            GR_CHECK(gr_present_rgba8(p, stream, s->filtered_frame, out, w, h, 1, h, 0, 1, 0));
-        else if (what == DELIVER_YUV420)
-            GR_CHECK(gr_present_yuv420(p, stream, s->filtered_frame, out, w, h, 1, layout));
-        else if (what == DELIVER_YUV420P10)
-            GR_CHECK(gr_present_yuv420p10(p, stream, s->filtered_frame, out, w, h, 1, layout));
-    } else if (what == DELIVER_FLOAT4)
-        GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, rows, rank, count, compact_out));
-    else if (what == DELIVER_RGBA8)
-        GR_CHECK(gr_present_rgba8(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, rows, rank, count, compact_out));
-    else if (what == DELIVER_YUV420)
-        GR_CHECK(gr_present_yuv420(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, layout));
-    else
-        GR_CHECK(gr_present_yuv420p10(p, stream, s->traced_frame, out, s->out_width, s->out_height, factor, layout));
+    // a state with a filter: the filtered frame - straight into the caller's memory where that is float4 - and the sink from it at factor 1
+    const bool direct = filtered && !to.accumulate && to.format == GR_FRAME_F32;
+    if (filtered) GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, direct ? to.out : s->filtered_frame, w, h, factor, taps, tap_count));
+    const void* src = filtered ? s->filtered_frame : s->traced_frame;
+    if (to.accumulate) GR_CHECK(gr_shutter_accumulate(p, stream, src, s->accumulation, w, h, filtered ? 1 : factor, to.weight, to.first));
+    else if (!direct) GR_CHECK(encode_frame(p, stream, to.format, to.layout, src, w, h, filtered ? 1 : factor, strips ? &opt : nullptr, to.out));
     if (timed) {
         HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
         s->resolve_timed = true;
     }
+    if (to.accumulate) s->accumulated++;
     return GR_OK;
+}
+
+// gr_render_frame and its three encoded kin by format.  All but float4 refuse a NULL and what their launch would of `out` before anything is rendered or allocated.
+int gr_internal_render_frame_as(int format, int layout, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
+                                const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
+                                int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* options) {
+    if (!frame_format::find(format)) return refuse_output("gr_internal_render_frame_as", format, layout, out, s, 1);
+    const frame_format::row& f = *frame_format::find(format);
+    if (format != GR_FRAME_F32) {
+        if (!s || !p || !m || !camera || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(f.entry) + ": null argument").c_str());
+        GR_CHECK(refuse_output(f.entry, format, layout, out, s, options ? options->strip_count : 1));
+    }
+    if (s) s->resolve_timed = false;
+    // (a factor-1 box state's float4 frame goes straight to the caller; out == NULL stops after the records: nothing was shaded, nothing to resolve)
+    if (format == GR_FRAME_F32 && (!s || (s->supersample == 1 && s->filter == GR_FILTER_BOX) || !out))
+        return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out, options);
+    return deliver_frame(f.entry, sink{format, layout, out, false, 0.f, 0}, s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2,
+                         bg_width, bg_height, bg_levels, options);
 }
 
 int gr_render_frame(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
                     const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height,
                     int bg_levels, void* out, const gr_frame_options* options) {
-    if (s) s->resolve_timed = false;
-    // (out == NULL stops after the records: nothing was shaded, nothing to resolve)
-    if (!s || (s->supersample == 1 && s->filter == GR_FILTER_BOX) || !out)
-        return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out, options);
-    return deliver_frame(DELIVER_FLOAT4, 0, "gr_render_frame", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width,
-                         bg_height, bg_levels, out, options);
+    return gr_internal_render_frame_as(GR_FRAME_F32, 0, s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height,
+                                       bg_levels, out, options);
 }
 
 int gr_render_frame_rgba8(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
                           const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height,
                           int bg_levels, void* out_rgba8, const gr_frame_options* options) {
-    if (!s || !out_rgba8) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_rgba8: null argument");
-    s->resolve_timed = false;
-    return deliver_frame(DELIVER_RGBA8, 0, "gr_render_frame_rgba8", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width,
-                         bg_height, bg_levels, out_rgba8, options);
+    return gr_internal_render_frame_as(GR_FRAME_RGBA8, 0, s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height,
+                                       bg_levels, out_rgba8, options);
 }
 
-// Everything the gr_present_yuv420 launch itself would refuse is refused here, before the frame is rendered (and before a factor-1 state
-// allocates its traced frame).
 int gr_render_frame_yuv420(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
                            const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height,
                            int bg_levels, void* out_yuv420, int layout, const gr_frame_options* options) {
-    if (!s || !p || !m || !camera || !out_yuv420) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: null argument");
-    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: layout (GR_YUV420_I420 or GR_YUV420_NV12)");
-    if ((uintptr_t)out_yuv420 % 4) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: out_yuv420 must be aligned to 4 bytes");
-    if (options && options->strip_count > 1)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420: whole frames only (strip_count > 1); a split frame travels as float4 or "
-                                                           "RGBA8: gr_render_frame_tiled_as");
-    s->resolve_timed = false;
-    return deliver_frame(DELIVER_YUV420, layout, "gr_render_frame_yuv420", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2,
-                         bg_width, bg_height, bg_levels, out_yuv420, options);
+    return gr_internal_render_frame_as(GR_FRAME_YUV420, layout, s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width,
+                                       bg_height, bg_levels, out_yuv420, options);
 }
 
-// The same with ten bits a sample (geodesic_hip_internal.h, "10-bit video frames"): gr_present_yuv420p10's refusals, before the frame is rendered
 int gr_render_frame_yuv420p10(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
                               const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
                               int bg_width, int bg_height, int bg_levels, void* out_yuv420p10, int layout, const gr_frame_options* options) {
-    if (!s || !p || !m || !camera || !out_yuv420p10) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420p10: null argument");
-    if (layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420p10: layout (GR_YUV420_I420 or GR_YUV420_NV12)");
-    // (the state is read only for a pointer that is not aligned to 8 bytes)
-    if ((uintptr_t)out_yuv420p10 % 8 && ((uintptr_t)out_yuv420p10 % 2 || s->out_width % 4 == 0))
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420p10: out_yuv420p10 must be aligned to 8 bytes where the width is a "
-                                                           "multiple of 4, to 2 bytes otherwise");
-    if (options && options->strip_count > 1)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_yuv420p10: whole frames only (strip_count > 1); a split frame travels as float4 "
-                                                           "or RGBA8: gr_render_frame_tiled_as");
-    s->resolve_timed = false;
-    return deliver_frame(DELIVER_YUV420P10, layout, "gr_render_frame_yuv420p10", s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1,
-                         bg2, bg_width, bg_height, bg_levels, out_yuv420p10, options);
+    return gr_internal_render_frame_as(GR_FRAME_YUV420P10, layout, s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width,
+                                       bg_height, bg_levels, out_yuv420p10, options);
 }
 
 // ---- motion-blurred frames (geodesic_hip_internal.h, "Motion-blurred frames") -------------------------------------------------------
-// One sub-frame of a shutter: the frame as render_traced_frame renders it, into the state's traced frame as deliver_frame does, and ONE
-// launch of gr_shutter_accumulate from there into the state's accumulation frame.  A sub-frame is a frame: nothing in frame_plan.cpp knows
-// of it, and consecutive sub-frames are consecutive frames of the state (tile history, look-ahead, still-camera reuse).  Everything that
-// needs no device is refused first; nothing is allocated for a call that is refused.
+// One sub-frame of a shutter: a delivery whose sink is the state's accumulation frame, by ONE launch of gr_shutter_accumulate.  A
+// sub-frame is a frame: nothing in frame_plan.cpp knows of it, and consecutive sub-frames are consecutive frames of the state (tile
+// history, look-ahead, still-camera reuse).
 int gr_render_subframe(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
                        const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height, int bg_levels,
                        float weight, int first, const gr_frame_options* options) {
@@ -1717,66 +1714,18 @@ int gr_render_subframe(gr_render_state* s, gr_program* p, const gr_metric* m, vo
     if (!first && !s->accumulated)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: first = 0 on a state that holds no accumulation (a shutter's first sub-frame has first = 1)");
     s->resolve_timed = false;
-    gr_frame_options opt;   // (as deliver_frame hands them on: a supersampled state's frame is this frame, options and all)
-    gr_frame_options_default(&opt);
-    if (options) opt = *options;
-    if (opt.block_rows > 0x7fffffff / s->supersample) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: block_rows");
-    opt.block_rows *= s->supersample;
-    GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, s));   // (s: any non-NULL out)
-    HIP_CHECK(hipSetDevice(s->device));
-    if (!s->traced_frame) {   // a factor-1 state's first frame that does not go straight to the caller
-        HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
-        for (auto& ev : s->ev_resolve)
-            if (!ev) HIP_CHECK(hipEventCreate(&ev));
-    }
-    if (!s->accumulation) HIP_CHECK(hipMalloc(&s->accumulation, (size_t)s->out_width * s->out_height * 4 * sizeof(float)));
-    const bool filtered = s->filter != GR_FILTER_BOX;
-    float taps[GR_FILTER_MAX_TAPS];
-    int tap_count = 0;
-    if (filtered) {
-        GR_CHECK(gr_filter_taps(s->filter, s->supersample, taps, &tap_count));
-        GR_CHECK(allocate_filtered_frame(s));
-    }
-    if (first) s->accumulated = 0;   // (a sub-frame that fails below leaves nothing to deliver)
-    GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
-                                 s->traced_frame, &opt));
-    const bool timed = opt.time_kernels == 1;
-    if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
-    if (filtered) {   // the filtered frame, accumulated from there at factor 1
-        GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, s->filtered_frame, s->out_width, s->out_height, s->supersample, taps, tap_count));
-        GR_CHECK(gr_shutter_accumulate(p, stream, s->filtered_frame, s->accumulation, s->out_width, s->out_height, 1, weight, first));
-    } else
-        GR_CHECK(gr_shutter_accumulate(p, stream, s->traced_frame, s->accumulation, s->out_width, s->out_height, s->supersample, weight, first));
-    if (timed) {
-        HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
-        s->resolve_timed = true;
-    }
-    s->accumulated++;
-    return GR_OK;
+    return deliver_frame("gr_render_subframe", sink{GR_FRAME_F32, 0, nullptr, true, weight, first}, s, p, m, stream, camera, features, cfg_values,
+                         num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, options);
 }
 
-// The accumulation frame through one of the four existing kernels at factor 1 - the launch gr_render_frame* ends with, from another source.
+// The accumulation frame through the format's launch at factor 1 - the launch gr_render_frame* ends with, from another source.
 int gr_deliver_accumulated(gr_render_state* s, gr_program* p, void* stream, int format, int layout, void* out) {
     if (!s || !p || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: null argument");
-    if (format != GR_FRAME_F32 && format != GR_FRAME_RGBA8 && format != GR_FRAME_YUV420 && format != GR_FRAME_YUV420P10)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_deliver_accumulated: unknown frame format " + std::to_string(format) +
-                                                            " (GR_FRAME_F32, GR_FRAME_RGBA8, GR_FRAME_YUV420 or GR_FRAME_YUV420P10)").c_str());
-    const bool video = format == GR_FRAME_YUV420 || format == GR_FRAME_YUV420P10;
-    if (video && layout != GR_YUV420_I420 && layout != GR_YUV420_NV12)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: layout (GR_YUV420_I420 or GR_YUV420_NV12)");
-    if (format == GR_FRAME_YUV420 && (uintptr_t)out % 4)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: out must be aligned to 4 bytes for GR_FRAME_YUV420");
-    if (format == GR_FRAME_YUV420P10 && (uintptr_t)out % 8 && ((uintptr_t)out % 2 || s->out_width % 4 == 0))
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: out must be aligned to 8 bytes for GR_FRAME_YUV420P10 where the width is a "
-                                                           "multiple of 4, to 2 bytes otherwise");
+    GR_CHECK(refuse_output("gr_deliver_accumulated", format, layout, out, s, 1));
     if (!s->accumulated || !s->accumulation)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: the state holds no accumulation (gr_render_subframe first)");
     HIP_CHECK(hipSetDevice(s->device));
-    const int w = s->out_width, h = s->out_height;
-    if (format == GR_FRAME_F32) return gr_resolve_supersampled(p, stream, s->accumulation, out, w, h, 1, h, 0, 1, 0);
-    if (format == GR_FRAME_RGBA8) return gr_present_rgba8(p, stream, s->accumulation, out, w, h, 1, h, 0, 1, 0);
-    if (format == GR_FRAME_YUV420) return gr_present_yuv420(p, stream, s->accumulation, out, w, h, 1, layout);
-    return gr_present_yuv420p10(p, stream, s->accumulation, out, w, h, 1, layout);
+    return encode_frame(p, stream, format, layout, s->accumulation, s->out_width, s->out_height, 1, nullptr, out);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/geodesic_hip_internal.h"
+#include "frame_format.hpp"
 
 extern "C" int gr_internal_fail(int code, const char* msg);
 
@@ -211,11 +212,7 @@ int gr_read_png_rgba8(const char* path, int* width, int* height, unsigned char* 
 
 // ---- video frames (include/geodesic_hip.h says all of it: formulas, siting, layouts, the stream's format) ----------------------------
 
-size_t gr_yuv420_bytes(int width, int height) {
-    if (width < 1 || height < 1) return 0;
-    const size_t cw = ((size_t)width + 1) / 2, ch = ((size_t)height + 1) / 2;
-    return (size_t)width * height + 2 * cw * ch;
-}
+size_t gr_yuv420_bytes(int width, int height) { return frame_format::yuv420_bytes(width, height); }
 
 // BT.709, limited range, 16 fractional bits, int32 throughout (the largest intermediate is 28784 * 1020 + 131072 < 2^25); each chroma
 // row sums to zero, so a grey block gives 128 exactly.  A missing column or row of the last block is the edge pixel itself.

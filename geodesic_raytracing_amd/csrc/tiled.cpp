@@ -39,9 +39,14 @@
 #include <vector>
 
 #include "../../include/geodesic_hip_internal.h"
+#include "frame_format.hpp"
 
 extern "C" int gr_internal_fail(int code, const char* msg);
 extern "C" int gr_internal_render_state_size(const gr_render_state* s, int* width, int* height);
+// frame.cpp: gr_render_frame and its three encoded kin by the format's value (a share is rendered through it)
+extern "C" int gr_internal_render_frame_as(int format, int layout, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
+                                           const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
+                                           int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* options);
 struct gr_tiled;
 
 namespace {
@@ -501,12 +506,11 @@ size_t gr_tiled_staging_bytes(const gr_tiled* t) { return t ? t->staging_bytes()
 // match in issue order).  `format` sets the size of a pixel - 16 bytes (GR_FRAME_F32) or 4 (GR_FRAME_RGBA8) - and with it every offset
 // and count: rows of a byte frame are a quarter as long, in the frame and in the staged blocks alike, and a table's send / recv is
 // given a block as 4-byte words whatever they hold (RCCL moves them as ncclFloat: bytes in, the same bytes out).
-static int pixel_bytes_of(int format) { return format == GR_FRAME_F32 ? 16 : format == GR_FRAME_RGBA8 ? 4 : 0; }
-
 int gr_tiled_exchange_as(gr_tiled* t, const void* staging, void* frame_on_root, int rotation, void* stream_v, int format) {
     if (!t) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
-    const size_t pixel_bytes = (size_t)pixel_bytes_of(format);
-    if (!pixel_bytes) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_tiled_exchange_as: unknown frame format " + std::to_string(format) + " (GR_FRAME_F32 or GR_FRAME_RGBA8)").c_str());
+    const std::string unknown = frame_format::refusal(format, true, 0, 0, nullptr, 1);   // (of a split frame's format nothing else is refused)
+    if (!unknown.empty()) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_tiled_exchange_as: " + unknown).c_str());
+    const size_t pixel_bytes = (size_t)frame_format::find(format)->split_pixel_bytes;
     if (t->world == 1) return GR_OK;
     hipStream_t stream = (hipStream_t)stream_v;
     const bool is_root = t->rank == t->root;
@@ -564,7 +568,8 @@ int gr_render_frame_tiled_as(gr_tiled* t, gr_render_state* s, gr_program* p, con
                              const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
                              int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation, int format) {
     if (!t) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
-    if (!pixel_bytes_of(format)) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_render_frame_tiled_as: unknown frame format " + std::to_string(format) + " (GR_FRAME_F32 or GR_FRAME_RGBA8)").c_str());
+    const std::string unknown = frame_format::refusal(format, true, 0, 0, nullptr, 1);
+    if (!unknown.empty()) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_render_frame_tiled_as: " + unknown).c_str());
     const bool is_root = t->rank == t->root;
     if (is_root && !frame_on_root) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "the root needs the frame buffer");
     if (t->transport == GR_TRANSPORT_PEER && !frame_on_root) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "peer transport: every participant is given the root's frame buffer");
@@ -586,7 +591,6 @@ int gr_render_frame_tiled_as(gr_tiled* t, gr_render_state* s, gr_program* p, con
             return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_render_frame_tiled_as: blocks of " + std::to_string(t->block_rows) + " rows traced at factor " + std::to_string(factor) + " have more rows than an int counts").c_str());
     }
     hipStream_t stream = (hipStream_t)stream_v;
-    const auto render = format == GR_FRAME_RGBA8 ? gr_render_frame_rgba8 : gr_render_frame;
     gr_frame_options opt;
     gr_frame_options_default(&opt);
     if (options) opt = *options;
@@ -612,12 +616,13 @@ int gr_render_frame_tiled_as(gr_tiled* t, gr_render_state* s, gr_program* p, con
     }
     HIP_CHECK(hipSetDevice(t->device));
     if (t->world == 1)
-        return render(s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, frame_on_root, &opt);
+        return gr_internal_render_frame_as(format, 0, s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
+                                           frame_on_root, &opt);
     frame_slot* sl = nullptr;
     int rc = next_slot(t, stream, &sl);
     if (rc != GR_OK) return rc;
-    const int render_rc = render(s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
-                                 is_root ? frame_on_root : sl->buffer, &opt);
+    const int render_rc = gr_internal_render_frame_as(format, 0, s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height,
+                                                      bg_levels, is_root ? frame_on_root : sl->buffer, &opt);
     std::string render_error = render_rc != GR_OK ? gr_last_error() : "";
     // The transfers are issued even when this participant's render failed: the others have matching sends / receives in their
     // groups and would wait for ever.  The caller sees the render's error.

@@ -1,11 +1,12 @@
 """Thin object layer over the C ABI: Metric, Program, RenderState (host mirror of the reference's
 metric_manager / render_state roles).  All compute happens inside libgeodesic_hip.so."""
+import collections
 import ctypes
 import os
 
 import numpy as np
 
-from . import (Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
+from . import (Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, FRAME_YUV420, FRAME_YUV420P10, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
                c_size_t, c_void_p, check, lib)
 
 LIGHTRAY_DTYPE = np.dtype([("position", "<f4", 4), ("velocity", "<f4", 4), ("initial_quat", "<f4", 4),
@@ -430,17 +431,10 @@ class RenderState:
             raise ValueError(f"RenderState.render: bit_depth={bit_depth!r} (8, or 10 with a yuv420 layout)")
         features, arr, n, bg1, bg2, bw, bh, bl = _frame_arguments(metric, features, cfg_values, background)
         options = ctypes.byref(options) if options is not None else None
-        if yuv420 is not None and bit_depth == 10:
-            check(lib.gr_render_frame_yuv420p10(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr,
-                                                n, bg1, bg2, bw, bh, bl, out_ptr, int(yuv420), options))
-            return
-        if yuv420 is not None:
-            check(lib.gr_render_frame_yuv420(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n,
-                                             bg1, bg2, bw, bh, bl, out_ptr, int(yuv420), options))
-            return
-        entry = lib.gr_render_frame_rgba8 if rgba8 else lib.gr_render_frame
-        check(entry(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n, bg1, bg2, bw, bh, bl,
-                    out_ptr, options))
+        fmt = FRAME_FORMATS[frame_format_of(rgba8, yuv420 is not None, bit_depth)]
+        layout = (int(yuv420),) if fmt.takes_layout else ()
+        check(getattr(lib, fmt.entry)(self.handle, program.handle, metric.handle, stream, ctypes.byref(camera), ctypes.byref(features), arr, n, bg1, bg2,
+                                      bw, bh, bl, out_ptr, *layout, options))
 
     def render_rgba8(self, program, metric, camera, out_ptr, background=None, features=None, cfg_values=None, options=None, stream=None):
         """render(), delivered as 8-bit sRGB (gr_render_frame_rgba8): `out_ptr` is a device pointer to width*height*4 bytes, R G B A, rows
@@ -674,6 +668,22 @@ def filter_frame(frame, factor, taps):
 def yuv420p10_bytes(width, height):
     """the bytes of a width x height frame in 10-bit Y'CbCr 4:2:0 (16-bit words), either layout: 2 * yuv420_bytes(width, height)"""
     return int(lib.gr_yuv420p10_bytes(int(width), int(height)))
+
+
+# A frame format is a FRAME_* value with a row here: the library's entry point that renders a frame in it, whether that takes a layout, the
+# bytes of a width x height frame, and the numpy dtype and shape of one fetched from the device (csrc/frame_format.cpp is the library's table)
+FrameFormat = collections.namedtuple("FrameFormat", "entry takes_layout bytes dtype shape")
+FRAME_FORMATS = {
+    FRAME_F32: FrameFormat("gr_render_frame", False, lambda w, h: w * h * 16, np.float32, lambda w, h: (h, w, 4)),
+    FRAME_RGBA8: FrameFormat("gr_render_frame_rgba8", False, lambda w, h: w * h * 4, np.uint8, lambda w, h: (h, w, 4)),
+    FRAME_YUV420: FrameFormat("gr_render_frame_yuv420", True, yuv420_bytes, np.uint8, lambda w, h: (yuv420_bytes(w, h),)),
+    FRAME_YUV420P10: FrameFormat("gr_render_frame_yuv420p10", True, yuv420p10_bytes, np.uint16, lambda w, h: (yuv420p10_bytes(w, h) // 2,)),
+}
+
+
+def frame_format_of(rgba8=False, yuv420=False, bit_depth=8):
+    """the FRAME_* value that render()'s three keyword arguments name between them: a video format wins over rgba8"""
+    return FRAME_YUV420P10 if yuv420 and bit_depth == 10 else FRAME_YUV420 if yuv420 else FRAME_RGBA8 if rgba8 else FRAME_F32
 
 
 def srgb10_thresholds():

@@ -29,7 +29,7 @@ import sys
 import numpy as np
 
 import geodesic_raytracing_amd as gra
-from geodesic_raytracing_amd.pipeline import DeviceBuffer, PinnedBuffer, ProgramManager, Y4MWriter, yuv420_bytes, yuv420p10_bytes
+from geodesic_raytracing_amd.pipeline import FRAME_FORMATS, DeviceBuffer, PinnedBuffer, ProgramManager, Y4MWriter, frame_format_of
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -164,6 +164,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
         raise ValueError("render: cameras (interpolated poses) and geodesic_speed (a camera on its geodesic) exclude each other")
     if filter not in gra.FILTER_NAMES and filter not in gra.FILTER_NAMES.values():
         raise ValueError(f"render: filter={filter!r} ({', '.join(gra.FILTER_NAMES)})")
+    frame_format = frame_format_of(rgba8, yuv420, bit_depth)
+    fmt = FRAME_FORMATS[frame_format]
     shutter_samples = int(shutter_samples)
     if shutter_samples:
         moving = cameras if cameras is not None else geodesic_times if geodesic_speed is not None else None
@@ -182,45 +184,35 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     else:
         packed, levels = gra.pack_background(rgba)
         dbg = DeviceBuffer.from_numpy(device, packed)
-    deep = bool(yuv420) and bit_depth == 10
-    out_bytes = yuv420p10_bytes(width, height) if deep else yuv420_bytes(width, height) if yuv420 else width * height * (4 if rgba8 else 16)
+    out_bytes = fmt.bytes(width, height)
     out = DeviceBuffer(device, out_bytes)
-    pinned = PinnedBuffer(out_bytes) if rgba8 or yuv420 else None
+    pinned = PinnedBuffer(out_bytes) if frame_format != gra.FRAME_F32 else None   # (a float frame is downloaded as it always was)
     cam = gra.default_camera(camera_pos, camera_quat)
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
     bg = (dbg.ptr, rgba.shape[1], rgba.shape[0], levels)
 
     def fetch():
+        if pinned is None:
+            state.synchronize()
+            return out.to_numpy(fmt.dtype, fmt.shape(width, height))
         pinned.download_async(None, out.ptr, out_bytes)   # the frame's stream: copies queue behind its launches
         gra.check(gra.lib.gr_stream_synchronize(None))
-        if deep:
-            return pinned.view(np.uint16, (out_bytes // 2,)).copy()
-        return pinned.view(np.uint8, (out_bytes,) if yuv420 else (height, width, 4)).copy()
+        return pinned.view(fmt.dtype, fmt.shape(width, height)).copy()
 
     weight = np.float32(1) / np.float32(shutter_samples) if shutter_samples else None
     subframe = [0]   # sub-frames of the current shutter rendered so far
 
     def one_frame(options, cam=cam):
-        if shutter_samples:   # a sub-frame: accumulated on the device; the last one of a shutter delivers
-            state.render_subframe(program, metric, cam, weight, subframe[0] == 0, bg, feats, cfg_values, options)
-            subframe[0] = (subframe[0] + 1) % shutter_samples
-            if subframe[0]:
-                return None
-            state.deliver_accumulated(program, out.ptr, gra.FRAME_YUV420P10 if deep else gra.FRAME_YUV420 if yuv420 else gra.FRAME_RGBA8 if rgba8 else gra.FRAME_F32)
-            if pinned is not None:
-                return fetch()
-            state.synchronize()
-            return out.to_numpy(np.float32, (height, width, 4))
-        if deep:
-            state.render_yuv420p10(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
-        elif yuv420:
-            state.render_yuv420(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
-        elif rgba8:
-            state.render_rgba8(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
-        else:
-            state.render(program, metric, cam, out.ptr, bg, feats, cfg_values, options)
-            state.synchronize()
-            return out.to_numpy(np.float32, (height, width, 4))
+        if not shutter_samples:
+            state.render(program, metric, cam, out.ptr, bg, feats, cfg_values, options, rgba8=rgba8, yuv420=gra.YUV420_I420 if yuv420 else None,
+                         bit_depth=bit_depth)
+            return fetch()
+        # a sub-frame: accumulated on the device; the last one of a shutter delivers
+        state.render_subframe(program, metric, cam, weight, subframe[0] == 0, bg, feats, cfg_values, options)
+        subframe[0] = (subframe[0] + 1) % shutter_samples
+        if subframe[0]:
+            return None
+        state.deliver_accumulated(program, out.ptr, frame_format)
         return fetch()
 
     def frames_of_the_call():
