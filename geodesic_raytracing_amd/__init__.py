@@ -338,6 +338,15 @@ _SIGNATURES = {
     "gr_resolve_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
     "gr_render_state_set_filter": (c_int, [c_void_p, c_int]),
     "gr_render_state_filter": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "gr_png_encode_bound": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "gr_png_encode_rgba8_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
+    "gr_png_build_table": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
+    "gr_png_encoder_create": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "gr_png_encoder_destroy": (None, [c_void_p]),
+    "gr_png_encode_rgba8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
+    "gr_png_encoder_time_launches": (c_int, [c_void_p, c_int]),
+    "gr_png_encoder_launch_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
+    "gr_png_encoder_scratch_intact": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
 }
 
 for _name, (_res, _args) in _SIGNATURES.items():
@@ -361,4 +370,4 @@ def check(rc):
 from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, build_background,  # noqa: E402,F401
                        default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background, rgba8_to_yuv420,
                        yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes, accumulate_frame, filter_taps,
-                       filter_frame)
+                       filter_frame, PngEncoder, png_encode_bound, png_encode_host)

@@ -33,6 +33,7 @@
 #include "frame_format.hpp"
 #include "jsfront.hpp"
 #include "metric_codegen.hpp"
+#include "png_stream.hpp"
 #include "program_build.hpp"
 
 namespace {
@@ -76,20 +77,22 @@ const char* const KERNEL_NAMES[] = {
     "gr_do_generic_rays", "gr_calculate_singularities", "gr_calculate_render_data",
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
-    "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered"};
+    "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_COUNT
 };
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
 // filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and 8- and 10-bit Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
-// (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation
+// (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation - and the two integer kernels of the
+// PNG encoder (kernels/png.hip), which want no part in it either
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
-           k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE || k == K_RESOLVE_FILTERED;
+           k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE || k == K_RESOLVE_FILTERED ||
+           k == K_PNG_HISTOGRAM || k == K_PNG_PACK;
 }
 
 namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files
@@ -1275,6 +1278,174 @@ int gr_build_mipped_background(gr_program* p, void* stream, const void* rgba8, i
     void* args[] = {&rgba8, &scratch, &packed_out, &width, &height, &levels_arg, &in_place_arg};
     rc = launch(p, K_BACKGROUND_SLICES, stream, blocks(((long long)width * height * levels + 3) / 4, 256), 1, 256, 1, args);
     return rc != GR_OK ? rc : levels;
+}
+
+// ---- PNG frames: the device encoder (kernels/png.hip; the stream and its host encoder: png_stream.cpp) ---------------------------
+
+struct gr_png_encoder {
+    gr_program* program = nullptr;
+    int width = 0, height = 0;
+    // device: [frame histogram 256 | rows' histograms height x 256 | rows' sums height x 2] words, downloaded in one copy ...
+    unsigned int* statistics = nullptr;
+    size_t statistics_words = 0;
+    // ... [rows' offsets height + 1, 64 bit | table 257 | header png_stream::HEADER_WORDS] uploaded in one copy ...
+    unsigned char* placement = nullptr;
+    unsigned char* placement_host = nullptr;   // (pinned)
+    size_t placement_bytes = 0;
+    // ... and the stream: GUARD_WORDS, then stream_capacity_words, then GUARD_WORDS, all filled with GUARD_PATTERN at creation; an encode
+    // zeroes the words its stream takes and nothing else
+    static const size_t GUARD_WORDS = 64;
+    static const unsigned int GUARD_PATTERN = 0xa5c3e1f7u;
+    unsigned int* scratch = nullptr;
+    size_t stream_capacity_words = 0, most_stream_words = 0;   // (the longest stream of any encode so far)
+    unsigned char* staging = nullptr;   // pinned: the statistics, then the stream
+    size_t staging_bytes = 0;
+    bool time_launches = false, timed = false;
+    hipEvent_t events[4] = {};
+    ~gr_png_encoder() {
+        if (program) (void)hipSetDevice(program->device);
+        if (statistics) (void)hipFree(statistics);
+        if (placement) (void)hipFree(placement);
+        if (scratch) (void)hipFree(scratch);
+        if (placement_host) (void)hipHostFree(placement_host);
+        if (staging) (void)hipHostFree(staging);
+        for (hipEvent_t e : events)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+int gr_png_encoder_create(gr_program* p, int width, int height, gr_png_encoder** out) {
+    const std::string who = "gr_png_encoder_create: ";
+    if (!p || !out) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
+    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
+    const uint64_t rows_bound = png_stream::rows_bound(width, height);
+    if (!rows_bound) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a frame of more than 2^31 - 1 raw bytes");
+    HIP_CHECK(hipSetDevice(p->device));
+    auto e = std::make_unique<gr_png_encoder>();
+    e->program = p;
+    e->width = width;
+    e->height = height;
+    e->statistics_words = 256 + (size_t)height * 258;
+    e->placement_bytes = ((size_t)height + 1) * 8 + (png_stream::SYMBOLS + png_stream::HEADER_WORDS) * 4;
+    e->stream_capacity_words = (size_t)((rows_bound + 3) / 4);
+    e->staging_bytes = std::max(e->statistics_words * 4, e->stream_capacity_words * 4);
+    const size_t scratch_words = e->stream_capacity_words + 2 * gr_png_encoder::GUARD_WORDS;
+    HIP_CHECK(hipMalloc((void**)&e->statistics, e->statistics_words * 4));
+    HIP_CHECK(hipMalloc((void**)&e->placement, e->placement_bytes));
+    HIP_CHECK(hipMalloc((void**)&e->scratch, scratch_words * 4));
+    HIP_CHECK(hipHostMalloc((void**)&e->placement_host, e->placement_bytes, hipHostMallocDefault));
+    HIP_CHECK(hipHostMalloc((void**)&e->staging, e->staging_bytes, hipHostMallocDefault));
+    HIP_CHECK(hipMemsetD32((hipDeviceptr_t)e->scratch, (int)gr_png_encoder::GUARD_PATTERN, scratch_words));
+    HIP_CHECK(hipDeviceSynchronize());
+    *out = e.release();
+    return GR_OK;
+}
+
+void gr_png_encoder_destroy(gr_png_encoder* e) { delete e; }
+
+int gr_png_encoder_time_launches(gr_png_encoder* e, int on) {
+    if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_png_encoder_time_launches: a required pointer is NULL");
+    HIP_CHECK(hipSetDevice(e->program->device));
+    if (on)
+        for (hipEvent_t& event : e->events)
+            if (!event) HIP_CHECK(hipEventCreate(&event));
+    e->time_launches = on != 0;
+    e->timed = false;
+    return GR_OK;
+}
+
+int gr_png_encoder_launch_ms(gr_png_encoder* e, float ms[2]) {
+    if (!e || !ms) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_png_encoder_launch_ms: a required pointer is NULL");
+    if (!e->timed) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_png_encoder_launch_ms: no encode was timed (gr_png_encoder_time_launches)");
+    HIP_CHECK(hipEventElapsedTime(&ms[0], e->events[0], e->events[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms[1], e->events[2], e->events[3]));
+    return GR_OK;
+}
+
+int gr_png_encoder_scratch_intact(gr_png_encoder* e, int* intact) {
+    if (!e || !intact) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_png_encoder_scratch_intact: a required pointer is NULL");
+    HIP_CHECK(hipSetDevice(e->program->device));
+    const size_t G = gr_png_encoder::GUARD_WORDS, words = e->stream_capacity_words + 2 * G;
+    std::vector<unsigned int> host(words);
+    HIP_CHECK(hipMemcpy(host.data(), e->scratch, words * 4, hipMemcpyDeviceToHost));
+    *intact = 1;
+    for (size_t i = 0; i < words; i++)
+        if ((i < G || i >= G + e->most_stream_words) && host[i] != gr_png_encoder::GUARD_PATTERN) *intact = 0;
+    return GR_OK;
+}
+
+int gr_png_encode_rgba8(gr_png_encoder* e, void* stream, const void* device_rgba8, unsigned char* out_file, size_t capacity, size_t* out_bytes) {
+    const std::string who = "gr_png_encode_rgba8: ";
+    if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
+    bool too_small = false;
+    const std::string wrong = png_stream::refusal(device_rgba8, e->width, e->height, out_file, capacity, out_bytes, &too_small);
+    if (!wrong.empty()) return fail(too_small ? GR_ERROR_BUFFER_TOO_SMALL : GR_ERROR_INVALID_ARGUMENT, who + wrong);
+    gr_program* p = e->program;
+    const int width = e->width, height = e->height;
+    hipStream_t on = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(p->device));
+    // the first round trip: the frame's and the rows' histograms, the rows' Adler sums
+    unsigned int* frame_histogram = e->statistics;
+    unsigned int* row_histogram = e->statistics + 256;
+    unsigned int* row_sums = row_histogram + (size_t)height * 256;
+    HIP_CHECK(hipMemsetAsync(frame_histogram, 0, 256 * 4, on));
+    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[0], on));
+    {
+        int w = width, h = height;
+        void* args[] = {&device_rgba8, &w, &h, &frame_histogram, &row_histogram, &row_sums};
+        int rc = launch(p, K_PNG_HISTOGRAM, stream, (unsigned)height, 1, 64, 4, args);
+        if (rc != GR_OK) return rc;
+    }
+    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[1], on));
+    HIP_CHECK(hipMemcpyAsync(e->staging, e->statistics, e->statistics_words * 4, hipMemcpyDeviceToHost, on));
+    HIP_CHECK(hipStreamSynchronize(on));
+    // the table from the frame's histogram - with what the device does not count: a filter-type byte and an end-of-block a row -, the rows'
+    // offsets from their own histograms, the Adler-32 from their sums
+    const unsigned int* got = (const unsigned int*)e->staging;
+    uint64_t histogram[png_stream::SYMBOLS];
+    for (int v = 0; v < 256; v++) histogram[v] = got[v];
+    histogram[1] += 1;
+    histogram[2] += (uint64_t)height - 1;
+    histogram[png_stream::END_OF_BLOCK] = (uint64_t)height;
+    png_stream::table t;
+    png_stream::build_table(histogram, t);
+    uint64_t* offset = (uint64_t*)e->placement_host;
+    unsigned int* table_words = (unsigned int*)(e->placement_host + ((size_t)height + 1) * 8);
+    unsigned int* header_words = table_words + png_stream::SYMBOLS;
+    std::vector<uint32_t> adlers(height);
+    offset[0] = 0;
+    for (int r = 0; r < height; r++) {
+        offset[r + 1] = offset[r] + png_stream::row_segment_bytes(png_stream::row_block_bits(t, r, got + 256 + (size_t)r * 256));
+        const unsigned int* sums = got + 256 + (size_t)height * 256 + 2 * (size_t)r;
+        adlers[r] = png_stream::row_adler(r, width, sums[0], sums[1]);
+    }
+    const uint64_t rows_bytes = offset[height], stream_words = (rows_bytes + 3) / 4;
+    if (stream_words > e->stream_capacity_words) return fail(GR_ERROR_DEVICE, who + "the rows' sizes exceed the bound (the device's histograms are not a frame's)");
+    for (int s = 0; s < png_stream::SYMBOLS; s++) table_words[s] = (unsigned int)t.code[s] | ((unsigned int)t.length[s] << 16);
+    std::copy(t.header, t.header + png_stream::HEADER_WORDS, header_words);
+    // the second: placement up, the stream zeroed (the pack ORs the words segments share), the pack, the stream down
+    unsigned int* stream_at = e->scratch + gr_png_encoder::GUARD_WORDS;
+    HIP_CHECK(hipMemcpyAsync(e->placement, e->placement_host, e->placement_bytes, hipMemcpyHostToDevice, on));
+    HIP_CHECK(hipMemsetAsync(stream_at, 0, (size_t)stream_words * 4, on));
+    e->most_stream_words = std::max(e->most_stream_words, (size_t)stream_words);
+    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[2], on));
+    {
+        int w = width, h = height, header_bits = t.header_bits;
+        const unsigned long long* offsets_on_device = (const unsigned long long*)e->placement;
+        const unsigned int* table_on_device = (const unsigned int*)(e->placement + ((size_t)height + 1) * 8);
+        const unsigned int* header_on_device = table_on_device + png_stream::SYMBOLS;
+        unsigned long long word_count = stream_words;
+        void* args[] = {&device_rgba8, &w, &h, &table_on_device, &header_on_device, &header_bits, &offsets_on_device, &stream_at, &word_count};
+        int rc = launch(p, K_PNG_PACK, stream, (unsigned)height, 1, 64, 4, args);
+        if (rc != GR_OK) return rc;
+    }
+    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[3], on));
+    HIP_CHECK(hipMemcpyAsync(e->staging, stream_at, (size_t)stream_words * 4, hipMemcpyDeviceToHost, on));
+    HIP_CHECK(hipStreamSynchronize(on));
+    e->timed = e->time_launches;
+    png_stream::write_container(out_file, width, height, e->staging, rows_bytes, png_stream::join_adler(adlers.data(), width, height));
+    *out_bytes = (size_t)png_stream::file_bytes(rows_bytes);
+    return GR_OK;
 }
 
 int gr_internal_fail(int code, const char* msg) { return fail((gr_status)code, msg ? msg : ""); }

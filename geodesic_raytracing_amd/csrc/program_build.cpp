@@ -215,10 +215,10 @@ const char* const KERNEL_PARTS[] = {"program.hip",       // structs of the bound
                                     "trace.hip",         // render-data, the reference-shaped and the fused kernels, prepass, tile order, adaptive sampling
                                     "shading.hip"};      // texture sampling, gr_render
 // ... and the set-up module's: what runs once per frame on one lane (camera.hip, geodesic_camera.hip), the box filter of a supersampled
-// frame, the separable filters that replace it (filter.hip), the shutter's accumulation (which uses the box), the encodes and the sky's
-// mip slices
+// frame, the separable filters that replace it (filter.hip), the shutter's accumulation (which uses the box), the encodes, the sky's
+// mip slices and the PNG encoder's two kernels
 const char* const PARTS[] = {"program.hip", "probes.inc", "metric.hip", "setup.hip", "camera.hip", "geodesic_camera.hip", "resolve.hip",
-                             "filter.hip", "shutter.hip", "present.hip", "background.hip"};
+                             "filter.hip", "shutter.hip", "present.hip", "background.hip", "png.hip"};
 }   // namespace
 
 bool read_file(const std::string& path, std::string& out) {

@@ -382,6 +382,73 @@ class PinnedBuffer:
             pass
 
 
+def png_encode_bound(width, height):
+    """the capacity both PNG encoders ask for (gr_png_encode_bound)"""
+    need = ctypes.c_size_t()
+    check(lib.gr_png_encode_bound(int(width), int(height), ctypes.byref(need)))
+    return need.value
+
+
+def png_encode_host(pixels):
+    """the PNG file of RGBA8 pixels [H, W, 4] as bytes, by the host encoder that defines PngEncoder's stream (gr_png_encode_rgba8_host:
+    Sub / Up filters, one Huffman table a frame, literals only)"""
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+    if pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ValueError(f"png_encode_host: an image of shape {pixels.shape} is not [H, W, 4]")
+    h, w = pixels.shape[:2]
+    out = np.empty(png_encode_bound(w, h), dtype=np.uint8)
+    size = ctypes.c_size_t()
+    check(lib.gr_png_encode_rgba8_host(pixels.ctypes.data_as(c_void_p), w, h, out.ctypes.data_as(c_void_p), out.nbytes, ctypes.byref(size)))
+    return out[:size.value].tobytes()
+
+
+class PngEncoder:
+    """A PNG encoder behind RGBA8 frames of one size that are already on the program's device (gr_png_encoder): filtering, histogram and
+    bit-packing run there, the compressed bytes come back.  encode() synchronises the stream it is given.  The program must outlive it."""
+
+    def __init__(self, program, width, height):
+        self.program, self.width, self.height = program, int(width), int(height)   # (the program is borrowed: kept alive here)
+        self.handle = c_void_p()
+        check(lib.gr_png_encoder_create(program.handle, self.width, self.height, ctypes.byref(self.handle)))
+        self._out = np.empty(png_encode_bound(self.width, self.height), dtype=np.uint8)
+
+    def encode(self, device_ptr, stream=None):
+        """the PNG file of the frame at device_ptr (width x height RGBA8 pixels) as bytes: png_encode_host's of the same pixels"""
+        size = ctypes.c_size_t()
+        check(lib.gr_png_encode_rgba8(self.handle, stream, device_ptr, self._out.ctypes.data_as(c_void_p), self._out.nbytes, ctypes.byref(size)))
+        return self._out[:size.value].tobytes()
+
+    def write(self, path, device_ptr, stream=None):
+        """encode() into a file; returns its size"""
+        data = self.encode(device_ptr, stream)
+        with open(path, "wb") as f:
+            f.write(data)
+        return len(data)
+
+    def time_launches(self, on=True):
+        check(lib.gr_png_encoder_time_launches(self.handle, int(bool(on))))
+
+    def launch_ms(self):
+        """(gr_png_histogram, gr_png_pack) of the last encode after time_launches(), in milliseconds"""
+        ms = (c_float * 2)()
+        check(lib.gr_png_encoder_launch_ms(self.handle, ms))
+        return ms[0], ms[1]
+
+    def scratch_intact(self):
+        """True when nothing outside the longest stream this encoder has made was written in its stream scratch, the guard words included"""
+        intact = c_int()
+        check(lib.gr_png_encoder_scratch_intact(self.handle, ctypes.byref(intact)))
+        return bool(intact.value)
+
+    def close(self):
+        handle, self.handle = getattr(self, "handle", None), None
+        if handle:
+            lib.gr_png_encoder_destroy(handle)
+
+    def __del__(self):
+        self.close()
+
+
 class RenderState:
     """Per-frame device buffers + the frame sequence (render_state.hpp:97-197, main.cpp:2244-2526)."""
 

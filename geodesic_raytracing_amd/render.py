@@ -4,6 +4,8 @@
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 1920x1080 --supersample 2 --out kerr_ss2.png
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --encode device --out kerr_4k.png
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --background sky.png --mips device --out kerr_sky.png
+    # the PNG itself made on the device (filter, histogram, Huffman coding): only the compressed bytes come back
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --png device --out kerr_4k.png
     # one frame over four GPUs (one process, peer copies): every device traces its rows at 4 x 4 rays a pixel and ships them as 8-bit sRGB
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --devices 0,1,2,3 --supersample 4 --encode device --out poster.png
     python -m geodesic_raytracing_amd.render --metric alcubierre --redshift --camera 0,0,-6,0.5 --background sky.png --out warp.png
@@ -53,6 +55,12 @@ def write_rgba8_png(path, pixels):
     pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
     h, w = pixels.shape[:2]
     gra.check(gra.lib.gr_write_png_rgba8(path.encode(), pixels.ctypes.data_as(ctypes.c_void_p), w, h))
+
+
+def write_png_bytes(path, data):
+    """a PNG file that is already encoded (render(png="device"), pipeline.PngEncoder.encode)"""
+    with open(path, "wb") as f:
+        f.write(data)
 
 
 def parse_fps(text):
@@ -134,7 +142,8 @@ def camera_path_at(position, quat, position_to=None, quat_to=None, frames=1, tim
 
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
-           parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box"):
+           parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box",
+           png="host"):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
@@ -155,9 +164,14 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     pipeline.filter_taps' table of the frame a plain state of the traced size renders, bit for bit), at any supersample, 1 included, and
     in every format; sub-frames of a shutter are filtered before they are accumulated.
     mips: where the sky's mip slices are made - "host" (pack_background, all slices uploaded) or "device" (build_background: the image is
-    uploaded and the slices are built there, the same bytes)."""
+    uploaded and the slices are built there, the same bytes).
+    png: "device" (with rgba8) - every frame returned is the bytes of a finished PNG file instead of pixels: the RGBA8 frame stays on the
+    device, is filtered, histogrammed and bit-packed there (pipeline.PngEncoder) and only the compressed bytes come back - the file
+    pipeline.png_encode_host makes of the rgba8 frame, byte for byte."""
     if mips not in ("host", "device"):
         raise ValueError(f"render: mips={mips!r} (host or device)")
+    if png not in ("host", "device") or (png == "device" and (not rgba8 or yuv420)):
+        raise ValueError(f"render: png={png!r} (host, or device with rgba8=True and no yuv420)")
     if bit_depth not in (8, 10) or (bit_depth == 10 and not yuv420):
         raise ValueError(f"render: bit_depth={bit_depth!r} (8, or 10 with yuv420=True)")
     if cameras is not None and geodesic_speed is not None:
@@ -186,12 +200,15 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
         dbg = DeviceBuffer.from_numpy(device, packed)
     out_bytes = fmt.bytes(width, height)
     out = DeviceBuffer(device, out_bytes)
-    pinned = PinnedBuffer(out_bytes) if frame_format != gra.FRAME_F32 else None   # (a float frame is downloaded as it always was)
+    encoder = gra.PngEncoder(program, width, height) if png == "device" else None
+    pinned = PinnedBuffer(out_bytes) if frame_format != gra.FRAME_F32 and encoder is None else None   # (a float frame is downloaded as it always was)
     cam = gra.default_camera(camera_pos, camera_quat)
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
     bg = (dbg.ptr, rgba.shape[1], rgba.shape[0], levels)
 
     def fetch():
+        if encoder is not None:
+            return encoder.encode(out.ptr, None)   # the frame's stream: the encoder's launches queue behind the frame's
         if pinned is None:
             state.synchronize()
             return out.to_numpy(fmt.dtype, fmt.shape(width, height))
@@ -252,14 +269,17 @@ def split_block_rows(height, block_rows=16):
 
 
 def render_split(metric_name, width, height, devices, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, background=None,
-                 fov=90.0, universe=20.0, wait_for_static=True, supersample=1, rgba8=False, mips="host", frames=1, block_rows=16):
+                 fov=90.0, universe=20.0, wait_for_static=True, supersample=1, rgba8=False, mips="host", frames=1, block_rows=16, png="host"):
     """render() of a Cartesian camera with the rows of every frame dealt to `devices` (TiledFrame.local: one process, peer copies, participant
     r on devices[r]; a device may be named more than once, which is how a box with one GPU rehearses it).  Every device has its own program,
     sky (with mips="device" built there, once per device) and render state, traces its share at `supersample` x per axis, resolves it
     there and ships width x rows pixels to devices[0] - float4, or with rgba8 4 bytes each (TiledFrame.render_as).  Frame k is rendered
-    with rotation k, so the shares go round over `frames`.  Returns the list of frames: the arrays render() returns, bit for bit."""
+    with rotation k, so the shares go round over `frames`.  Returns the list of frames: the arrays render() returns, bit for bit.  png="device"
+    (with rgba8): the finished frame on devices[0] is encoded there (pipeline.PngEncoder) and every frame returned is a PNG file's bytes."""
     if mips not in ("host", "device"):
         raise ValueError(f"render_split: mips={mips!r} (host or device)")
+    if png not in ("host", "device") or (png == "device" and not rgba8):
+        raise ValueError(f"render_split: png={png!r} (host, or device with rgba8=True)")
     devices = [int(d) for d in devices]
     if not devices:
         raise ValueError("render_split: no devices")
@@ -284,6 +304,7 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
         states = [gra.RenderState(width, height, d, supersample=supersample) for d in devices]
         out = DeviceBuffer(devices[0], width * height * (4 if rgba8 else 16))
         cam = gra.default_camera(camera_pos, camera_quat)
+        encoder = gra.PngEncoder(programs[devices[0]], width, height) if png == "device" else None
         result = []
         for k in range(max(int(frames), 1)):
             for r, d in enumerate(devices):
@@ -291,7 +312,7 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
                                    rotation=k, rgba8=rgba8)
             parts[0].join()
             gra.check(gra.lib.gr_device_synchronize(devices[0]))
-            result.append(out.to_numpy(np.uint8 if rgba8 else np.float32, (height, width, 4)))
+            result.append(encoder.encode(out.ptr, None) if encoder is not None else out.to_numpy(np.uint8 if rgba8 else np.float32, (height, width, 4)))
         return result
     finally:
         for part in parts:
@@ -325,6 +346,9 @@ def main(argv=None):
     ap.add_argument("--encode", choices=["host", "device"], default="host", help="where the frame becomes 8-bit sRGB: host = download float4 and "
                     "convert there; device = encode on the GPU and download 4 bytes a pixel (the same bytes).  Ignored for --out NAME.y4m, "
                     "whose frames are always encoded on the device")
+    ap.add_argument("--png", choices=["host", "device"], default="host", help="where a frame becomes a PNG file: host = the pixels come back and one host "
+                    "thread deflates them; device = the 8-bit frame is filtered, histogrammed and Huffman-coded on the GPU (Sub / Up filters, one "
+                    "table a frame, no matches) and only the compressed bytes come back.  device implies --encode device; not with --out NAME.y4m")
     ap.add_argument("--mips", choices=["host", "device"], default="host", help="where the sky's mip slices are made: host = pack them on the CPU "
                     "and upload all of them; device = upload the image and build the slices on the GPU (the same bytes)")
     ap.add_argument("--device", type=int, default=0)
@@ -353,6 +377,10 @@ def main(argv=None):
         ap.error(f"--fps: {e}")
     if a.bit_depth != 8 and not video:
         ap.error("--bit-depth 10 is a depth of video frames: it needs --out NAME.y4m (a PNG is 8-bit sRGB)")
+    if a.png == "device":
+        if video:
+            ap.error("--png device with --out NAME.y4m: a video file holds no PNG; --png is about --out NAME.png")
+        a.encode = "device"
     if a.shutter_samples is not None and a.shutter is None:
         ap.error("--shutter-samples without --shutter: the sub-frames are those of a shutter; give its open fraction, e.g. --shutter 0.5")
     if a.shutter is not None:
@@ -381,7 +409,7 @@ def main(argv=None):
     speed = [float(v) for v in a.geodesic_speed.split(",")] if a.geodesic_speed else None
     times = [a.geodesic_time + i * a.geodesic_dt for i in range(max(a.frames, 1))]
     moments = shutter_times(max(a.frames, 1), a.shutter, samples).ravel() if samples else None   # frame numbers, `samples` a frame
-    write = write_rgba8_png if a.encode == "device" else write_frame_png
+    write = write_png_bytes if a.png == "device" else write_rgba8_png if a.encode == "device" else write_frame_png
     if a.devices is not None:
         try:
             devices = [int(v) for v in a.devices.split(",")]
@@ -395,7 +423,7 @@ def main(argv=None):
             ap.error("--geodesic-speed with --devices: a split frame takes a Cartesian camera")
         result = render_split(a.metric, w, h, devices, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
                               [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, read_png(a.background) if a.background else None,
-                              a.fov, a.universe, supersample=a.supersample, rgba8=a.encode == "device", mips=a.mips, frames=a.frames)
+                              a.fov, a.universe, supersample=a.supersample, rgba8=a.encode == "device", mips=a.mips, frames=a.frames, png=a.png)
         stem, ext = os.path.splitext(a.out)
         for i, frame in enumerate(result):
             path = a.out if len(result) == 1 else f"{stem}_{i:03d}{ext}"
@@ -415,7 +443,7 @@ def main(argv=None):
                     geodesic_times=[a.geodesic_time + float(t) * a.geodesic_dt for t in moments] if samples else times,
                     parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
                     rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples,
-                    filter=a.filter)
+                    filter=a.filter, png=a.png)
     if speed is None and cameras is None:
         result = [result]
     if video:

@@ -302,6 +302,56 @@ int gr_resolve_filtered(gr_program* p, void* stream, const void* src, void* dst,
 int gr_render_state_set_filter(gr_render_state* s, int filter);
 int gr_render_state_filter(const gr_render_state* s, int* filter);
 
+/* ---- PNG frames -----------------------------------------------------------------------------------------------------------------------
+ * A PNG encoder behind an RGBA8 frame that is already in device memory (gr_render_frame_rgba8, gr_deliver_accumulated(GR_FRAME_RGBA8),
+ * participant 0's frame of gr_render_frame_tiled_as): filtering, histogram and bit-packing run on the device (kernels/png.hip, set-up
+ * module), only the compressed bytes come back.  A sink, not a fifth GR_FRAME_* format: a compressed size is no function of width and height.
+ * gr_write_png_rgba8 (geodesic_hip.h) stays as it is.  (Declared here and not in geodesic_hip.h only because the contract header keeps to 80
+ * names and 350 lines; all of this is public.)
+ *
+ * The stream is fixed, so that host and device write the same bytes:
+ *   container   8 bit, colour type 6 (RGBA), no interlace; one IDAT where the zlib stream is below 2^31 - 1 bytes, otherwise several
+ *   row filters row 0 is filter type 1 (Sub, bpp = 4), every other row type 2 (Up): a filtered byte depends on one other byte of the frame
+ *   zlib        78 01, one deflate segment per row, then 03 00 (a final empty fixed block) and the big-endian Adler-32
+ *   segment     one non-final dynamic-Huffman block - the frame's block header (the same bits for every row), the codes of the filter byte
+ *               and the row's 4 * width filtered bytes, end-of-block - then an empty stored block: three 0 bits, 0 bits up to a byte
+ *               boundary, 00 00 FF FF.  Segments therefore meet at byte boundaries and concatenate byte-wise.  Literals only, no matches.
+ *   table       one literal/length code per frame, from the frame's histogram of filtered bytes (filter bytes included) plus one
+ *               end-of-block a row: Huffman's lengths (ties: the node made first, leaves in symbol order), lengths above 15 moved to 15
+ *               and the code made complete again (one leaf of the deepest level dropped a level at a time), the shortest lengths dealt to
+ *               the commonest symbols (ties: the lower symbol); canonical codes.  A histogram with fewer than two symbols gets the
+ *               lowest-numbered others as leaves that never occur (two leaves of one bit).  HLIT = 257, HDIST = 1 with the one distance
+ *               length 0 (RFC 1951 3.2.7: no distance codes, literals only); the 258 lengths run-length coded (16, 17, 18) and coded
+ *               with lengths limited to 7 in the same way.
+ *   checksums   the Adler-32 is joined from the rows' (adler32_combine), the chunk CRCs are taken on the host over the finished bytes. */
+typedef struct gr_png_encoder gr_png_encoder;
+/* What a file of this size never exceeds (every literal 15 bits, a block header of 512 bytes a row): the capacity both encoders ask for. */
+int gr_png_encode_bound(int width, int height, size_t* bytes);
+/* The host encoder: the definition of the bytes above.  rgba8: [height][width][4] bytes, R, G, B, A; *out_bytes: the file's size.  Both
+ * encoders refuse, before anything is written or any device call is made, with a message that names the entry point: a NULL; a size below 1; a
+ * frame pointer not aligned to 4 bytes; a frame of more than 2^31 - 1 raw bytes (4 a pixel); a capacity below gr_png_encode_bound
+ * (GR_ERROR_BUFFER_TOO_SMALL; everything else GR_ERROR_INVALID_ARGUMENT).  out_file needs no alignment. */
+int gr_png_encode_rgba8_host(const unsigned char* rgba8, int width, int height, unsigned char* out_file, size_t capacity, size_t* out_bytes);
+/* The table builder on its own: histogram[257] (literals, then end-of-block; a 0 there is taken as 1) to lengths[257], codes[257] (bit-reversed:
+ * written from bit 0 up), the block header as bits from bit 0 of header_words[0] up (128 words) and its bit count. */
+int gr_png_build_table(const unsigned long long* histogram, unsigned char* lengths, unsigned short* codes, unsigned int* header_words, int* header_bits);
+/* A device encoder for frames of one size on the program's device: owns the device scratch (the rows' histograms and Adler sums, the table,
+ * the rows' offsets, the stream) and a pinned staging buffer of gr_png_encode_bound bytes.  The program is borrowed and must outlive it. */
+int gr_png_encoder_create(gr_program* p, int width, int height, gr_png_encoder** out);
+void gr_png_encoder_destroy(gr_png_encoder* e);
+/* Encodes device_rgba8 (device memory, width x height pixels) into out_file (host memory): enqueues on `stream` - gr_png_histogram, one
+ * download of the rows' histograms and Adler sums (1 KiB + 1 032 bytes a row), the table and the rows' offsets built on the host and
+ * uploaded, the stream zeroed, gr_png_pack, the download of the compressed bytes - and returns after the file's bytes are in out_file: it
+ * SYNCHRONISES that stream, twice.  The file is gr_png_encode_rgba8_host's of the same pixels, byte for byte. */
+int gr_png_encode_rgba8(gr_png_encoder* e, void* stream, const void* device_rgba8, unsigned char* out_file, size_t capacity, size_t* out_bytes);
+/* Measurement and tests.  _time_launches: with on != 0 every later encode brackets its two launches with events; _launch_ms: the last such
+ * encode's gr_png_histogram and gr_png_pack in milliseconds.  _scratch_intact: *intact = 1 when every word of the stream scratch outside the
+ * longest stream this encoder has made - the guard words in front of it and everything behind it - still holds what gr_png_encoder_create
+ * wrote there. */
+int gr_png_encoder_time_launches(gr_png_encoder* e, int on);
+int gr_png_encoder_launch_ms(gr_png_encoder* e, float ms[2]);
+int gr_png_encoder_scratch_intact(gr_png_encoder* e, int* intact);
+
 /* ---- fused MI355X path (no reference counterpart) ------------------------------------------- */
 
 /* Prepass termination flags from one fused trace at prepass resolution (replaces the sequence
