@@ -31,6 +31,7 @@
 #include "builtin_metrics.hpp"
 #include "codeobject.hpp"
 #include "frame_format.hpp"
+#include "jpeg_stream.hpp"
 #include "jsfront.hpp"
 #include "metric_codegen.hpp"
 #include "png_stream.hpp"
@@ -77,22 +78,23 @@ const char* const KERNEL_NAMES[] = {
     "gr_do_generic_rays", "gr_calculate_singularities", "gr_calculate_render_data",
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
-    "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack"};
+    "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack",
+    "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_JPEG_BLOCKS, K_JPEG_PACK, K_JPEG_GATHER, K_COUNT
 };
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
 // filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and 8- and 10-bit Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
 // (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation - and the two integer kernels of the
-// PNG encoder (kernels/png.hip), which want no part in it either
+// PNG encoder (kernels/png.hip) and the three of the JPEG encoder (kernels/jpeg.hip), which want no part in it either
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
            k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE || k == K_RESOLVE_FILTERED ||
-           k == K_PNG_HISTOGRAM || k == K_PNG_PACK;
+           k == K_PNG_HISTOGRAM || k == K_PNG_PACK || k == K_JPEG_BLOCKS || k == K_JPEG_PACK || k == K_JPEG_GATHER;
 }
 
 namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files
@@ -1445,6 +1447,162 @@ int gr_png_encode_rgba8(gr_png_encoder* e, void* stream, const void* device_rgba
     e->timed = e->time_launches;
     png_stream::write_container(out_file, width, height, e->staging, rows_bytes, png_stream::join_adler(adlers.data(), width, height));
     *out_bytes = (size_t)png_stream::file_bytes(rows_bytes);
+    return GR_OK;
+}
+
+// ---- JPEG frames: the device encoder (kernels/jpeg.hip; the stream and its host encoder: jpeg_stream.cpp) ------------------------
+
+struct gr_jpeg_encoder {
+    gr_program* program = nullptr;
+    int width = 0, height = 0, quality = 0;
+    // device: one allocation of 32-bit words, every region with GUARD_WORDS in front of it and behind the last, all filled with
+    // GUARD_PATTERN at creation - [coefficients | rows' slots | rows' byte counts, rows' FF counts, the file's size (64 bit) | file];
+    // the file region starts with the headers, uploaded at creation and never written again
+    static const size_t GUARD_WORDS = 64;
+    static const unsigned int GUARD_PATTERN = 0xa5c3e1f7u;
+    unsigned int* scratch = nullptr;
+    size_t region_at[4] = {}, region_words[4] = {}, scratch_words = 0;
+    size_t most_file_bytes = jpeg_stream::HEADER_BYTES;   // (the longest file of any encode so far)
+    unsigned int* tables = nullptr;    // jpeg_stream::device_tables
+    unsigned char* staging = nullptr;  // pinned: the file's size, then the file
+    uint64_t file_capacity = 0;
+    bool time_launches = false, timed = false;
+    hipEvent_t events[4] = {};
+    ~gr_jpeg_encoder() {
+        if (program) (void)hipSetDevice(program->device);
+        if (scratch) (void)hipFree(scratch);
+        if (tables) (void)hipFree(tables);
+        if (staging) (void)hipHostFree(staging);
+        for (hipEvent_t e : events)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+int gr_jpeg_encoder_create(gr_program* p, int width, int height, int quality, gr_jpeg_encoder** out) {
+    const std::string who = "gr_jpeg_encoder_create: ";
+    if (!p || !out) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
+    std::string wrong = jpeg_stream::size_refusal(width, height);
+    if (wrong.empty()) wrong = jpeg_stream::quality_refusal(quality);
+    if (!wrong.empty()) return fail(GR_ERROR_INVALID_ARGUMENT, who + wrong);
+    HIP_CHECK(hipSetDevice(p->device));
+    auto e = std::make_unique<gr_jpeg_encoder>();
+    e->program = p;
+    e->width = width;
+    e->height = height;
+    e->quality = quality;
+    const size_t rows = (size_t)jpeg_stream::mcu_rows(height), across = (size_t)jpeg_stream::mcus_across(width);
+    e->file_capacity = jpeg_stream::file_bound(width, height);
+    const size_t words[4] = {rows * across * jpeg_stream::BLOCKS_PER_MCU * 32, rows * (size_t)(jpeg_stream::row_slot_bytes(width) / 4), 2 * rows + 2,
+                             (size_t)((e->file_capacity + 3) / 4)};
+    size_t at = gr_jpeg_encoder::GUARD_WORDS;
+    for (int r = 0; r < 4; r++) {   // (every region starts at a multiple of 16 bytes)
+        e->region_at[r] = at;
+        e->region_words[r] = (words[r] + 3) / 4 * 4;
+        at += e->region_words[r] + gr_jpeg_encoder::GUARD_WORDS;
+    }
+    e->scratch_words = at;
+    HIP_CHECK(hipMalloc((void**)&e->scratch, e->scratch_words * 4));
+    HIP_CHECK(hipMalloc((void**)&e->tables, jpeg_stream::TABLE_WORDS * 4));
+    HIP_CHECK(hipHostMalloc((void**)&e->staging, 8 + e->region_words[3] * 4, hipHostMallocDefault));
+    HIP_CHECK(hipMemsetD32((hipDeviceptr_t)e->scratch, (int)gr_jpeg_encoder::GUARD_PATTERN, e->scratch_words));
+    uint32_t tables[jpeg_stream::TABLE_WORDS];
+    uint8_t headers[jpeg_stream::HEADER_BYTES];
+    jpeg_stream::device_tables(quality, tables);
+    jpeg_stream::write_headers(headers, width, height, quality);
+    HIP_CHECK(hipMemcpy(e->tables, tables, sizeof(tables), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(e->scratch + e->region_at[3], headers, sizeof(headers), hipMemcpyHostToDevice));
+    HIP_CHECK(hipDeviceSynchronize());
+    *out = e.release();
+    return GR_OK;
+}
+
+void gr_jpeg_encoder_destroy(gr_jpeg_encoder* e) { delete e; }
+
+int gr_jpeg_encoder_time_launches(gr_jpeg_encoder* e, int on) {
+    if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_jpeg_encoder_time_launches: a required pointer is NULL");
+    HIP_CHECK(hipSetDevice(e->program->device));
+    if (on)
+        for (hipEvent_t& event : e->events)
+            if (!event) HIP_CHECK(hipEventCreate(&event));
+    e->time_launches = on != 0;
+    e->timed = false;
+    return GR_OK;
+}
+
+int gr_jpeg_encoder_launch_ms(gr_jpeg_encoder* e, float ms[3]) {
+    if (!e || !ms) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_jpeg_encoder_launch_ms: a required pointer is NULL");
+    if (!e->timed) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_jpeg_encoder_launch_ms: no encode was timed (gr_jpeg_encoder_time_launches)");
+    for (int k = 0; k < 3; k++) HIP_CHECK(hipEventElapsedTime(&ms[k], e->events[k], e->events[k + 1]));
+    return GR_OK;
+}
+
+int gr_jpeg_encoder_scratch_intact(gr_jpeg_encoder* e, int* intact) {
+    if (!e || !intact) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_jpeg_encoder_scratch_intact: a required pointer is NULL");
+    HIP_CHECK(hipSetDevice(e->program->device));
+    const size_t G = gr_jpeg_encoder::GUARD_WORDS;
+    *intact = 1;
+    // the five guards, the last of them together with what the file region holds behind the longest file so far
+    const size_t file_words_used = (e->most_file_bytes + 3) / 4;
+    for (int r = 0; r <= 4; r++) {
+        const size_t from = r < 4 ? e->region_at[r] - G : e->region_at[3] + file_words_used, to = r < 4 ? e->region_at[r] : e->scratch_words;
+        std::vector<unsigned int> host(to - from);
+        HIP_CHECK(hipMemcpy(host.data(), e->scratch + from, host.size() * 4, hipMemcpyDeviceToHost));
+        for (unsigned int word : host)
+            if (word != gr_jpeg_encoder::GUARD_PATTERN) *intact = 0;
+    }
+    return GR_OK;
+}
+
+int gr_jpeg_encode_rgba8(gr_jpeg_encoder* e, void* stream, const void* device_rgba8, unsigned char* out_file, size_t capacity, size_t* out_bytes) {
+    const std::string who = "gr_jpeg_encode_rgba8: ";
+    if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
+    bool too_small = false;
+    const std::string wrong = jpeg_stream::refusal(device_rgba8, e->width, e->height, e->quality, out_file, capacity, out_bytes, &too_small);
+    if (!wrong.empty()) return fail(too_small ? GR_ERROR_BUFFER_TOO_SMALL : GR_ERROR_INVALID_ARGUMENT, who + wrong);
+    gr_program* p = e->program;
+    hipStream_t on = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(p->device));
+    int width = e->width, height = e->height, rows = jpeg_stream::mcu_rows(height);
+    unsigned int* coefficients = e->scratch + e->region_at[0];
+    unsigned int* slots = e->scratch + e->region_at[1];
+    unsigned int* row_bytes = e->scratch + e->region_at[2];
+    unsigned int* row_ff = row_bytes + rows;
+    unsigned long long* file_bytes = (unsigned long long*)(e->scratch + e->region_at[2] + e->region_words[2] - 2);   // the region's last two words: 8-byte aligned
+    unsigned char* file = (unsigned char*)(e->scratch + e->region_at[3]);
+    unsigned int slot_words = (unsigned int)(jpeg_stream::row_slot_bytes(width) / 4), header_bytes = jpeg_stream::HEADER_BYTES;
+    unsigned long long file_capacity = e->file_capacity;
+    const unsigned int* tables = e->tables;
+    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[0], on));
+    {
+        void* args[] = {&device_rgba8, &width, &height, &tables, &coefficients};
+        int rc = launch(p, K_JPEG_BLOCKS, stream, blocks(jpeg_stream::mcus_across(width), 4), (unsigned)rows, 64, 4, args);
+        if (rc != GR_OK) return rc;
+    }
+    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[1], on));
+    {
+        void* args[] = {&coefficients, &width, &height, &tables, &slots, &slot_words, &row_bytes, &row_ff};
+        int rc = launch(p, K_JPEG_PACK, stream, (unsigned)rows, 1, 64, 6, args);
+        if (rc != GR_OK) return rc;
+    }
+    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[2], on));
+    {
+        void* args[] = {&slots, &slot_words, &row_bytes, &row_ff, &rows, &file, &header_bytes, &file_capacity, &file_bytes};
+        int rc = launch(p, K_JPEG_GATHER, stream, (unsigned)rows, 1, 64, 4, args);
+        if (rc != GR_OK) return rc;
+    }
+    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[3], on));
+    // the first synchronisation: the file's size; the second: that many bytes
+    HIP_CHECK(hipMemcpyAsync(e->staging, file_bytes, 8, hipMemcpyDeviceToHost, on));
+    HIP_CHECK(hipStreamSynchronize(on));
+    e->timed = e->time_launches;
+    unsigned long long bytes = 0;
+    memcpy(&bytes, e->staging, 8);
+    if (bytes <= header_bytes || bytes > file_capacity) return fail(GR_ERROR_DEVICE, who + "the device's file size is not a file's of this frame size");
+    e->most_file_bytes = std::max(e->most_file_bytes, (size_t)bytes);
+    HIP_CHECK(hipMemcpyAsync(e->staging + 8, file, (size_t)bytes, hipMemcpyDeviceToHost, on));
+    HIP_CHECK(hipStreamSynchronize(on));
+    memcpy(out_file, e->staging + 8, (size_t)bytes);
+    *out_bytes = (size_t)bytes;
     return GR_OK;
 }
 

@@ -387,6 +387,130 @@ int gr_y4m_close(gr_y4m* y) {
     return complete ? GR_OK : gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_y4m_close: " + path + " is incomplete (a write failed)").c_str());
 }
 
+// ---- Motion-JPEG in AVI 1.0 (geodesic_hip_internal.h, "JPEG frames"): RIFF 'AVI ' { LIST 'hdrl' { 'avih', LIST 'strl' { 'strh', 'strf' } },
+// LIST 'movi' { '00dc' a frame, padded to even length }, 'idx1' }.  The 224 bytes in front of the first frame are written at open with
+// counts of 0 and written again at close with the counts the file ended up with.
+struct gr_avi {
+    FILE* file;          // NULL after a short write: the handle then only waits for gr_avi_close
+    std::string path;
+    uint32_t width, height, rate, scale;
+    uint64_t bytes;      // of the file so far
+    uint64_t limit;      // of the finished file: 2^31 - 1 (AVI 1.0 players read sizes and offsets as signed 32-bit numbers)
+    uint32_t largest;    // frame so far
+    std::vector<std::pair<uint32_t, uint32_t>> frames;   // offset of the '00dc' chunk from the 'movi' tag, size of its data
+};
+
+enum { AVI_HEADER_BYTES = 224, AVI_MOVI_TAG_AT = 220 };
+
+static void avi_header(const gr_avi* a, uint8_t out[AVI_HEADER_BYTES], uint64_t file_bytes, uint64_t movi_bytes) {
+    uint8_t* at = out;
+    auto tag = [&](const char* t) { memcpy(at, t, 4); at += 4; };
+    auto u32 = [&](uint64_t v) { for (int b = 0; b < 4; b++) *at++ = (uint8_t)(v >> (8 * b)); };
+    auto u16 = [&](unsigned v) { *at++ = (uint8_t)v; *at++ = (uint8_t)(v >> 8); };
+    const uint32_t count = (uint32_t)a->frames.size();
+    tag("RIFF"); u32(file_bytes - 8); tag("AVI ");
+    tag("LIST"); u32(4 + 64 + 12 + 64 + 48); tag("hdrl");
+    tag("avih"); u32(56);
+    u32((1000000ull * a->scale + a->rate / 2) / a->rate);            // microseconds a frame
+    u32(((uint64_t)a->largest * a->rate + a->scale - 1) / a->scale); // at most, bytes a second
+    u32(0); u32(0x10);                                                // no padding granularity; AVIF_HASINDEX
+    u32(count); u32(0); u32(1); u32(a->largest);                      // frames, no initial frames, one stream, the largest chunk
+    u32(a->width); u32(a->height); u32(0); u32(0); u32(0); u32(0);
+    tag("LIST"); u32(4 + 64 + 48); tag("strl");
+    tag("strh"); u32(56);
+    tag("vids"); tag("MJPG"); u32(0); u16(0); u16(0); u32(0);
+    u32(a->scale); u32(a->rate); u32(0); u32(count);                  // rate / scale frames a second, `count` of them from 0
+    u32(a->largest); u32(0xffffffffu); u32(0);                        // buffer, default quality, samples of varying size
+    u16(0); u16(0); u16(a->width); u16(a->height);
+    tag("strf"); u32(40);
+    u32(40); u32(a->width); u32(a->height); u16(1); u16(24); tag("MJPG"); u32((uint64_t)a->width * a->height * 3); u32(0); u32(0); u32(0); u32(0);
+    tag("LIST"); u32(4 + movi_bytes); tag("movi");
+}
+
+static int avi_put(gr_avi* a, const void* data, size_t bytes, const char* what) {
+    if (fwrite(data, 1, bytes, a->file) == bytes && fflush(a->file) == 0) return GR_OK;
+    fclose(a->file);
+    a->file = nullptr;
+    return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string("gr_avi: short write of ") + what + " to " + a->path).c_str());
+}
+
+int gr_avi_open(const char* path, int width, int height, int fps_num, int fps_den, gr_avi** out) {
+    const std::string name = "gr_avi_open";
+    if (out) *out = nullptr;
+    if (!path || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (name + ": null argument").c_str());
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (name + ": the frame's size (1 to 65535)").c_str());
+    if (fps_num < 1 || fps_den < 1)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (name + ": the frame rate fps_num / fps_den needs both parts >= 1").c_str());
+    FILE* f = fopen(path, "wb");
+    if (!f) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (name + ": cannot write " + path).c_str());
+    gr_avi* a = new gr_avi{f, path, (uint32_t)width, (uint32_t)height, (uint32_t)fps_num, (uint32_t)fps_den, AVI_HEADER_BYTES, 0x7fffffffull, 0, {}};
+    uint8_t header[AVI_HEADER_BYTES];
+    avi_header(a, header, AVI_HEADER_BYTES + 8, 0);
+    const int rc = avi_put(a, header, sizeof(header), "the header");
+    if (rc != GR_OK) { delete a; return rc; }
+    *out = a;
+    return GR_OK;
+}
+
+int gr_avi_set_size_limit(gr_avi* a, unsigned long long bytes) {
+    if (!a || bytes > 0x7fffffffull) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_avi_set_size_limit: a null handle, or a limit above 2^31 - 1");
+    a->limit = bytes;
+    return GR_OK;
+}
+
+int gr_avi_write_frame(gr_avi* a, const unsigned char* jpeg, size_t bytes) {
+    if (!a || !jpeg || !bytes) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_avi_write_frame: null argument or an empty frame");
+    if (!a->file) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_avi_write_frame: " + a->path + " was closed by a failed write").c_str());
+    // the file as it would end up: what is there, this chunk with its padding, and an index of one entry more
+    const uint64_t chunk = 8 + (uint64_t)bytes + (bytes & 1), after = a->bytes + chunk + 8 + 16 * ((uint64_t)a->frames.size() + 1);
+    if (after > a->limit)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_avi_write_frame: frame " + std::to_string(a->frames.size()) + " of " + std::to_string(bytes) +
+                                                            " bytes would take " + a->path + " to " + std::to_string(after) + " bytes, past the " +
+                                                            std::to_string(a->limit) + " an AVI 1.0 file holds; close it and start another").c_str());
+    uint8_t head[8] = {'0', '0', 'd', 'c'};
+    for (int b = 0; b < 4; b++) head[4 + b] = (uint8_t)(bytes >> (8 * b));
+    if (fwrite(head, 1, 8, a->file) != 8 || fwrite(jpeg, 1, bytes, a->file) != bytes) {
+        fclose(a->file);
+        a->file = nullptr;
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_avi: short write of a frame to " + a->path).c_str());
+    }
+    const uint8_t pad = 0;
+    const int rc = avi_put(a, &pad, bytes & 1, "a frame");
+    if (rc != GR_OK) return rc;
+    a->frames.push_back({(uint32_t)(a->bytes - AVI_MOVI_TAG_AT), (uint32_t)bytes});
+    a->largest = std::max(a->largest, (uint32_t)bytes);
+    a->bytes += chunk;
+    return GR_OK;
+}
+
+int gr_avi_close(gr_avi* a) {
+    if (!a) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_avi_close: null argument");
+    bool complete = a->file != nullptr;
+    if (complete) {
+        std::vector<uint8_t> index(8 + 16 * a->frames.size());
+        uint8_t* at = index.data();
+        auto u32 = [&](uint32_t v) { for (int b = 0; b < 4; b++) *at++ = (uint8_t)(v >> (8 * b)); };
+        memcpy(at, "idx1", 4);
+        at += 4;
+        u32((uint32_t)(16 * a->frames.size()));
+        for (auto& frame : a->frames) {
+            memcpy(at, "00dc", 4);
+            at += 4;
+            u32(0x10);   // AVIIF_KEYFRAME
+            u32(frame.first);
+            u32(frame.second);
+        }
+        uint8_t header[AVI_HEADER_BYTES];
+        avi_header(a, header, a->bytes + index.size(), a->bytes - AVI_HEADER_BYTES);
+        complete = fwrite(index.data(), 1, index.size(), a->file) == index.size() && fseek(a->file, 0, SEEK_SET) == 0 &&
+                   fwrite(header, 1, sizeof(header), a->file) == sizeof(header);
+        complete = (fclose(a->file) == 0) && complete;
+    }
+    const std::string path = a->path;
+    delete a;
+    return complete ? GR_OK : gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, ("gr_avi_close: " + path + " is incomplete (a write failed)").c_str());
+}
+
 // ---- the shutter of a motion-blurred frame: the host statement of one accumulation step (geodesic_hip_internal.h, "Motion-blurred frames";
 // kernels/shutter.hip's gr_shutter_accumulate is held to it at factor 1).  accum = [accum +] weight * frame, one fp32 multiply and one fp32
 // add per value, EACH ROUNDED: a fused multiply-add rounds once and gives other bits.  How the compiler is kept from contracting them: the

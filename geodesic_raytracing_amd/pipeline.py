@@ -449,6 +449,81 @@ class PngEncoder:
         self.close()
 
 
+def jpeg_encode_bound(width, height):
+    """the capacity both JPEG encoders ask for (gr_jpeg_encode_bound)"""
+    need = ctypes.c_size_t()
+    check(lib.gr_jpeg_encode_bound(int(width), int(height), ctypes.byref(need)))
+    return need.value
+
+
+def jpeg_quant_tables(quality):
+    """(luminance, chrominance): the quantiser's steps at a quality of 1 ... 100 as uint8 [8, 8] in natural order (gr_jpeg_quant_tables)"""
+    luma, chroma = np.empty((8, 8), np.uint8), np.empty((8, 8), np.uint8)
+    check(lib.gr_jpeg_quant_tables(int(quality), luma.ctypes.data_as(c_void_p), chroma.ctypes.data_as(c_void_p)))
+    return luma, chroma
+
+
+def jpeg_encode_host(pixels, quality=90):
+    """the baseline JPEG file of RGBA8 pixels [H, W, 4] (alpha ignored) as bytes, by the host encoder that defines JpegEncoder's stream
+    (gr_jpeg_encode_rgba8_host: JFIF, 4:2:0, the Annex K tables, one restart interval an MCU row)"""
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+    if pixels.ndim != 3 or pixels.shape[2] != 4:
+        raise ValueError(f"jpeg_encode_host: an image of shape {pixels.shape} is not [H, W, 4]")
+    h, w = pixels.shape[:2]
+    out = np.empty(jpeg_encode_bound(w, h), dtype=np.uint8)
+    size = ctypes.c_size_t()
+    check(lib.gr_jpeg_encode_rgba8_host(pixels.ctypes.data_as(c_void_p), w, h, int(quality), out.ctypes.data_as(c_void_p), out.nbytes, ctypes.byref(size)))
+    return out[:size.value].tobytes()
+
+
+class JpegEncoder:
+    """A JPEG encoder behind RGBA8 frames of one size that are already on the program's device (gr_jpeg_encoder): colour conversion, DCT,
+    quantiser, Huffman coding and byte stuffing run there, the file's bytes come back.  encode() synchronises the stream it is given.  The
+    program must outlive it."""
+
+    def __init__(self, program, width, height, quality=90):
+        self.program, self.width, self.height, self.quality = program, int(width), int(height), int(quality)   # (the program is borrowed: kept alive here)
+        self.handle = c_void_p()
+        check(lib.gr_jpeg_encoder_create(program.handle, self.width, self.height, self.quality, ctypes.byref(self.handle)))
+        self._out = np.empty(jpeg_encode_bound(self.width, self.height), dtype=np.uint8)
+
+    def encode(self, device_ptr, stream=None):
+        """the JPEG file of the frame at device_ptr (width x height RGBA8 pixels) as bytes: jpeg_encode_host's of the same pixels"""
+        size = ctypes.c_size_t()
+        check(lib.gr_jpeg_encode_rgba8(self.handle, stream, device_ptr, self._out.ctypes.data_as(c_void_p), self._out.nbytes, ctypes.byref(size)))
+        return self._out[:size.value].tobytes()
+
+    def write(self, path, device_ptr, stream=None):
+        """encode() into a file; returns its size"""
+        data = self.encode(device_ptr, stream)
+        with open(path, "wb") as f:
+            f.write(data)
+        return len(data)
+
+    def time_launches(self, on=True):
+        check(lib.gr_jpeg_encoder_time_launches(self.handle, int(bool(on))))
+
+    def launch_ms(self):
+        """(gr_jpeg_blocks, gr_jpeg_pack, gr_jpeg_gather) of the last encode after time_launches(), in milliseconds"""
+        ms = (c_float * 3)()
+        check(lib.gr_jpeg_encoder_launch_ms(self.handle, ms))
+        return ms[0], ms[1], ms[2]
+
+    def scratch_intact(self):
+        """True when the guard words of the encoder's scratch and the file region behind the longest file it has made are untouched"""
+        intact = c_int()
+        check(lib.gr_jpeg_encoder_scratch_intact(self.handle, ctypes.byref(intact)))
+        return bool(intact.value)
+
+    def close(self):
+        handle, self.handle = getattr(self, "handle", None), None
+        if handle:
+            lib.gr_jpeg_encoder_destroy(handle)
+
+    def __del__(self):
+        self.close()
+
+
 class RenderState:
     """Per-frame device buffers + the frame sequence (render_state.hpp:97-197, main.cpp:2244-2526)."""
 
@@ -811,6 +886,38 @@ class Y4MWriter:
         handle, self.handle = getattr(self, "handle", None), None
         if handle:
             check(lib.gr_y4m_close(handle))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (a destructor has nobody to raise to; close() called by hand does raise)
+            pass
+
+
+class AviWriter:
+    """A Motion-JPEG file in plain AVI 1.0 (gr_avi_open / _write_frame / _close): one '00dc' chunk per finished JPEG file, an index, sizes
+    patched at close; at most 2^31 - 1 bytes.  fps: an int, or (numerator, denominator).  Use as a context manager, or call close()."""
+
+    def __init__(self, path, width, height, fps=24):
+        num, den = fps if isinstance(fps, tuple) else (fps, 1)
+        self.handle = c_void_p()
+        check(lib.gr_avi_open(os.fsencode(path), int(width), int(height), int(num), int(den), ctypes.byref(self.handle)))
+
+    def write(self, jpeg):
+        """appends one frame: the bytes of a JPEG file (JpegEncoder.encode, jpeg_encode_host)"""
+        jpeg = bytes(jpeg)
+        check(lib.gr_avi_write_frame(self.handle, jpeg, len(jpeg)))
+
+    def close(self):
+        handle, self.handle = getattr(self, "handle", None), None
+        if handle:
+            check(lib.gr_avi_close(handle))
 
     def __enter__(self):
         return self

@@ -22,6 +22,10 @@
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --shutter 0.5 --out pan_blur.y4m
     # ... the 16 rays a pixel of --supersample 4 through a Mitchell-Netravali filter of radius 2 instead of a box one pixel wide: less shimmer
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --supersample 4 --filter mitchell --out pan_aa.y4m
+    # a baseline JPEG (JFIF, 4:2:0) made on the device - colour conversion, DCT, quantiser, Huffman coding: only the file's bytes come back
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --jpeg device --quality 90 --out kerr_4k.jpg
+    # ... and the pan as one Motion-JPEG file that every player opens, an order of magnitude smaller than the .y4m
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --fps 30000/1001 --jpeg device --out pan.avi
 """
 import argparse
 import ctypes
@@ -31,7 +35,7 @@ import sys
 import numpy as np
 
 import geodesic_raytracing_amd as gra
-from geodesic_raytracing_amd.pipeline import FRAME_FORMATS, DeviceBuffer, PinnedBuffer, ProgramManager, Y4MWriter, frame_format_of
+from geodesic_raytracing_amd.pipeline import FRAME_FORMATS, AviWriter, DeviceBuffer, PinnedBuffer, ProgramManager, Y4MWriter, frame_format_of
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -61,6 +65,11 @@ def write_png_bytes(path, data):
     """a PNG file that is already encoded (render(png="device"), pipeline.PngEncoder.encode)"""
     with open(path, "wb") as f:
         f.write(data)
+
+
+def write_jpeg_rgba8(path, pixels, quality=90):
+    """an 8-bit sRGB frame as a baseline JPEG file, by the host encoder (pipeline.jpeg_encode_host)"""
+    write_png_bytes(path, gra.jpeg_encode_host(pixels, quality))
 
 
 def parse_fps(text):
@@ -143,7 +152,7 @@ def camera_path_at(position, quat, position_to=None, quat_to=None, frames=1, tim
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
            parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box",
-           png="host"):
+           png="host", jpeg=None, quality=90):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
@@ -167,9 +176,16 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     uploaded and the slices are built there, the same bytes).
     png: "device" (with rgba8) - every frame returned is the bytes of a finished PNG file instead of pixels: the RGBA8 frame stays on the
     device, is filtered, histogrammed and bit-packed there (pipeline.PngEncoder) and only the compressed bytes come back - the file
-    pipeline.png_encode_host makes of the rgba8 frame, byte for byte."""
+    pipeline.png_encode_host makes of the rgba8 frame, byte for byte.
+    jpeg: "host" or "device" (with rgba8; not with png="device") - every frame returned is the bytes of a finished baseline JPEG file at
+    `quality` (1 ... 100): with "device" the RGBA8 frame stays on the device and is converted, transformed, quantised and Huffman-coded there
+    (pipeline.JpegEncoder), with "host" its pixels come back and pipeline.jpeg_encode_host makes the file - the same bytes."""
     if mips not in ("host", "device"):
         raise ValueError(f"render: mips={mips!r} (host or device)")
+    if jpeg not in (None, "host", "device") or (jpeg is not None and (not rgba8 or yuv420 or png == "device")):
+        raise ValueError(f"render: jpeg={jpeg!r} (None, or host or device with rgba8=True, no yuv420 and png='host')")
+    if jpeg is not None and not 1 <= int(quality) <= 100:
+        raise ValueError(f"render: quality={quality!r} (1 to 100)")
     if png not in ("host", "device") or (png == "device" and (not rgba8 or yuv420)):
         raise ValueError(f"render: png={png!r} (host, or device with rgba8=True and no yuv420)")
     if bit_depth not in (8, 10) or (bit_depth == 10 and not yuv420):
@@ -200,7 +216,7 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
         dbg = DeviceBuffer.from_numpy(device, packed)
     out_bytes = fmt.bytes(width, height)
     out = DeviceBuffer(device, out_bytes)
-    encoder = gra.PngEncoder(program, width, height) if png == "device" else None
+    encoder = gra.PngEncoder(program, width, height) if png == "device" else gra.JpegEncoder(program, width, height, quality) if jpeg == "device" else None
     pinned = PinnedBuffer(out_bytes) if frame_format != gra.FRAME_F32 and encoder is None else None   # (a float frame is downloaded as it always was)
     cam = gra.default_camera(camera_pos, camera_quat)
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
@@ -214,6 +230,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
             return out.to_numpy(fmt.dtype, fmt.shape(width, height))
         pinned.download_async(None, out.ptr, out_bytes)   # the frame's stream: copies queue behind its launches
         gra.check(gra.lib.gr_stream_synchronize(None))
+        if jpeg == "host":
+            return gra.jpeg_encode_host(pinned.view(fmt.dtype, fmt.shape(width, height)), quality)
         return pinned.view(fmt.dtype, fmt.shape(width, height)).copy()
 
     weight = np.float32(1) / np.float32(shutter_samples) if shutter_samples else None
@@ -269,17 +287,22 @@ def split_block_rows(height, block_rows=16):
 
 
 def render_split(metric_name, width, height, devices, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, background=None,
-                 fov=90.0, universe=20.0, wait_for_static=True, supersample=1, rgba8=False, mips="host", frames=1, block_rows=16, png="host"):
+                 fov=90.0, universe=20.0, wait_for_static=True, supersample=1, rgba8=False, mips="host", frames=1, block_rows=16, png="host", jpeg=None,
+                 quality=90):
     """render() of a Cartesian camera with the rows of every frame dealt to `devices` (TiledFrame.local: one process, peer copies, participant
     r on devices[r]; a device may be named more than once, which is how a box with one GPU rehearses it).  Every device has its own program,
     sky (with mips="device" built there, once per device) and render state, traces its share at `supersample` x per axis, resolves it
     there and ships width x rows pixels to devices[0] - float4, or with rgba8 4 bytes each (TiledFrame.render_as).  Frame k is rendered
     with rotation k, so the shares go round over `frames`.  Returns the list of frames: the arrays render() returns, bit for bit.  png="device"
-    (with rgba8): the finished frame on devices[0] is encoded there (pipeline.PngEncoder) and every frame returned is a PNG file's bytes."""
+    (with rgba8): the finished frame on devices[0] is encoded there (pipeline.PngEncoder) and every frame returned is a PNG file's bytes.
+    jpeg="host" or "device" (with rgba8, not with png="device"): every frame returned is a JPEG file's bytes at `quality`, made by
+    pipeline.jpeg_encode_host of the downloaded frame or on devices[0] (pipeline.JpegEncoder) - the same bytes."""
     if mips not in ("host", "device"):
         raise ValueError(f"render_split: mips={mips!r} (host or device)")
     if png not in ("host", "device") or (png == "device" and not rgba8):
         raise ValueError(f"render_split: png={png!r} (host, or device with rgba8=True)")
+    if jpeg not in (None, "host", "device") or (jpeg is not None and (not rgba8 or png == "device")) or (jpeg is not None and not 1 <= int(quality) <= 100):
+        raise ValueError(f"render_split: jpeg={jpeg!r}, quality={quality!r} (None, or host or device with rgba8=True, png='host' and a quality of 1 to 100)")
     devices = [int(d) for d in devices]
     if not devices:
         raise ValueError("render_split: no devices")
@@ -304,7 +327,8 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
         states = [gra.RenderState(width, height, d, supersample=supersample) for d in devices]
         out = DeviceBuffer(devices[0], width * height * (4 if rgba8 else 16))
         cam = gra.default_camera(camera_pos, camera_quat)
-        encoder = gra.PngEncoder(programs[devices[0]], width, height) if png == "device" else None
+        encoder = (gra.PngEncoder(programs[devices[0]], width, height) if png == "device" else
+                   gra.JpegEncoder(programs[devices[0]], width, height, quality) if jpeg == "device" else None)
         result = []
         for k in range(max(int(frames), 1)):
             for r, d in enumerate(devices):
@@ -312,7 +336,12 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
                                    rotation=k, rgba8=rgba8)
             parts[0].join()
             gra.check(gra.lib.gr_device_synchronize(devices[0]))
-            result.append(encoder.encode(out.ptr, None) if encoder is not None else out.to_numpy(np.uint8 if rgba8 else np.float32, (height, width, 4)))
+            if encoder is not None:
+                result.append(encoder.encode(out.ptr, None))
+            elif jpeg == "host":
+                result.append(gra.jpeg_encode_host(out.to_numpy(np.uint8, (height, width, 4)), quality))
+            else:
+                result.append(out.to_numpy(np.uint8 if rgba8 else np.float32, (height, width, 4)))
         return result
     finally:
         for part in parts:
@@ -349,6 +378,11 @@ def main(argv=None):
     ap.add_argument("--png", choices=["host", "device"], default="host", help="where a frame becomes a PNG file: host = the pixels come back and one host "
                     "thread deflates them; device = the 8-bit frame is filtered, histogrammed and Huffman-coded on the GPU (Sub / Up filters, one "
                     "table a frame, no matches) and only the compressed bytes come back.  device implies --encode device; not with --out NAME.y4m")
+    ap.add_argument("--jpeg", choices=["host", "device"], default=None, help="where a frame of --out NAME.jpg or NAME.avi becomes a baseline JPEG file "
+                    "(JFIF, 4:2:0, the standard Huffman tables, one restart interval a row of 16 x 16 blocks): host (the default) = the 8-bit pixels "
+                    "come back and one host thread encodes them; device = colour conversion, DCT, quantiser and Huffman coding run on the GPU and only "
+                    "the file's bytes come back (the same bytes).  device implies --encode device; not with --out NAME.png or NAME.y4m")
+    ap.add_argument("--quality", type=int, default=None, help="of a .jpg or .avi: 1 ... 100, the usual scaling of the standard quantisation tables (90)")
     ap.add_argument("--mips", choices=["host", "device"], default="host", help="where the sky's mip slices are made: host = pack them on the CPU "
                     "and upload all of them; device = upload the image and build the slices on the GPU (the same bytes)")
     ap.add_argument("--device", type=int, default=0)
@@ -359,7 +393,7 @@ def main(argv=None):
                     "post-filter there, tent changes nothing).  Not with --devices")
     ap.add_argument("--devices", default=None, help="0,1,2,3: deal the rows of every frame to these GPUs (one process, peer copies; a device may "
                     "repeat); each traces, resolves and - with --encode device - encodes its share, the share rotating over --frames")
-    ap.add_argument("--fps", default="24", help="frame rate of a .y4m file: N or N/D (24; 30000/1001)")
+    ap.add_argument("--fps", default="24", help="frame rate of a .y4m or .avi file: N or N/D (24; 30000/1001)")
     ap.add_argument("--bit-depth", type=int, choices=[8, 10], default=8, help="bits a sample of a .y4m file: 8 (C420jpeg, 1.5 bytes a pixel) or 10 "
                     "(C420p10: 16-bit little-endian words, 3 bytes a pixel - the master for a 10-bit encode).  Only with --out NAME.y4m")
     ap.add_argument("--shutter", type=float, default=None, help="motion blur: the fraction of the frame interval the shutter is open, above 0 and at "
@@ -368,19 +402,32 @@ def main(argv=None):
                     "linear light.  Needs a camera that moves: --camera-to / --quat-to or --geodesic-speed")
     ap.add_argument("--shutter-samples", type=int, default=None, help="sub-frames a frame of --shutter, 2 ... 64 (8)")
     ap.add_argument("--out", required=True, help="NAME.png: one PNG, or NAME_000.png ... for a sequence.  NAME.y4m: all frames in one uncompressed "
-                    "YUV4MPEG2 file of 8-bit BT.709 Y'CbCr 4:2:0 frames, converted on the device")
+                    "YUV4MPEG2 file of 8-bit BT.709 Y'CbCr 4:2:0 frames, converted on the device.  NAME.jpg: one baseline JPEG, or NAME_000.jpg ... for a "
+                    "sequence.  NAME.avi: all frames in one Motion-JPEG file (AVI 1.0, at most 2 GiB)")
     a = ap.parse_args(argv)
     video = a.out.lower().endswith(".y4m")
+    avi = a.out.lower().endswith(".avi")
+    jpeg_out = avi or a.out.lower().endswith((".jpg", ".jpeg"))
     try:
         fps = parse_fps(a.fps)
     except ValueError as e:
         ap.error(f"--fps: {e}")
     if a.bit_depth != 8 and not video:
-        ap.error("--bit-depth 10 is a depth of video frames: it needs --out NAME.y4m (a PNG is 8-bit sRGB)")
+        ap.error("--bit-depth 10 is a depth of video frames: it needs --out NAME.y4m (a PNG is 8-bit sRGB, and so is a JPEG or a Motion-JPEG file)")
     if a.png == "device":
         if video:
             ap.error("--png device with --out NAME.y4m: a video file holds no PNG; --png is about --out NAME.png")
         a.encode = "device"
+    if jpeg_out:
+        if a.png == "device":
+            ap.error("--png device with --out NAME.jpg / NAME.avi: the frames of such a file are JPEG files; --png is about --out NAME.png")
+        a.jpeg = a.jpeg or "host"
+        a.quality = 90 if a.quality is None else a.quality
+        if not 1 <= a.quality <= 100:
+            ap.error(f"--quality {a.quality}: 1 to 100")
+        a.encode = "device"   # a JPEG is made of the 8-bit frame; with --jpeg host its pixels come back at 4 bytes each
+    elif a.jpeg is not None or a.quality is not None:
+        ap.error("--jpeg / --quality with --out NAME.png / NAME.y4m: they are about JPEG frames; give --out NAME.jpg or NAME.avi")
     if a.shutter_samples is not None and a.shutter is None:
         ap.error("--shutter-samples without --shutter: the sub-frames are those of a shutter; give its open fraction, e.g. --shutter 0.5")
     if a.shutter is not None:
@@ -409,7 +456,7 @@ def main(argv=None):
     speed = [float(v) for v in a.geodesic_speed.split(",")] if a.geodesic_speed else None
     times = [a.geodesic_time + i * a.geodesic_dt for i in range(max(a.frames, 1))]
     moments = shutter_times(max(a.frames, 1), a.shutter, samples).ravel() if samples else None   # frame numbers, `samples` a frame
-    write = write_png_bytes if a.png == "device" else write_rgba8_png if a.encode == "device" else write_frame_png
+    write = write_png_bytes if a.png == "device" or jpeg_out else write_rgba8_png if a.encode == "device" else write_frame_png
     if a.devices is not None:
         try:
             devices = [int(v) for v in a.devices.split(",")]
@@ -423,7 +470,14 @@ def main(argv=None):
             ap.error("--geodesic-speed with --devices: a split frame takes a Cartesian camera")
         result = render_split(a.metric, w, h, devices, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
                               [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, read_png(a.background) if a.background else None,
-                              a.fov, a.universe, supersample=a.supersample, rgba8=a.encode == "device", mips=a.mips, frames=a.frames, png=a.png)
+                              a.fov, a.universe, supersample=a.supersample, rgba8=a.encode == "device", mips=a.mips, frames=a.frames, png=a.png,
+                              jpeg=a.jpeg, quality=a.quality or 90)
+        if avi:
+            with AviWriter(a.out, w, h, fps) as stream:
+                for frame in result:
+                    stream.write(frame)
+            print(f"wrote {a.out} ({w}x{h}, {len(result)} frames at {fps[0]}/{fps[1]} a second, Motion-JPEG, {len(devices)} participants)")
+            return 0
         stem, ext = os.path.splitext(a.out)
         for i, frame in enumerate(result):
             path = a.out if len(result) == 1 else f"{stem}_{i:03d}{ext}"
@@ -443,7 +497,7 @@ def main(argv=None):
                     geodesic_times=[a.geodesic_time + float(t) * a.geodesic_dt for t in moments] if samples else times,
                     parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
                     rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples,
-                    filter=a.filter, png=a.png)
+                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90)
     if speed is None and cameras is None:
         result = [result]
     if video:
@@ -451,6 +505,12 @@ def main(argv=None):
             for frame in result:
                 stream.write(frame)
         print(f"wrote {a.out} ({w}x{h}, {len(result)} frames at {fps[0]}/{fps[1]} a second, {'10-bit ' if a.bit_depth == 10 else ''}BT.709 Y'CbCr 4:2:0)")
+        return 0
+    if avi:
+        with AviWriter(a.out, w, h, fps) as stream:
+            for frame in result:
+                stream.write(frame)
+        print(f"wrote {a.out} ({w}x{h}, {len(result)} frames at {fps[0]}/{fps[1]} a second, Motion-JPEG at quality {a.quality})")
         return 0
     stem, ext = os.path.splitext(a.out)
     for i, frame in enumerate(result):

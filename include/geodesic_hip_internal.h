@@ -352,6 +352,89 @@ int gr_png_encoder_time_launches(gr_png_encoder* e, int on);
 int gr_png_encoder_launch_ms(gr_png_encoder* e, float ms[2]);
 int gr_png_encoder_scratch_intact(gr_png_encoder* e, int* intact);
 
+/* ---- JPEG frames ----------------------------------------------------------------------------------------------------------------------
+ * A baseline JPEG encoder behind an RGBA8 frame that is already in device memory - the three sources the PNG encoder takes - and a
+ * Motion-JPEG AVI writer for a sequence of such files: colour conversion, DCT, quantiser, Huffman coding and byte stuffing run on the device
+ * (kernels/jpeg.hip, set-up module), only the file's bytes come back.  A sink like PNG, not a fifth GR_FRAME_* format.  (Declared here and not
+ * in geodesic_hip.h only because the contract header keeps to 80 names and 350 lines; all of this is public.)
+ *
+ * The stream is fixed, so that host and device write the same bytes:
+ *   container   JFIF: SOI, APP0 "JFIF" 1.01 (density 1:1 without units, no thumbnail), DQT luminance, DQT chrominance, SOF0, DHT DC and AC
+ *               luminance, DHT DC and AC chrominance, DRI, SOS, the entropy-coded data, EOI - 629 bytes in front of the data.  SOF0: baseline,
+ *               8 bit, components 1, 2, 3 sampled 2x2, 1x1, 1x1: an MCU is 16 x 16 pixels, blocks Y00 Y01 Y10 Y11 Cb Cr.  Width and height
+ *               1 ... 65 535.  Alpha is ignored.
+ *   colour      JFIF's full-range BT.601 Y'CbCr of the 8-bit sRGB codes as they stand - NOT the limited-range BT.709 of gr_present_yuv420:
+ *               a JFIF decoder assumes 601 full range and would show anything else with wrong colours.  Integers:
+ *                 Y' = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *                 Cb = ((-11059 R - 21709 G + 32768 B + 32768) >> 16) + 128       Cr = ((32768 R - 27439 G - 5329 B + 32768) >> 16) + 128
+ *               (arithmetic shifts: rounded to nearest, halves up), clamped to 0 ... 255.  CHROMA: the mean of the 2 x 2 pixels' R, of their
+ *               G and of their B, each (sum + 2) >> 2, converted once.  A pixel past the right or bottom edge is the last of its row or column.
+ *   DCT         of sample - 128, separable, with K[u][x] = round(2^14 c[u][x]), c the orthonormal DCT-II matrix (c[0][x] = 1 / (2 sqrt 2),
+ *               c[u][x] = cos((2x + 1) u pi / 16) / 2; the eight magnitudes 5793 8035 7568 6811 5793 4551 3135 1598):
+ *                 rows     t[y][u] = (sum over x of K[u][x] s[y][x] + 128) >> 8             6 fraction bits
+ *                 columns  F[v][u] = (sum over y of K[v][y] t[y][u] + 32768) >> 16          4 fraction bits: F is 16 x the coefficient
+ *               Every sum fits 32 bits (|t| <= 23 175, sum over y of |K| = 46 344: below 1.08 x 10^9) and every product's operands 24.
+ *               ERROR BOUND of F / 16 against the exact DCT: 0.19.  With e = 0.00019 >= the largest row sum of |K / 2^14 - c| and A = 2 sqrt 2
+ *               = the largest row sum of |c|: a row value is off by at most e1 = 128 e + 2^-7 < 0.0317, a coefficient by at most
+ *               A e1 + e (128 A + e1) + 2^-5 < 0.0896 + 0.0689 + 0.0313 = 0.19 - below 0.5, half the smallest quantiser step.
+ *   quantiser   the Annex K.1 tables scaled by the quality q = 1 ... 100: s = 5000 / q below 50, else 200 - 2 q; step = (table s + 50) / 100
+ *               clamped to 1 ... 255 (integer divisions).  Quantised = sign(F) ((|F| + 8 step) / (16 step)): rounded half away from zero.  An AC
+ *               value stays within +-1 020.2, the DC within -1 024 ... 1 016: sizes 10 and 11 are never exceeded.  Zig-zag order.
+ *   entropy     the four Annex K.3 Huffman tables, as DHT holds them.  Tables optimised per frame are OUT OF SCOPE: they would cost a pass over
+ *               the frame and a round trip through the host, for some 5 to 10 % of the file.  DC: the difference to the component's previous
+ *               block, 0 at the start of a restart interval; AC: run/size with ZRL (F0) and EOB (00).
+ *   restarts    DRI = the MCUs of one MCU row.  Every MCU row is a segment of its own: its bits, 1-bits up to a byte boundary, FF 00 for every
+ *               FF byte, then RSTm with m = row mod 8 - EOI behind the last row.  Rows are therefore coded independently.
+ *   AVI         plain AVI 1.0: RIFF 'AVI ', LIST 'hdrl' with 'avih' and one LIST 'strl' of 'strh' ('vids' / 'MJPG', dwScale = fps_den, dwRate =
+ *               fps_num) and 'strf' (BITMAPINFOHEADER, 24 bit, 'MJPG'); LIST 'movi' with one '00dc' chunk a frame, padded to even length;
+ *               'idx1' with one key-frame entry a frame, offsets from the 'movi' tag.  Sizes and counts are patched at close.  OpenDML (files
+ *               of 2 GiB and more) is out of scope. */
+typedef struct gr_jpeg_encoder gr_jpeg_encoder;
+typedef struct gr_avi gr_avi;
+/* What no file of this size exceeds - the capacity both encoders ask for: 629 bytes of headers and, per MCU row, twice (every byte an FF, stuffed)
+ * the row's largest segment - ceil(MCUs x 6 blocks x 1 658 bits / 8) bytes, a block being at most a DC code of 9 bits with 11 value bits and 63
+ * AC codes of 16 bits with 10 value bits - and 2 bytes of marker.  Refused: a NULL, a width or height outside 1 ... 65 535. */
+int gr_jpeg_encode_bound(int width, int height, size_t* bytes);
+/* The quantiser's steps at a quality, in natural (row-major) order.  Refused: a NULL, a quality outside 1 ... 100. */
+int gr_jpeg_quant_tables(int quality, unsigned char luma[64], unsigned char chroma[64]);
+/* The host encoder: the definition of the bytes above.  rgba8: [height][width][4] bytes, R, G, B, A; *out_bytes: the file's size.  Both
+ * encoders refuse, before anything is written or any device call is made, with a message that names the entry point: a NULL; a width or height
+ * outside 1 ... 65 535; a quality outside 1 ... 100; a frame pointer not aligned to 4 bytes; a capacity below gr_jpeg_encode_bound
+ * (GR_ERROR_BUFFER_TOO_SMALL; everything else GR_ERROR_INVALID_ARGUMENT).  out_file needs no alignment. */
+int gr_jpeg_encode_rgba8_host(const unsigned char* rgba8, int width, int height, int quality, unsigned char* out_file, size_t capacity, size_t* out_bytes);
+/* The quantised coefficients alone: per MCU in scan order (rows of MCUs, left to right) six blocks of 64 values in zig-zag order;
+ * out holds ceil(width / 16) x ceil(height / 16) x 384 values. */
+int gr_jpeg_blocks_host(const unsigned char* rgba8, int width, int height, int quality, short* out);
+/* The DCT alone (tests hold its error bound to it): samples[64] in natural order, each -128 ... 127 (anything else is refused), to F as
+ * defined above - 16 x the coefficient - in natural order. */
+int gr_jpeg_fdct_host(const short* samples, int* coefficients_x16);
+/* A device encoder for frames of one size and quality on the program's device: owns the device scratch (3 bytes a pixel of coefficients, the
+ * MCU rows' segments, the file; the headers are made here, by the host encoder's own function, and uploaded once) and a pinned staging buffer
+ * of gr_jpeg_encode_bound bytes.  The program is borrowed and must outlive it. */
+int gr_jpeg_encoder_create(gr_program* p, int width, int height, int quality, gr_jpeg_encoder** out);
+void gr_jpeg_encoder_destroy(gr_jpeg_encoder* e);
+/* Encodes device_rgba8 (device memory, width x height pixels) into out_file (host memory): enqueues on `stream` gr_jpeg_blocks, gr_jpeg_pack and
+ * gr_jpeg_gather with nothing between them, downloads the file's size and then exactly that many bytes, and returns after they are in
+ * out_file: it SYNCHRONISES that stream, twice.  The file is gr_jpeg_encode_rgba8_host's of the same pixels, byte for byte. */
+int gr_jpeg_encode_rgba8(gr_jpeg_encoder* e, void* stream, const void* device_rgba8, unsigned char* out_file, size_t capacity, size_t* out_bytes);
+/* Measurement and tests.  _time_launches: with on != 0 every later encode brackets its three launches with events; _launch_ms: the last such
+ * encode's gr_jpeg_blocks, gr_jpeg_pack and gr_jpeg_gather in milliseconds.  _scratch_intact: *intact = 1 when the guard words around each
+ * region of the scratch and every word of the file region behind the longest file this encoder has made still hold what
+ * gr_jpeg_encoder_create wrote there. */
+int gr_jpeg_encoder_time_launches(gr_jpeg_encoder* e, int on);
+int gr_jpeg_encoder_launch_ms(gr_jpeg_encoder* e, float ms[3]);
+int gr_jpeg_encoder_scratch_intact(gr_jpeg_encoder* e, int* intact);
+/* The Motion-JPEG writer, shaped like gr_y4m_*: _open writes the headers (refused: a NULL, a size outside 1 ... 65 535, a rate part below 1, a
+ * path that cannot be written), _write_frame appends one finished JPEG file of `bytes` bytes as a chunk, _close writes the index, patches the
+ * sizes and counts and frees the handle.  A frame with which the finished file would pass 2^31 - 1 bytes is refused with a message that says
+ * so, nothing of it is written, and the file still closes valid.  After a short write the handle only waits for gr_avi_close, which then
+ * reports the file incomplete. */
+int gr_avi_open(const char* path, int width, int height, int fps_num, int fps_den, gr_avi** out);
+int gr_avi_write_frame(gr_avi* a, const unsigned char* jpeg, size_t bytes);
+int gr_avi_close(gr_avi* a);
+/* For tests: a lower limit than 2^31 - 1 for the finished file of this handle (a limit above that is refused). */
+int gr_avi_set_size_limit(gr_avi* a, unsigned long long bytes);
+
 /* ---- fused MI355X path (no reference counterpart) ------------------------------------------- */
 
 /* Prepass termination flags from one fused trace at prepass resolution (replaces the sequence
