@@ -45,12 +45,13 @@ import numpy as np
 
 import geodesic_raytracing_amd as gra
 from oracle.refpipe import LIGHTRAY_DTYPE, RENDER_DATA_DTYPE, pack_features
+from model_common import (JACOBIAN_STEP, _cartesian_to_polar, _frame_basis_with_swap, _jacobian_of, _polar_to_cartesian, _rot_quat,  # noqa: F401
+                          _spherical_velocity_to_cartesian)
 from shading_model import REDSHIFT_Z
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPTS = os.path.join(ROOT, "geodesic_raytracing_amd", "scripts")
 PI_F32 = float(np.float32(np.pi))
-JACOBIAN_STEP = 1e-5
 MARGIN_R, MARGIN_SIGN, MARGIN_DISCRIM, MARGIN_ROOTS, MARGIN_THETA, MARGIN_GTT, MARGIN_Z = 1e-6, 1e-6, 1e-3, 1e-4, 2e-6, 5e-7, 1e-4
 TEX_FLOOR, Z_FLOOR = 2e-6, 1e-4           # the stage's tolerances (tests/test_gpu_parity.py), the floors of the device's bounds
 FIX_NONE, FIX_UNIVERSE, FIX_TERMINATOR = 0, 1, 2
@@ -130,30 +131,6 @@ def closed_form(name, x, cfg):
 
 
 # ---- the model ---------------------------------------------------------------------------------------------------------------------
-def _polar_to_cartesian(p):
-    r, th, ph = p
-    return np.array([r * np.sin(th) * np.cos(ph), r * np.sin(th) * np.sin(ph), r * np.cos(th)])
-
-
-def _cartesian_to_polar(c):
-    with np.errstate(invalid="ignore", divide="ignore"):
-        r = np.sqrt(c @ c)
-        return np.array([r, np.arccos(c[2] / r), np.arctan2(c[1], c[0])])
-
-
-def _spherical_velocity_to_cartesian(p, dp):
-    r, x, y = p
-    dr, dx, dy = dp
-    sx, cx, sy, cy = np.sin(x), np.cos(x), np.sin(y), np.cos(y)
-    return np.array([-r * sx * sy * dy + r * cx * cy * dx + sx * cy * dr, sx * sy * dr + r * sx * cy * dy + r * cx * sy * dx, cx * dr - r * sx * dx])
-
-
-def _rot_quat(point, q):
-    q = q / np.sqrt(q @ q)
-    t = 2 * np.cross(q[:3], point)
-    return point + q[3] * t + np.cross(q[:3], t)
-
-
 def _fix_ray_position(polar_pos, polar_vel, radius, constant_theta, out):
     """fix_ray_position and fix_ray_position_cart; the discriminant, both roots and the cancellation's size go to `out`"""
     sgn = np.sign(polar_pos[0])
@@ -181,41 +158,6 @@ def _fix_ray_position(polar_pos, polar_vel, radius, constant_theta, out):
     return res
 
 
-def _frame_basis_with_swap(g, index_swap):
-    arr = [np.eye(4)[i] for i in range(4)]
-    lengths = [g[i, i] for i in range(4)]
-    arr[0], arr[index_swap] = arr[index_swap], arr[0]
-    lengths[0], lengths[index_swap] = lengths[index_swap], lengths[0]
-    indices = [0, 1, 2, 3]
-    first = next((i for i in range(4) if not abs(lengths[i]) <= 0.00001), 0)
-    if first != 0:
-        arr[0], arr[first] = arr[first], arr[0]
-        indices[0], indices[first] = indices[first], indices[0]
-    dot = lambda u, v: (g @ u) @ v
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        proj = lambda u, v: (dot(u, v) / dot(u, u)) * u
-        u1 = arr[0]
-        u2 = arr[1] - proj(u1, arr[1])
-        u3 = arr[2] - proj(u1, arr[2])
-        u3 = u3 - proj(u2, u3)
-        u4 = arr[3] - proj(u1, arr[3])
-        u4 = u4 - proj(u2, u4)
-        u4 = u4 - proj(u3, u4)
-        res = [u / np.sqrt(abs(dot(u, u))) for u in (u1, u2, u3, u4)]
-    ordered = [None] * 4
-    for i in range(4):
-        ordered[indices[i]] = res[i]
-    lowest, lowest_value = -1, 0.0
-    for i in range(4):
-        d = dot(ordered[i], ordered[i])
-        if d < lowest_value:
-            lowest, lowest_value = i, d
-    which = lowest if lowest != -1 else 0
-    if which > 0:
-        ordered[0], ordered[which] = ordered[which], ordered[0]
-    return which, ordered
-
-
 def _timelike_leg(g):
     """e[0] of calculate_tetrads(position, no speed, no orientation) at a position that is not degenerate"""
     which, e = _frame_basis_with_swap(g, 0)
@@ -226,16 +168,7 @@ def _timelike_leg(g):
 
 
 def _jacobian(prog, x, p0):
-    J = np.zeros((4, 4))
-    for k in range(4):
-        h = JACOBIAN_STEP * max(1.0, abs(x[k]))
-        up, down = x.copy(), x.copy()
-        up[k] += h
-        down[k] -= h
-        d = prog.to_polar(up) - prog.to_polar(down)
-        d[3] = d[3] - 2 * np.pi * np.rint(d[3] / (2 * np.pi))
-        J[:, k] = d / (2 * h)
-    return J
+    return _jacobian_of(prog.to_polar, x)
 
 
 def angle_to_tex(theta, phi):

@@ -6,6 +6,7 @@ Tolerances (fp32; the reference is built with -cl-unsafe-math-optimizations, bot
 and libm, and rays near photon orbits amplify 1-ulp differences - SURVEY.md section 8d):
   camera / tetrad          abs 2e-6
   initial rays             abs 2e-5 (position, velocity, acceleration, quaternion, k.u)
+                           (the same two floors on cameras made by hand, against a float64 model: tests/test_gpu_setup.py)
   traced rays              termination flags differ for <= 0.5 % of rays (1 % super-extremal Kerr); per ray: a ray is
                            "ordinary" when it took fewer than twice the frame's median number of Verlet attempts, and
                            every ordinary ray that terminated on both sides agrees in position to 1e-3 (position_err:
