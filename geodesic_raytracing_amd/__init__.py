@@ -126,6 +126,8 @@ FRAME_YUV420, FRAME_YUV420P10 = 2, 3   # GR_FRAME_YUV420 / _YUV420P10: the video
 FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN, FILTER_MITCHELL = 0, 1, 2, 3   # GR_FILTER_*: the reconstruction filter of a state's frames (include/geodesic_hip_internal.h, "Filtered frames")
 FILTER_NAMES = {"box": FILTER_BOX, "tent": FILTER_TENT, "gaussian": FILTER_GAUSSIAN, "mitchell": FILTER_MITCHELL}
 FILTER_MAX_TAPS = 16
+PNG_STREAM_LITERALS, PNG_STREAM_RUNS = 0, 1   # GR_PNG_STREAM_*: the stream kind of a device-made PNG (include/geodesic_hip_internal.h, "PNG frames")
+PNG_STREAM_NAMES = {"literals": PNG_STREAM_LITERALS, "runs": PNG_STREAM_RUNS}
 YUV420_I420, YUV420_NV12 = 0, 1   # GR_YUV420_*: the layouts of an 8-bit Y'CbCr 4:2:0 frame (include/geodesic_hip.h, "video frames")
 EVAL_METRIC_TENSOR, EVAL_METRIC_DERIVATIVES, EVAL_ACCELERATION, EVAL_TO_POLAR, EVAL_FROM_POLAR, EVAL_ORIGIN_DISTANCE = range(6)
 (STAGE_CAMERA, STAGE_PREPASS, STAGE_INIT, STAGE_TRACE, STAGE_RENDER_DATA, STAGE_ADAPTIVE, STAGE_RENDER) = range(7)
@@ -340,8 +342,11 @@ _SIGNATURES = {
     "gr_render_state_filter": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "gr_png_encode_bound": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "gr_png_encode_rgba8_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
+    "gr_png_encode_rgba8_host_as": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_int]),
     "gr_png_build_table": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
+    "gr_png_build_table_as": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
     "gr_png_encoder_create": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "gr_png_encoder_create_as": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "gr_png_encoder_destroy": (None, [c_void_p]),
     "gr_png_encode_rgba8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
     "gr_png_encoder_time_launches": (c_int, [c_void_p, c_int]),

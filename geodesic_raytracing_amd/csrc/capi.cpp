@@ -79,22 +79,24 @@ const char* const KERNEL_NAMES[] = {
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
     "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack",
-    "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather"};
+    "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather", "gr_png_histogram_runs", "gr_png_pack_runs"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_JPEG_BLOCKS, K_JPEG_PACK, K_JPEG_GATHER, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_JPEG_BLOCKS, K_JPEG_PACK, K_JPEG_GATHER, K_PNG_HISTOGRAM_RUNS, K_PNG_PACK_RUNS, K_COUNT
 };
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
 // filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and 8- and 10-bit Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
 // (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation - and the two integer kernels of the
-// PNG encoder (kernels/png.hip) and the three of the JPEG encoder (kernels/jpeg.hip), which want no part in it either
+// PNG encoder (kernels/png.hip; each in two instances, one a stream kind) and the three of the JPEG encoder (kernels/jpeg.hip), which want
+// no part in it either
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
            k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE || k == K_RESOLVE_FILTERED ||
-           k == K_PNG_HISTOGRAM || k == K_PNG_PACK || k == K_JPEG_BLOCKS || k == K_JPEG_PACK || k == K_JPEG_GATHER;
+           k == K_PNG_HISTOGRAM || k == K_PNG_PACK || k == K_JPEG_BLOCKS || k == K_JPEG_PACK || k == K_JPEG_GATHER || k == K_PNG_HISTOGRAM_RUNS ||
+           k == K_PNG_PACK_RUNS;
 }
 
 namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files
@@ -1287,10 +1289,12 @@ int gr_build_mipped_background(gr_program* p, void* stream, const void* rgba8, i
 struct gr_png_encoder {
     gr_program* program = nullptr;
     int width = 0, height = 0;
-    // device: [frame histogram 256 | rows' histograms height x 256 | rows' sums height x 2] words, downloaded in one copy ...
+    // the stream kind, and with it the bins of a histogram as the kernels store it (256, runs: 285) and the table's symbols (257, 285)
+    int stream_kind = GR_PNG_STREAM_LITERALS, bins = 256, symbols = png_stream::SYMBOLS;
+    // device: [frame histogram bins | rows' histograms height x bins | rows' sums height x 2] words, downloaded in one copy ...
     unsigned int* statistics = nullptr;
     size_t statistics_words = 0;
-    // ... [rows' offsets height + 1, 64 bit | table 257 | header png_stream::HEADER_WORDS] uploaded in one copy ...
+    // ... [rows' offsets height + 1, 64 bit | table symbols | header png_stream::HEADER_WORDS] uploaded in one copy ...
     unsigned char* placement = nullptr;
     unsigned char* placement_host = nullptr;   // (pinned)
     size_t placement_bytes = 0;
@@ -1316,19 +1320,23 @@ struct gr_png_encoder {
     }
 };
 
-int gr_png_encoder_create(gr_program* p, int width, int height, gr_png_encoder** out) {
-    const std::string who = "gr_png_encoder_create: ";
+namespace {
+int png_encoder_create(const std::string& who, gr_program* p, int width, int height, int stream_kind, gr_png_encoder** out) {
     if (!p || !out) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
     if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
     const uint64_t rows_bound = png_stream::rows_bound(width, height);
     if (!rows_bound) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a frame of more than 2^31 - 1 raw bytes");
+    if (!png_stream::known_kind(stream_kind)) return fail(GR_ERROR_INVALID_ARGUMENT, who + "an unknown stream kind " + std::to_string(stream_kind));
     HIP_CHECK(hipSetDevice(p->device));
     auto e = std::make_unique<gr_png_encoder>();
     e->program = p;
     e->width = width;
     e->height = height;
-    e->statistics_words = 256 + (size_t)height * 258;
-    e->placement_bytes = ((size_t)height + 1) * 8 + (png_stream::SYMBOLS + png_stream::HEADER_WORDS) * 4;
+    e->stream_kind = stream_kind;
+    e->bins = png_stream::row_bins_of(stream_kind);
+    e->symbols = png_stream::symbols_of(stream_kind);
+    e->statistics_words = (size_t)e->bins + (size_t)height * ((size_t)e->bins + 2);
+    e->placement_bytes = ((size_t)height + 1) * 8 + ((size_t)e->symbols + png_stream::HEADER_WORDS) * 4;
     e->stream_capacity_words = (size_t)((rows_bound + 3) / 4);
     e->staging_bytes = std::max(e->statistics_words * 4, e->stream_capacity_words * 4);
     const size_t scratch_words = e->stream_capacity_words + 2 * gr_png_encoder::GUARD_WORDS;
@@ -1341,6 +1349,15 @@ int gr_png_encoder_create(gr_program* p, int width, int height, gr_png_encoder**
     HIP_CHECK(hipDeviceSynchronize());
     *out = e.release();
     return GR_OK;
+}
+}   // namespace
+
+int gr_png_encoder_create(gr_program* p, int width, int height, gr_png_encoder** out) {
+    return png_encoder_create("gr_png_encoder_create: ", p, width, height, GR_PNG_STREAM_LITERALS, out);
+}
+
+int gr_png_encoder_create_as(gr_program* p, int width, int height, int stream_kind, gr_png_encoder** out) {
+    return png_encoder_create("gr_png_encoder_create_as: ", p, width, height, stream_kind, out);
 }
 
 void gr_png_encoder_destroy(gr_png_encoder* e) { delete e; }
@@ -1384,18 +1401,20 @@ int gr_png_encode_rgba8(gr_png_encoder* e, void* stream, const void* device_rgba
     if (!wrong.empty()) return fail(too_small ? GR_ERROR_BUFFER_TOO_SMALL : GR_ERROR_INVALID_ARGUMENT, who + wrong);
     gr_program* p = e->program;
     const int width = e->width, height = e->height;
+    const bool runs = e->stream_kind == GR_PNG_STREAM_RUNS;
+    const size_t bins = (size_t)e->bins;
     hipStream_t on = (hipStream_t)stream;
     HIP_CHECK(hipSetDevice(p->device));
     // the first round trip: the frame's and the rows' histograms, the rows' Adler sums
     unsigned int* frame_histogram = e->statistics;
-    unsigned int* row_histogram = e->statistics + 256;
-    unsigned int* row_sums = row_histogram + (size_t)height * 256;
-    HIP_CHECK(hipMemsetAsync(frame_histogram, 0, 256 * 4, on));
+    unsigned int* row_histogram = e->statistics + bins;
+    unsigned int* row_sums = row_histogram + (size_t)height * bins;
+    HIP_CHECK(hipMemsetAsync(frame_histogram, 0, bins * 4, on));
     if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[0], on));
     {
         int w = width, h = height;
         void* args[] = {&device_rgba8, &w, &h, &frame_histogram, &row_histogram, &row_sums};
-        int rc = launch(p, K_PNG_HISTOGRAM, stream, (unsigned)height, 1, 64, 4, args);
+        int rc = launch(p, runs ? K_PNG_HISTOGRAM_RUNS : K_PNG_HISTOGRAM, stream, (unsigned)height, 1, 64, 4, args);
         if (rc != GR_OK) return rc;
     }
     if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[1], on));
@@ -1404,26 +1423,26 @@ int gr_png_encode_rgba8(gr_png_encoder* e, void* stream, const void* device_rgba
     // the table from the frame's histogram - with what the device does not count: a filter-type byte and an end-of-block a row -, the rows'
     // offsets from their own histograms, the Adler-32 from their sums
     const unsigned int* got = (const unsigned int*)e->staging;
-    uint64_t histogram[png_stream::SYMBOLS];
-    for (int v = 0; v < 256; v++) histogram[v] = got[v];
+    uint64_t histogram[png_stream::MAX_SYMBOLS] = {};
+    for (size_t v = 0; v < bins; v++) histogram[v] = got[v];
     histogram[1] += 1;
     histogram[2] += (uint64_t)height - 1;
     histogram[png_stream::END_OF_BLOCK] = (uint64_t)height;
     png_stream::table t;
-    png_stream::build_table(histogram, t);
+    png_stream::build_table(histogram, e->stream_kind, t);
     uint64_t* offset = (uint64_t*)e->placement_host;
     unsigned int* table_words = (unsigned int*)(e->placement_host + ((size_t)height + 1) * 8);
-    unsigned int* header_words = table_words + png_stream::SYMBOLS;
+    unsigned int* header_words = table_words + e->symbols;
     std::vector<uint32_t> adlers(height);
     offset[0] = 0;
     for (int r = 0; r < height; r++) {
-        offset[r + 1] = offset[r] + png_stream::row_segment_bytes(png_stream::row_block_bits(t, r, got + 256 + (size_t)r * 256));
-        const unsigned int* sums = got + 256 + (size_t)height * 256 + 2 * (size_t)r;
+        offset[r + 1] = offset[r] + png_stream::row_segment_bytes(png_stream::row_block_bits(t, r, got + bins + (size_t)r * bins));
+        const unsigned int* sums = got + bins + (size_t)height * bins + 2 * (size_t)r;
         adlers[r] = png_stream::row_adler(r, width, sums[0], sums[1]);
     }
     const uint64_t rows_bytes = offset[height], stream_words = (rows_bytes + 3) / 4;
     if (stream_words > e->stream_capacity_words) return fail(GR_ERROR_DEVICE, who + "the rows' sizes exceed the bound (the device's histograms are not a frame's)");
-    for (int s = 0; s < png_stream::SYMBOLS; s++) table_words[s] = (unsigned int)t.code[s] | ((unsigned int)t.length[s] << 16);
+    for (int s = 0; s < e->symbols; s++) table_words[s] = (unsigned int)t.code[s] | ((unsigned int)t.length[s] << 16);
     std::copy(t.header, t.header + png_stream::HEADER_WORDS, header_words);
     // the second: placement up, the stream zeroed (the pack ORs the words segments share), the pack, the stream down
     unsigned int* stream_at = e->scratch + gr_png_encoder::GUARD_WORDS;
@@ -1435,10 +1454,10 @@ int gr_png_encode_rgba8(gr_png_encoder* e, void* stream, const void* device_rgba
         int w = width, h = height, header_bits = t.header_bits;
         const unsigned long long* offsets_on_device = (const unsigned long long*)e->placement;
         const unsigned int* table_on_device = (const unsigned int*)(e->placement + ((size_t)height + 1) * 8);
-        const unsigned int* header_on_device = table_on_device + png_stream::SYMBOLS;
+        const unsigned int* header_on_device = table_on_device + e->symbols;
         unsigned long long word_count = stream_words;
         void* args[] = {&device_rgba8, &w, &h, &table_on_device, &header_on_device, &header_bits, &offsets_on_device, &stream_at, &word_count};
-        int rc = launch(p, K_PNG_PACK, stream, (unsigned)height, 1, 64, 4, args);
+        int rc = launch(p, runs ? K_PNG_PACK_RUNS : K_PNG_PACK, stream, (unsigned)height, 1, 64, 4, args);
         if (rc != GR_OK) return rc;
     }
     if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[3], on));

@@ -24,6 +24,17 @@
 // workgroup's buffer starts at the word that holds the segment's first byte, with the neighbour's bits in it left 0, and a word is stored
 // with atomicOr when it is the segment's first or its last word and with a plain store otherwise (a word that is neither lies inside the
 // segment whole).  No store goes past stream_word_count, whatever the offsets say.
+//
+// Both kernels are instances of one template over the stream kind: gr_png_histogram and gr_png_pack are kind 0 (literals only),
+// gr_png_histogram_runs and gr_png_pack_runs kind 1 (previous-pixel run matches; the header states the stream).  What kind 1 adds: a pass
+// of 256 lanes is four waves and a wave's 64 pixels are one group of the stream (passes start at multiples of 256), so a wave tokenises
+// its own group - every lane compares its filtered pixel with the lane's before it (a shuffle; lane 0 loads pixel x - 1 itself), one
+// ballot gives the group's repeat mask, and from the mask a lane knows what it is: four literals (its bit is 0), the head of a run (its bit
+// is 1 and the bit below is 0, or it is lane 0; the run's length is the count of 1 bits from its own up) or nothing (inside a run).  No scan
+// crosses waves.  The histogram counts a head's length symbol (RFC 1951 3.2.5, computed, no table) in bins 257 ... 284 - 285 bins a row, bin
+// 256 left 0 for the host's end-of-block - and nothing for a pixel inside a run, while the Adler sums still run over all filtered bytes.
+// The pack's item of a head is the length symbol's code, its extra bits and the one 0 bit of the distance code, 21 bits at most; a lane
+// inside a run has an item of 0 bits, which png_emit places nowhere.
 
 #define GR_PNG_LANES 256
 // 31 carried bits and 256 items of at most 60 bits are 15 391 bits, 481 words; an item's OR may name two words more
@@ -36,27 +47,78 @@ __device__ __forceinline__ unsigned int png_filtered_pixel(const unsigned int* _
     return ((here | 0x80808080u) - (from & 0x7f7f7f7fu)) ^ ((here ^ ~from) & 0x80808080u);
 }
 
-// grid: height workgroups of 64 x 4.  frame_histogram: 256 words, zeroed by the launcher; row_histogram: height x 256 words;
-// row_sums: height x 2 words (sum of b, sum of (n - i) b, each mod 65521, over the row's pixel bytes)
-extern "C" __global__ void __launch_bounds__(GR_PNG_LANES) gr_png_histogram(const unsigned int* __restrict__ frame, int width, int height,
-                                                                            unsigned int* frame_histogram, unsigned int* __restrict__ row_histogram,
-                                                                            unsigned int* __restrict__ row_sums) {
-    __shared__ unsigned int bins[256];
+// what pixel x of a row is in the runs stream: PNG_LITERALS, the pixels of the run it heads (1 ... 64), or PNG_NOTHING - inside a run, or
+// past the row's end.  Every lane of the wave calls it, x = a multiple of 256 + t; f: the pixel's filtered bytes (0 past the row's end)
+#define PNG_LITERALS 0u
+#define PNG_NOTHING 0xffffffffu
+__device__ __forceinline__ unsigned int png_run_token(const unsigned int* __restrict__ frame, int width, int row, int x, unsigned int& f) {
+    const int lane = x & 63;   // in the wave, and of the pixel in its group
+    const bool in_row = x < width;
+    f = in_row ? png_filtered_pixel(frame, width, row, x) : 0u;
+    unsigned int before = (unsigned int)__shfl_up((int)f, 1, 64);
+    if (lane == 0 && in_row && x > 0) before = png_filtered_pixel(frame, width, row, x - 1);   // the last pixel of the group before
+    const bool repeats = in_row && x > 0 && f == before;
+    const unsigned long long mask = __ballot(repeats);
+    if (!in_row) return PNG_NOTHING;
+    if (!repeats) return PNG_LITERALS;
+    if (lane && ((mask >> (lane - 1)) & 1ull)) return PNG_NOTHING;
+    const unsigned long long rest = ~(mask >> lane);   // its lowest 1 bit: the first pixel from this one up that does not repeat
+    return rest ? (unsigned int)__ffsll(rest) - 1u : 64u;
+}
+
+// the length symbol of a match of `run` pixels, 4 run bytes: with m = length - 3 the symbols 257 ... 264 are m = 0 ... 7, and four symbols
+// follow for every count of extra bits 1 ... 5, m = 8 ... 15, 16 ... 31 and so on
+__device__ __forceinline__ unsigned int png_length_symbol(unsigned int run, unsigned int& extra_bits, unsigned int& extra) {
+    const unsigned int m = 4u * run - 3u;
+    extra_bits = m < 8u ? 0u : 29u - (unsigned int)__clz((int)m);
+    extra = m & ((1u << extra_bits) - 1u);
+    return 257u + 4u * extra_bits + (m >> extra_bits);
+}
+
+template <int KIND>
+__device__ __forceinline__ void png_histogram_row(const unsigned int* __restrict__ frame, int width, int height, unsigned int* frame_histogram,
+                                                  unsigned int* __restrict__ row_histogram, unsigned int* __restrict__ row_sums) {
+    constexpr int BINS = KIND ? 285 : 256;
+    __shared__ unsigned int bins[BINS];
     __shared__ unsigned int of_wave[2][4];
     const int t = (int)(threadIdx.y * 64 + threadIdx.x), row = (int)blockIdx.x;
     if (row >= height) return;   // (uniform)
     bins[t] = 0u;
+    if constexpr (BINS > GR_PNG_LANES)
+        if (t + GR_PNG_LANES < BINS) bins[t + GR_PNG_LANES] = 0u;
     __syncthreads();
     unsigned long long sum = 0ull, weighted = 0ull;
-    for (int x = t; x < width; x += GR_PNG_LANES) {
-        const unsigned int f = png_filtered_pixel(frame, width, row, x);
-        const unsigned int weight = 4u * (unsigned int)(width - x);   // n - i of the pixel's first byte
+    if constexpr (KIND == 0) {
+        for (int x = t; x < width; x += GR_PNG_LANES) {
+            const unsigned int f = png_filtered_pixel(frame, width, row, x);
+            const unsigned int weight = 4u * (unsigned int)(width - x);   // n - i of the pixel's first byte
 #pragma unroll
-        for (unsigned int c = 0; c < 4u; c++) {
-            const unsigned int b = (f >> (8u * c)) & 255u;
-            atomicAdd(&bins[b], 1u);
-            sum += b;
-            weighted += (unsigned long long)(((weight - c) % 65521u) * b);
+            for (unsigned int c = 0; c < 4u; c++) {
+                const unsigned int b = (f >> (8u * c)) & 255u;
+                atomicAdd(&bins[b], 1u);
+                sum += b;
+                weighted += (unsigned long long)(((weight - c) % 65521u) * b);
+            }
+        }
+    } else {
+        for (int base = 0; base < width; base += GR_PNG_LANES) {   // (uniform: the ballot wants every lane)
+            const int x = base + t;
+            unsigned int f;
+            const unsigned int token = png_run_token(frame, width, row, x, f);
+            if (x < width) {
+                const unsigned int weight = 4u * (unsigned int)(width - x);
+#pragma unroll
+                for (unsigned int c = 0; c < 4u; c++) {
+                    const unsigned int b = (f >> (8u * c)) & 255u;
+                    if (token == PNG_LITERALS) atomicAdd(&bins[b], 1u);
+                    sum += b;
+                    weighted += (unsigned long long)(((weight - c) % 65521u) * b);
+                }
+                if (token != PNG_LITERALS && token != PNG_NOTHING) {
+                    unsigned int extra_bits, extra;
+                    atomicAdd(&bins[png_length_symbol(token, extra_bits, extra)], 1u);
+                }
+            }
         }
     }
     unsigned int a = (unsigned int)(sum % 65521ull), w = (unsigned int)(weighted % 65521ull);
@@ -74,8 +136,32 @@ extern "C" __global__ void __launch_bounds__(GR_PNG_LANES) gr_png_histogram(cons
         row_sums[2 * (size_t)row + 1] = (of_wave[1][0] + of_wave[1][1] + of_wave[1][2] + of_wave[1][3]) % 65521u;
     }
     const unsigned int mine = bins[t];
-    row_histogram[(size_t)row * 256 + (size_t)t] = mine;
+    row_histogram[(size_t)row * BINS + (size_t)t] = mine;
     if (mine) atomicAdd(&frame_histogram[t], mine);
+    if constexpr (BINS > GR_PNG_LANES) {   // (the bins behind the first 256: the length symbols)
+        static_assert(BINS <= 2 * GR_PNG_LANES, "a lane stores two bins at most");
+        const int u = t + GR_PNG_LANES;
+        if (u < BINS) {
+            const unsigned int more = bins[u];
+            row_histogram[(size_t)row * BINS + (size_t)u] = more;
+            if (more) atomicAdd(&frame_histogram[u], more);
+        }
+    }
+}
+
+// grid: height workgroups of 64 x 4.  frame_histogram: 256 words, zeroed by the launcher; row_histogram: height x 256 words;
+// row_sums: height x 2 words (sum of b, sum of (n - i) b, each mod 65521, over the row's pixel bytes)
+extern "C" __global__ void __launch_bounds__(GR_PNG_LANES) gr_png_histogram(const unsigned int* __restrict__ frame, int width, int height,
+                                                                            unsigned int* frame_histogram, unsigned int* __restrict__ row_histogram,
+                                                                            unsigned int* __restrict__ row_sums) {
+    png_histogram_row<0>(frame, width, height, frame_histogram, row_histogram, row_sums);
+}
+
+// the runs stream's: frame_histogram 285 words, row_histogram height x 285 words - a bin a symbol, [256] left 0
+extern "C" __global__ void __launch_bounds__(GR_PNG_LANES) gr_png_histogram_runs(const unsigned int* __restrict__ frame, int width, int height,
+                                                                                 unsigned int* frame_histogram, unsigned int* __restrict__ row_histogram,
+                                                                                 unsigned int* __restrict__ row_sums) {
+    png_histogram_row<1>(frame, width, height, frame_histogram, row_histogram, row_sums);
 }
 
 // where a row's workgroup is in its segment: buffer[0] of the pass is word `word_at` of the stream and holds `fill` bits already
@@ -134,19 +220,17 @@ __device__ __forceinline__ void png_emit(png_segment& s, unsigned int* buffer, u
     s.fill = last ? 0u : (total & 31u);
 }
 
-// grid: height workgroups of 64 x 4.  table: 257 words, code | length << 16, the code bit-reversed; header: the block header's bits from
-// bit 0 of word 0 up, the bits past header_bits 0; row_offset: height + 1 byte offsets of the segments in the stream (the last: its size);
-// stream_words: zeroed by the launcher on this stream, stream_word_count words
-extern "C" __global__ void __launch_bounds__(GR_PNG_LANES) gr_png_pack(const unsigned int* __restrict__ frame, int width, int height,
-                                                                       const unsigned int* __restrict__ table, const unsigned int* __restrict__ header,
-                                                                       int header_bits, const unsigned long long* __restrict__ row_offset,
-                                                                       unsigned int* stream_words, unsigned long long stream_word_count) {
-    __shared__ unsigned int codes[257];
+template <int KIND>
+__device__ __forceinline__ void png_pack_row(const unsigned int* __restrict__ frame, int width, int height, const unsigned int* __restrict__ table,
+                                             const unsigned int* __restrict__ header, int header_bits, const unsigned long long* __restrict__ row_offset,
+                                             unsigned int* stream_words, unsigned long long stream_word_count) {
+    constexpr int SYMBOLS = KIND ? 285 : 257;
+    __shared__ unsigned int codes[SYMBOLS];
     __shared__ unsigned int buffer[GR_PNG_BUFFER_WORDS];
     __shared__ unsigned int wave_bits[4];
     const int t = (int)(threadIdx.y * 64 + threadIdx.x), row = (int)blockIdx.x;
     if (row >= height) return;   // (uniform)
-    for (int i = t; i < 257; i += GR_PNG_LANES) codes[i] = table[i];
+    for (int i = t; i < SYMBOLS; i += GR_PNG_LANES) codes[i] = table[i];
     for (int i = t; i < GR_PNG_BUFFER_WORDS; i += GR_PNG_LANES) buffer[i] = 0u;
     const unsigned long long begin = row_offset[row], end = row_offset[row + 1];
     png_segment s;
@@ -176,13 +260,32 @@ extern "C" __global__ void __launch_bounds__(GR_PNG_LANES) gr_png_pack(const uns
         const int x = base + t;
         unsigned long long bits = 0ull;
         unsigned int count = 0u;
-        if (x < width) {
-            const unsigned int f = png_filtered_pixel(frame, width, row, x);
+        if constexpr (KIND == 0) {
+            if (x < width) {
+                const unsigned int f = png_filtered_pixel(frame, width, row, x);
 #pragma unroll
-            for (unsigned int c = 0; c < 4u; c++) {
-                const unsigned int e = codes[(f >> (8u * c)) & 255u];
-                bits |= (unsigned long long)(e & 0xffffu) << count;
-                count += e >> 16;
+                for (unsigned int c = 0; c < 4u; c++) {
+                    const unsigned int e = codes[(f >> (8u * c)) & 255u];
+                    bits |= (unsigned long long)(e & 0xffffu) << count;
+                    count += e >> 16;
+                }
+            }
+        } else {
+            unsigned int f;
+            const unsigned int token = png_run_token(frame, width, row, x, f);
+            if (token == PNG_LITERALS) {
+#pragma unroll
+                for (unsigned int c = 0; c < 4u; c++) {
+                    const unsigned int e = codes[(f >> (8u * c)) & 255u];
+                    bits |= (unsigned long long)(e & 0xffffu) << count;
+                    count += e >> 16;
+                }
+            } else if (token != PNG_NOTHING) {
+                // a match: the length symbol's code, its extra bits, the distance code's one bit (0)
+                unsigned int extra_bits, extra;
+                const unsigned int e = codes[png_length_symbol(token, extra_bits, extra)];
+                bits = (unsigned long long)(e & 0xffffu) | ((unsigned long long)extra << (e >> 16));
+                count = (e >> 16) + extra_bits + 1u;
             }
         }
         png_emit(s, buffer, wave_bits, t, bits, count, false);
@@ -201,4 +304,22 @@ extern "C" __global__ void __launch_bounds__(GR_PNG_LANES) gr_png_pack(const uns
         }
         png_emit(s, buffer, wave_bits, t, bits, count, true);
     }
+}
+
+// grid: height workgroups of 64 x 4.  table: 257 words, code | length << 16, the code bit-reversed; header: the block header's bits from
+// bit 0 of word 0 up, the bits past header_bits 0; row_offset: height + 1 byte offsets of the segments in the stream (the last: its size);
+// stream_words: zeroed by the launcher on this stream, stream_word_count words
+extern "C" __global__ void __launch_bounds__(GR_PNG_LANES) gr_png_pack(const unsigned int* __restrict__ frame, int width, int height,
+                                                                       const unsigned int* __restrict__ table, const unsigned int* __restrict__ header,
+                                                                       int header_bits, const unsigned long long* __restrict__ row_offset,
+                                                                       unsigned int* stream_words, unsigned long long stream_word_count) {
+    png_pack_row<0>(frame, width, height, table, header, header_bits, row_offset, stream_words, stream_word_count);
+}
+
+// the runs stream's: table 285 words
+extern "C" __global__ void __launch_bounds__(GR_PNG_LANES) gr_png_pack_runs(const unsigned int* __restrict__ frame, int width, int height,
+                                                                            const unsigned int* __restrict__ table, const unsigned int* __restrict__ header,
+                                                                            int header_bits, const unsigned long long* __restrict__ row_offset,
+                                                                            unsigned int* stream_words, unsigned long long stream_word_count) {
+    png_pack_row<1>(frame, width, height, table, header, header_bits, row_offset, stream_words, stream_word_count);
 }

@@ -92,23 +92,30 @@ struct bit_string {
 };
 }   // namespace
 
-void build_table(const uint64_t histogram[SYMBOLS], table& out) {
-    uint64_t count[SYMBOLS];
-    std::copy(histogram, histogram + SYMBOLS, count);
+void build_table(const uint64_t* histogram, int stream_kind, table& out) {
+    const int symbols = symbols_of(stream_kind), distances = stream_kind == GR_PNG_STREAM_RUNS ? 4 : 1;
+    uint64_t count[MAX_SYMBOLS];
+    std::copy(histogram, histogram + symbols, count);
     if (!count[END_OF_BLOCK]) count[END_OF_BLOCK] = 1;
-    limited_lengths(count, SYMBOLS, MAX_LENGTH, out.length);
-    canonical_codes(out.length, SYMBOLS, out.code);
-    // the code lengths as deflate sends them: 257 literal/length lengths and the one distance length - 0, no distance code at all, which
-    // is what RFC 1951 3.2.7 gives a block of literals only - run-length coded (16: the last length 3 ... 6 more times; 17, 18: 3 ... 10
-    // and 11 ... 138 zeros)
-    uint8_t sent[SYMBOLS + 1];
-    std::copy(out.length, out.length + SYMBOLS, sent);
-    sent[SYMBOLS] = 0;
+    out.symbols = symbols;
+    std::fill(out.length, out.length + MAX_SYMBOLS, (uint8_t)0);
+    std::fill(out.code, out.code + MAX_SYMBOLS, (uint16_t)0);
+    limited_lengths(count, symbols, MAX_LENGTH, out.length);
+    canonical_codes(out.length, symbols, out.code);
+    // the code lengths as deflate sends them: the literal/length lengths and the distance lengths - literals: one, 0, no distance code at
+    // all, which is what RFC 1951 3.2.7 gives a block of literals only; runs: 0 0 0 1, the one distance code of one bit that the same
+    // paragraph allows, whether the frame has a match or not - run-length coded as one sequence (16: the last length 3 ... 6 more times;
+    // 17, 18: 3 ... 10 and 11 ... 138 zeros)
+    uint8_t sent[MAX_SYMBOLS + 4];
+    const int sent_count = symbols + distances;
+    std::copy(out.length, out.length + symbols, sent);
+    std::fill(sent + symbols, sent + sent_count, (uint8_t)0);
+    if (stream_kind == GR_PNG_STREAM_RUNS) sent[sent_count - 1] = 1;
     struct item { uint8_t symbol, extra_bits, extra; };
     std::vector<item> items;
-    for (int i = 0; i < SYMBOLS + 1;) {
+    for (int i = 0; i < sent_count;) {
         int run = 1;
-        while (i + run < SYMBOLS + 1 && sent[i + run] == sent[i]) run++;
+        while (i + run < sent_count && sent[i + run] == sent[i]) run++;
         const uint8_t v = sent[i];
         i += run;
         if (v == 0) {
@@ -134,8 +141,8 @@ void build_table(const uint64_t histogram[SYMBOLS], table& out) {
     bit_string h{out.header};
     h.put(0, 1);                    // BFINAL: the stream ends with a block of its own
     h.put(2, 2);                    // BTYPE: dynamic Huffman
-    h.put(SYMBOLS - 257, 5);        // HLIT
-    h.put(0, 5);                    // HDIST: one distance length
+    h.put((uint32_t)symbols - 257, 5);     // HLIT
+    h.put((uint32_t)distances - 1, 5);     // HDIST
     h.put((uint32_t)sent_lengths - 4, 4);
     for (int i = 0; i < sent_lengths; i++) h.put(length_of[ORDER[i]], 3);
     for (auto& it : items) {
@@ -147,10 +154,26 @@ void build_table(const uint64_t histogram[SYMBOLS], table& out) {
 
 // ---------------------------------------------------------------------------------------------------------------- sizes
 
-uint64_t row_block_bits(const table& t, int row, const uint32_t row_histogram[256]) {
+uint64_t row_block_bits(const table& t, int row, const uint32_t* row_histogram) {
     uint64_t bits = (uint64_t)t.header_bits + t.length[filter_of_row(row)] + t.length[END_OF_BLOCK];
     for (int v = 0; v < 256; v++) bits += (uint64_t)t.length[v] * row_histogram[v];
+    for (int s = FIRST_LENGTH_SYMBOL; s < t.symbols; s++) bits += (uint64_t)(t.length[s] + extra_bits_of(s) + 1) * row_histogram[s];
     return bits;
+}
+
+void tokenise_row(const uint8_t* filtered, int width, int stream_kind, int* run) {
+    std::fill(run, run + width, 0);
+    if (stream_kind != GR_PNG_STREAM_RUNS) return;
+    for (int x = 1; x < width;) {
+        if (memcmp(filtered + 4 * (size_t)x, filtered + 4 * (size_t)(x - 1), 4) != 0) { x++; continue; }
+        // a maximal run of repeats that ends with its group of GROUP_PIXELS at the latest
+        const int end_of_group = std::min(width, (x / GROUP_PIXELS + 1) * GROUP_PIXELS);
+        int r = 1;
+        while (x + r < end_of_group && memcmp(filtered + 4 * (size_t)(x + r), filtered + 4 * (size_t)(x + r - 1), 4) == 0) r++;
+        run[x] = r;
+        std::fill(run + x + 1, run + x + r, -1);
+        x += r;
+    }
 }
 
 namespace {
@@ -293,48 +316,64 @@ int gr_png_encode_bound(int width, int height, size_t* bytes) {
     return GR_OK;
 }
 
-int gr_png_build_table(const unsigned long long* histogram, unsigned char* lengths, unsigned short* codes, unsigned int* header_words, int* header_bits) {
-    if (!histogram || !lengths || !codes || !header_words || !header_bits) return refuse("gr_png_build_table", "a required pointer is NULL", false);
-    uint64_t h[ps::SYMBOLS];
-    std::copy(histogram, histogram + ps::SYMBOLS, h);
+}   // extern "C"
+
+namespace {
+int build_table_of(const char* who, const unsigned long long* histogram, int stream_kind, unsigned char* lengths, unsigned short* codes,
+                   unsigned int* header_words, int* header_bits) {
+    if (!histogram || !lengths || !codes || !header_words || !header_bits) return refuse(who, "a required pointer is NULL", false);
+    if (!ps::known_kind(stream_kind)) return refuse(who, "an unknown stream kind " + std::to_string(stream_kind), false);
+    const int symbols = ps::symbols_of(stream_kind);
+    uint64_t h[ps::MAX_SYMBOLS];
+    std::copy(histogram, histogram + symbols, h);
     ps::table t;
-    ps::build_table(h, t);
-    std::copy(t.length, t.length + ps::SYMBOLS, lengths);
-    std::copy(t.code, t.code + ps::SYMBOLS, codes);
+    ps::build_table(h, stream_kind, t);
+    std::copy(t.length, t.length + symbols, lengths);
+    std::copy(t.code, t.code + symbols, codes);
     std::copy(t.header, t.header + ps::HEADER_WORDS, header_words);
     *header_bits = t.header_bits;
     return GR_OK;
 }
 
-int gr_png_encode_rgba8_host(const unsigned char* rgba8, int width, int height, unsigned char* out_file, size_t capacity, size_t* out_bytes) {
-    const char* who = "gr_png_encode_rgba8_host";
+// the host encoder of both kinds: a row is its tokens - a pixel is four literals, the head of a match or nothing (literals stream: always
+// four literals) - and everything else is shared
+int encode_host(const char* who, const unsigned char* rgba8, int width, int height, unsigned char* out_file, size_t capacity, size_t* out_bytes,
+                int stream_kind) {
     bool too_small = false;
     const std::string wrong = ps::refusal(rgba8, width, height, out_file, capacity, out_bytes, &too_small);
     if (!wrong.empty()) return refuse(who, wrong, too_small);
-    const size_t n = 4 * (size_t)width;
+    if (!ps::known_kind(stream_kind)) return refuse(who, "an unknown stream kind " + std::to_string(stream_kind), false);
+    const size_t n = 4 * (size_t)width, bins = (size_t)ps::row_bins_of(stream_kind);
     std::vector<uint8_t> filtered(n);
+    std::vector<int> run(width);
     // first pass: the rows' histograms - the frame's is their sum plus the filter-type bytes and one end-of-block a row
-    std::vector<uint32_t> row_histogram((size_t)height * 256, 0u);
-    uint64_t histogram[ps::SYMBOLS] = {};
+    std::vector<uint32_t> row_histogram((size_t)height * bins, 0u);
+    uint64_t histogram[ps::MAX_SYMBOLS] = {};
     for (int r = 0; r < height; r++) {
         filter_row(rgba8, width, r, filtered.data());
-        uint32_t* mine = &row_histogram[(size_t)r * 256];
-        for (size_t i = 0; i < n; i++) mine[filtered[i]]++;
-        for (int v = 0; v < 256; v++) histogram[v] += mine[v];
+        ps::tokenise_row(filtered.data(), width, stream_kind, run.data());
+        uint32_t* mine = &row_histogram[(size_t)r * bins];
+        for (int x = 0; x < width; x++) {
+            if (run[x] > 0) mine[ps::length_code_of(run[x]).symbol]++;
+            if (run[x] == 0)
+                for (int c = 0; c < 4; c++) mine[filtered[4 * (size_t)x + c]]++;
+        }
+        for (size_t v = 0; v < bins; v++) histogram[v] += mine[v];
         histogram[ps::filter_of_row(r)]++;
     }
     histogram[ps::END_OF_BLOCK] = (uint64_t)height;
     ps::table t;
-    ps::build_table(histogram, t);
+    ps::build_table(histogram, stream_kind, t);
     // the sizes, before a bit is packed
     std::vector<uint64_t> offset((size_t)height + 1, 0);
-    for (int r = 0; r < height; r++) offset[r + 1] = offset[r] + ps::row_segment_bytes(ps::row_block_bits(t, r, &row_histogram[(size_t)r * 256]));
+    for (int r = 0; r < height; r++) offset[r + 1] = offset[r] + ps::row_segment_bytes(ps::row_block_bits(t, r, &row_histogram[(size_t)r * bins]));
     const uint64_t rows_bytes = offset[height];
     // second pass: the segments, each from a byte boundary, and the rows' Adler-32 values
     std::vector<uint8_t> rows(rows_bytes, 0);
     std::vector<uint32_t> adlers(height);
     for (int r = 0; r < height; r++) {
         filter_row(rgba8, width, r, filtered.data());
+        ps::tokenise_row(filtered.data(), width, stream_kind, run.data());
         uint8_t* segment = rows.data() + offset[r];
         uint64_t at = 0;   // in bits
         auto put = [&](uint32_t value, int count) {
@@ -344,7 +383,16 @@ int gr_png_encode_rgba8_host(const unsigned char* rgba8, int width, int height, 
         for (int b = 0; b < t.header_bits; b += 32) put(t.header[b >> 5], std::min(32, t.header_bits - b));
         const int f = ps::filter_of_row(r);
         put(t.code[f], t.length[f]);
-        for (size_t i = 0; i < n; i++) put(t.code[filtered[i]], t.length[filtered[i]]);
+        for (int x = 0; x < width; x++) {
+            if (run[x] > 0) {
+                const ps::length_code l = ps::length_code_of(run[x]);
+                put(t.code[l.symbol], t.length[l.symbol]);
+                put((uint32_t)l.extra, l.extra_bits);
+                put(0, 1);   // distance code 3, the only one: distance 4
+            }
+            if (run[x] == 0)
+                for (int c = 0; c < 4; c++) put(t.code[filtered[4 * (size_t)x + c]], t.length[filtered[4 * (size_t)x + c]]);
+        }
         put(t.code[ps::END_OF_BLOCK], t.length[ps::END_OF_BLOCK]);
         put(0, 3);                          // an empty stored block, not the last: BFINAL = 0, BTYPE = 0
         at = (at + 7) / 8 * 8;              // ... whose length field starts at a byte
@@ -362,6 +410,27 @@ int gr_png_encode_rgba8_host(const unsigned char* rgba8, int width, int height, 
     ps::write_container(out_file, width, height, rows.data(), rows_bytes, ps::join_adler(adlers.data(), width, height));
     *out_bytes = (size_t)ps::file_bytes(rows_bytes);
     return GR_OK;
+}
+}   // namespace
+
+extern "C" {
+
+int gr_png_build_table(const unsigned long long* histogram, unsigned char* lengths, unsigned short* codes, unsigned int* header_words, int* header_bits) {
+    return build_table_of("gr_png_build_table", histogram, GR_PNG_STREAM_LITERALS, lengths, codes, header_words, header_bits);
+}
+
+int gr_png_build_table_as(const unsigned long long* histogram, int stream_kind, unsigned char* lengths, unsigned short* codes, unsigned int* header_words,
+                          int* header_bits) {
+    return build_table_of("gr_png_build_table_as", histogram, stream_kind, lengths, codes, header_words, header_bits);
+}
+
+int gr_png_encode_rgba8_host(const unsigned char* rgba8, int width, int height, unsigned char* out_file, size_t capacity, size_t* out_bytes) {
+    return encode_host("gr_png_encode_rgba8_host", rgba8, width, height, out_file, capacity, out_bytes, GR_PNG_STREAM_LITERALS);
+}
+
+int gr_png_encode_rgba8_host_as(const unsigned char* rgba8, int width, int height, unsigned char* out_file, size_t capacity, size_t* out_bytes,
+                                int stream_kind) {
+    return encode_host("gr_png_encode_rgba8_host_as", rgba8, width, height, out_file, capacity, out_bytes, stream_kind);
 }
 
 }   // extern "C"

@@ -389,31 +389,51 @@ def png_encode_bound(width, height):
     return need.value
 
 
-def png_encode_host(pixels):
+def png_stream_kind(stream_kind):
+    """a stream kind as the library numbers it, from its number or its name ("literals", "runs")"""
+    from . import PNG_STREAM_NAMES
+    if isinstance(stream_kind, str):
+        if stream_kind not in PNG_STREAM_NAMES:
+            raise ValueError(f"PNG stream kind {stream_kind!r} (one of {', '.join(PNG_STREAM_NAMES)})")
+        return PNG_STREAM_NAMES[stream_kind]
+    return int(stream_kind)
+
+
+def png_encode_host(pixels, stream_kind=None):
     """the PNG file of RGBA8 pixels [H, W, 4] as bytes, by the host encoder that defines PngEncoder's stream (gr_png_encode_rgba8_host:
-    Sub / Up filters, one Huffman table a frame, literals only)"""
+    Sub / Up filters, one Huffman table a frame, literals only).  stream_kind ("literals", "runs" or PNG_STREAM_*): that kind's file
+    (gr_png_encode_rgba8_host_as)"""
     pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
     if pixels.ndim != 3 or pixels.shape[2] != 4:
         raise ValueError(f"png_encode_host: an image of shape {pixels.shape} is not [H, W, 4]")
     h, w = pixels.shape[:2]
     out = np.empty(png_encode_bound(w, h), dtype=np.uint8)
     size = ctypes.c_size_t()
-    check(lib.gr_png_encode_rgba8_host(pixels.ctypes.data_as(c_void_p), w, h, out.ctypes.data_as(c_void_p), out.nbytes, ctypes.byref(size)))
+    if stream_kind is None:
+        check(lib.gr_png_encode_rgba8_host(pixels.ctypes.data_as(c_void_p), w, h, out.ctypes.data_as(c_void_p), out.nbytes, ctypes.byref(size)))
+    else:
+        check(lib.gr_png_encode_rgba8_host_as(pixels.ctypes.data_as(c_void_p), w, h, out.ctypes.data_as(c_void_p), out.nbytes, ctypes.byref(size),
+                                              png_stream_kind(stream_kind)))
     return out[:size.value].tobytes()
 
 
 class PngEncoder:
     """A PNG encoder behind RGBA8 frames of one size that are already on the program's device (gr_png_encoder): filtering, histogram and
-    bit-packing run there, the compressed bytes come back.  encode() synchronises the stream it is given.  The program must outlive it."""
+    bit-packing run there, the compressed bytes come back.  encode() synchronises the stream it is given.  The program must outlive it.
+    stream_kind ("literals", "runs" or PNG_STREAM_*): the stream its files are written in (gr_png_encoder_create_as); None: literals."""
 
-    def __init__(self, program, width, height):
+    def __init__(self, program, width, height, stream_kind=None):
         self.program, self.width, self.height = program, int(width), int(height)   # (the program is borrowed: kept alive here)
         self.handle = c_void_p()
-        check(lib.gr_png_encoder_create(program.handle, self.width, self.height, ctypes.byref(self.handle)))
+        self.stream_kind = 0 if stream_kind is None else png_stream_kind(stream_kind)
+        if stream_kind is None:
+            check(lib.gr_png_encoder_create(program.handle, self.width, self.height, ctypes.byref(self.handle)))
+        else:
+            check(lib.gr_png_encoder_create_as(program.handle, self.width, self.height, self.stream_kind, ctypes.byref(self.handle)))
         self._out = np.empty(png_encode_bound(self.width, self.height), dtype=np.uint8)
 
     def encode(self, device_ptr, stream=None):
-        """the PNG file of the frame at device_ptr (width x height RGBA8 pixels) as bytes: png_encode_host's of the same pixels"""
+        """the PNG file of the frame at device_ptr (width x height RGBA8 pixels) as bytes: png_encode_host's of the same pixels and kind"""
         size = ctypes.c_size_t()
         check(lib.gr_png_encode_rgba8(self.handle, stream, device_ptr, self._out.ctypes.data_as(c_void_p), self._out.nbytes, ctypes.byref(size)))
         return self._out[:size.value].tobytes()
@@ -429,7 +449,7 @@ class PngEncoder:
         check(lib.gr_png_encoder_time_launches(self.handle, int(bool(on))))
 
     def launch_ms(self):
-        """(gr_png_histogram, gr_png_pack) of the last encode after time_launches(), in milliseconds"""
+        """(gr_png_histogram, gr_png_pack - or their _runs instances) of the last encode after time_launches(), in milliseconds"""
         ms = (c_float * 2)()
         check(lib.gr_png_encoder_launch_ms(self.handle, ms))
         return ms[0], ms[1]

@@ -149,10 +149,20 @@ def camera_path_at(position, quat, position_to=None, quat_to=None, frames=1, tim
     return poses
 
 
+def checked_png_stream(who, png, png_stream):
+    """the PNG stream kind as gra.PNG_STREAM_*; a kind other than literals is a property of device-made files"""
+    if png_stream not in gra.PNG_STREAM_NAMES and png_stream not in gra.PNG_STREAM_NAMES.values():
+        raise ValueError(f"{who}: png_stream={png_stream!r} ({', '.join(gra.PNG_STREAM_NAMES)})")
+    kind = gra.PNG_STREAM_NAMES.get(png_stream, png_stream)
+    if kind != gra.PNG_STREAM_LITERALS and png != "device":
+        raise ValueError(f"{who}: png_stream={png_stream!r} needs png='device' (the host writer has one stream)")
+    return kind
+
+
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
            parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box",
-           png="host", jpeg=None, quality=90):
+           png="host", jpeg=None, quality=90, png_stream="literals"):
     """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
@@ -177,6 +187,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     png: "device" (with rgba8) - every frame returned is the bytes of a finished PNG file instead of pixels: the RGBA8 frame stays on the
     device, is filtered, histogrammed and bit-packed there (pipeline.PngEncoder) and only the compressed bytes come back - the file
     pipeline.png_encode_host makes of the rgba8 frame, byte for byte.
+    png_stream: "literals" or "runs" (or a gra.PNG_STREAM_* value; other than literals only with png="device") - the stream kind of those
+    files: runs adds previous-pixel run matches (pipeline.png_encode_host(pixels, "runs") is then the file, byte for byte).
     jpeg: "host" or "device" (with rgba8; not with png="device") - every frame returned is the bytes of a finished baseline JPEG file at
     `quality` (1 ... 100): with "device" the RGBA8 frame stays on the device and is converted, transformed, quantised and Huffman-coded there
     (pipeline.JpegEncoder), with "host" its pixels come back and pipeline.jpeg_encode_host makes the file - the same bytes."""
@@ -188,6 +200,7 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
         raise ValueError(f"render: quality={quality!r} (1 to 100)")
     if png not in ("host", "device") or (png == "device" and (not rgba8 or yuv420)):
         raise ValueError(f"render: png={png!r} (host, or device with rgba8=True and no yuv420)")
+    png_stream = checked_png_stream("render", png, png_stream)
     if bit_depth not in (8, 10) or (bit_depth == 10 and not yuv420):
         raise ValueError(f"render: bit_depth={bit_depth!r} (8, or 10 with yuv420=True)")
     if cameras is not None and geodesic_speed is not None:
@@ -216,7 +229,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
         dbg = DeviceBuffer.from_numpy(device, packed)
     out_bytes = fmt.bytes(width, height)
     out = DeviceBuffer(device, out_bytes)
-    encoder = gra.PngEncoder(program, width, height) if png == "device" else gra.JpegEncoder(program, width, height, quality) if jpeg == "device" else None
+    encoder = (gra.PngEncoder(program, width, height, png_stream) if png == "device" else
+               gra.JpegEncoder(program, width, height, quality) if jpeg == "device" else None)
     pinned = PinnedBuffer(out_bytes) if frame_format != gra.FRAME_F32 and encoder is None else None   # (a float frame is downloaded as it always was)
     cam = gra.default_camera(camera_pos, camera_quat)
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
@@ -288,19 +302,21 @@ def split_block_rows(height, block_rows=16):
 
 def render_split(metric_name, width, height, devices, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, background=None,
                  fov=90.0, universe=20.0, wait_for_static=True, supersample=1, rgba8=False, mips="host", frames=1, block_rows=16, png="host", jpeg=None,
-                 quality=90):
+                 quality=90, png_stream="literals"):
     """render() of a Cartesian camera with the rows of every frame dealt to `devices` (TiledFrame.local: one process, peer copies, participant
     r on devices[r]; a device may be named more than once, which is how a box with one GPU rehearses it).  Every device has its own program,
     sky (with mips="device" built there, once per device) and render state, traces its share at `supersample` x per axis, resolves it
     there and ships width x rows pixels to devices[0] - float4, or with rgba8 4 bytes each (TiledFrame.render_as).  Frame k is rendered
     with rotation k, so the shares go round over `frames`.  Returns the list of frames: the arrays render() returns, bit for bit.  png="device"
-    (with rgba8): the finished frame on devices[0] is encoded there (pipeline.PngEncoder) and every frame returned is a PNG file's bytes.
+    (with rgba8): the finished frame on devices[0] is encoded there (pipeline.PngEncoder) and every frame returned is a PNG file's bytes, in
+    the stream kind png_stream ("literals" or "runs", as render() takes it).
     jpeg="host" or "device" (with rgba8, not with png="device"): every frame returned is a JPEG file's bytes at `quality`, made by
     pipeline.jpeg_encode_host of the downloaded frame or on devices[0] (pipeline.JpegEncoder) - the same bytes."""
     if mips not in ("host", "device"):
         raise ValueError(f"render_split: mips={mips!r} (host or device)")
     if png not in ("host", "device") or (png == "device" and not rgba8):
         raise ValueError(f"render_split: png={png!r} (host, or device with rgba8=True)")
+    png_stream = checked_png_stream("render_split", png, png_stream)
     if jpeg not in (None, "host", "device") or (jpeg is not None and (not rgba8 or png == "device")) or (jpeg is not None and not 1 <= int(quality) <= 100):
         raise ValueError(f"render_split: jpeg={jpeg!r}, quality={quality!r} (None, or host or device with rgba8=True, png='host' and a quality of 1 to 100)")
     devices = [int(d) for d in devices]
@@ -327,7 +343,7 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
         states = [gra.RenderState(width, height, d, supersample=supersample) for d in devices]
         out = DeviceBuffer(devices[0], width * height * (4 if rgba8 else 16))
         cam = gra.default_camera(camera_pos, camera_quat)
-        encoder = (gra.PngEncoder(programs[devices[0]], width, height) if png == "device" else
+        encoder = (gra.PngEncoder(programs[devices[0]], width, height, png_stream) if png == "device" else
                    gra.JpegEncoder(programs[devices[0]], width, height, quality) if jpeg == "device" else None)
         result = []
         for k in range(max(int(frames), 1)):
@@ -378,6 +394,9 @@ def main(argv=None):
     ap.add_argument("--png", choices=["host", "device"], default="host", help="where a frame becomes a PNG file: host = the pixels come back and one host "
                     "thread deflates them; device = the 8-bit frame is filtered, histogrammed and Huffman-coded on the GPU (Sub / Up filters, one "
                     "table a frame, no matches) and only the compressed bytes come back.  device implies --encode device; not with --out NAME.y4m")
+    ap.add_argument("--png-stream", choices=sorted(gra.PNG_STREAM_NAMES, key=gra.PNG_STREAM_NAMES.get), default=None, help="the stream of a PNG made "
+                    "with --png device: literals (the default: no matches) or runs (runs of pixels whose filtered bytes repeat the previous "
+                    "pixel's become matches of distance 4: smaller files of the same pixels).  Only with --png device")
     ap.add_argument("--jpeg", choices=["host", "device"], default=None, help="where a frame of --out NAME.jpg or NAME.avi becomes a baseline JPEG file "
                     "(JFIF, 4:2:0, the standard Huffman tables, one restart interval a row of 16 x 16 blocks): host (the default) = the 8-bit pixels "
                     "come back and one host thread encodes them; device = colour conversion, DCT, quantiser and Huffman coding run on the GPU and only "
@@ -414,6 +433,10 @@ def main(argv=None):
         ap.error(f"--fps: {e}")
     if a.bit_depth != 8 and not video:
         ap.error("--bit-depth 10 is a depth of video frames: it needs --out NAME.y4m (a PNG is 8-bit sRGB, and so is a JPEG or a Motion-JPEG file)")
+    if a.png_stream is not None and a.png != "device":
+        ap.error(f"--png-stream {a.png_stream} without --png device: the stream kind is one of device-made PNG files (--png host has one stream); "
+                 "give --png device")
+    a.png_stream = a.png_stream or "literals"
     if a.png == "device":
         if video:
             ap.error("--png device with --out NAME.y4m: a video file holds no PNG; --png is about --out NAME.png")
@@ -471,7 +494,7 @@ def main(argv=None):
         result = render_split(a.metric, w, h, devices, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
                               [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, read_png(a.background) if a.background else None,
                               a.fov, a.universe, supersample=a.supersample, rgba8=a.encode == "device", mips=a.mips, frames=a.frames, png=a.png,
-                              jpeg=a.jpeg, quality=a.quality or 90)
+                              jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream)
         if avi:
             with AviWriter(a.out, w, h, fps) as stream:
                 for frame in result:
@@ -497,7 +520,7 @@ def main(argv=None):
                     geodesic_times=[a.geodesic_time + float(t) * a.geodesic_dt for t in moments] if samples else times,
                     parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
                     rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples,
-                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90)
+                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream)
     if speed is None and cameras is None:
         result = [result]
     if video:

@@ -323,21 +323,61 @@ int gr_render_state_filter(const gr_render_state* s, int* filter);
  *               lowest-numbered others as leaves that never occur (two leaves of one bit).  HLIT = 257, HDIST = 1 with the one distance
  *               length 0 (RFC 1951 3.2.7: no distance codes, literals only); the 258 lengths run-length coded (16, 17, 18) and coded
  *               with lengths limited to 7 in the same way.
- *   checksums   the Adler-32 is joined from the rows' (adler32_combine), the chunk CRCs are taken on the host over the finished bytes. */
+ *   checksums   the Adler-32 is joined from the rows' (adler32_combine), the chunk CRCs are taken on the host over the finished bytes.
+ *
+ * A second stream kind, opt-in, beside that one (GR_PNG_STREAM_LITERALS, the default of everything that takes no kind): GR_PNG_STREAM_RUNS
+ * adds the one LZ77 match a rendered frame is full of and a wave finds without a search - "this pixel's four filtered bytes are the
+ * previous pixel's".  Container, row filters, zlib framing, one dynamic block a row with the frame's header repeated, the empty stored
+ * block and the checksums are the ones above; what differs:
+ *   repeats     q[x] is the four filtered bytes of pixel x of a row as one 32-bit word; repeat[x] = x >= 1 and q[x] == q[x - 1].  Pixel 0
+ *               never repeats: nothing refers across the filter byte or into the row before.
+ *   tokens      pixels are taken in groups of 64 by position (x / 64).  Inside a group every maximal run of consecutive pixels with repeat
+ *               set is one match of distance 4 and length 4 * run, 4 ... 256 bytes (the minimum run is 1 pixel, a constant of the stream);
+ *               the first pixel of a group may repeat the last pixel of the group before, and a run ends with its group whatever follows:
+ *               no match crosses a group boundary, so a run of repeats over a boundary is two matches.  Every other pixel is four
+ *               literals.  In the block: the filter byte's literal, the tokens in pixel order - a match is its length symbol's code, the
+ *               symbol's extra bits, and the one bit 0 of the distance code -, end-of-block.
+ *   alphabets   literal/length symbols 0 ... 284, HLIT = 285: lengths 4 ... 256 by RFC 1951 3.2.5 (symbol 258 = 4 ... 264 = 10 without extra
+ *               bits, then four symbols each with 1 ... 5 extra bits; 256 is symbol 284 with extra 29).  HDIST = 4 with the distance lengths
+ *               0 0 0 1: distance code 3 is distance 4 and has no extra bits; the single one-bit distance code is what RFC 1951 3.2.7
+ *               allows and zlib accepts.  These four lengths are always sent, also for a frame without a match.
+ *   table       one per frame from the frame's histogram over literals (filter bytes included), one end-of-block a row and the matches'
+ *               length symbols, by the rules above (tie-breaks, the limit of 15, Kraft's sum restored); the 285 + 4 lengths run-length
+ *               coded as one sequence and coded with lengths limited to 7.
+ *   bit count   of a row's block, from the row's histogram alone: the header, the filter byte's and end-of-block's codes, and the sum over
+ *               the symbols of count x (code length + the symbol's extra bits), plus one bit for every match.
+ *   bound       gr_png_encode_bound holds for both kinds.  It counts 15 bits for every filtered byte and 4 096 bits of header a row.  A
+ *               match stands for 4 bytes or more and costs 15 + 5 + 1 bits at most, less than the 60 counted for its bytes.  The header
+ *               is 17 bits of counts, 19 x 3 bits and the code-length symbols of 289 lengths: 7 bits at most for a symbol that stands for
+ *               one length, 7 + 7 for one with extra bits, which stands for three lengths or more - 7 bits a length at most,
+ *               74 + 289 x 7 = 2 097 bits. */
+enum { GR_PNG_STREAM_LITERALS = 0, GR_PNG_STREAM_RUNS = 1 };
 typedef struct gr_png_encoder gr_png_encoder;
-/* What a file of this size never exceeds (every literal 15 bits, a block header of 512 bytes a row): the capacity both encoders ask for. */
+/* What a file of this size never exceeds, of either stream kind (every literal 15 bits, a block header of 512 bytes a row): the capacity both
+ * encoders ask for. */
 int gr_png_encode_bound(int width, int height, size_t* bytes);
 /* The host encoder: the definition of the bytes above.  rgba8: [height][width][4] bytes, R, G, B, A; *out_bytes: the file's size.  Both
  * encoders refuse, before anything is written or any device call is made, with a message that names the entry point: a NULL; a size below 1; a
  * frame pointer not aligned to 4 bytes; a frame of more than 2^31 - 1 raw bytes (4 a pixel); a capacity below gr_png_encode_bound
  * (GR_ERROR_BUFFER_TOO_SMALL; everything else GR_ERROR_INVALID_ARGUMENT).  out_file needs no alignment. */
 int gr_png_encode_rgba8_host(const unsigned char* rgba8, int width, int height, unsigned char* out_file, size_t capacity, size_t* out_bytes);
+/* The host encoder of a stream kind, the definition of that kind's bytes: GR_PNG_STREAM_LITERALS gives gr_png_encode_rgba8_host's file.
+ * Refuses what that one refuses and an unknown kind (GR_ERROR_INVALID_ARGUMENT). */
+int gr_png_encode_rgba8_host_as(const unsigned char* rgba8, int width, int height, unsigned char* out_file, size_t capacity, size_t* out_bytes, int stream_kind);
 /* The table builder on its own: histogram[257] (literals, then end-of-block; a 0 there is taken as 1) to lengths[257], codes[257] (bit-reversed:
  * written from bit 0 up), the block header as bits from bit 0 of header_words[0] up (128 words) and its bit count. */
 int gr_png_build_table(const unsigned long long* histogram, unsigned char* lengths, unsigned short* codes, unsigned int* header_words, int* header_bits);
+/* ... of a stream kind: GR_PNG_STREAM_LITERALS is gr_png_build_table; GR_PNG_STREAM_RUNS takes histogram[285] (literals, end-of-block, the
+ * length symbols 257 ... 284) and gives lengths[285], codes[285] and the header with HLIT = 285 and the four distance lengths 0 0 0 1. */
+int gr_png_build_table_as(const unsigned long long* histogram, int stream_kind, unsigned char* lengths, unsigned short* codes, unsigned int* header_words, int* header_bits);
 /* A device encoder for frames of one size on the program's device: owns the device scratch (the rows' histograms and Adler sums, the table,
  * the rows' offsets, the stream) and a pinned staging buffer of gr_png_encode_bound bytes.  The program is borrowed and must outlive it. */
 int gr_png_encoder_create(gr_program* p, int width, int height, gr_png_encoder** out);
+/* ... for a stream kind (gr_png_encoder_create: GR_PNG_STREAM_LITERALS); an unknown kind is refused before any device call.  Everything
+ * below serves whichever kind the encoder was made with: gr_png_encode_rgba8 then launches gr_png_histogram_runs and gr_png_pack_runs, its
+ * file is gr_png_encode_rgba8_host_as's of that kind byte for byte, and its first download is 1 140 bytes + 1 148 bytes a row (285 bins a
+ * row and the two Adler sums). */
+int gr_png_encoder_create_as(gr_program* p, int width, int height, int stream_kind, gr_png_encoder** out);
 void gr_png_encoder_destroy(gr_png_encoder* e);
 /* Encodes device_rgba8 (device memory, width x height pixels) into out_file (host memory): enqueues on `stream` - gr_png_histogram, one
  * download of the rows' histograms and Adler sums (1 KiB + 1 032 bytes a row), the table and the rows' offsets built on the host and
