@@ -79,11 +79,11 @@ const char* const KERNEL_NAMES[] = {
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
     "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack",
-    "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather", "gr_png_histogram_runs", "gr_png_pack_runs"};
+    "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather", "gr_png_histogram_runs", "gr_png_pack_runs", "gr_render_analytic"};
 enum KernelId {
     K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_JPEG_BLOCKS, K_JPEG_PACK, K_JPEG_GATHER, K_PNG_HISTOGRAM_RUNS, K_PNG_PACK_RUNS, K_COUNT
+    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_JPEG_BLOCKS, K_JPEG_PACK, K_JPEG_GATHER, K_PNG_HISTOGRAM_RUNS, K_PNG_PACK_RUNS, K_RENDER_ANALYTIC, K_COUNT
 };
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
@@ -703,7 +703,7 @@ int gr_program_create(const char* argument_string, int device, gr_program** out)
         if (hipModuleGetFunction(&p->fn[k], p->module, KERNEL_NAMES[k]) != hipSuccess) {
             p->fn[k] = nullptr;
             (void)hipGetLastError();
-            p->in_rest[k] = !(k == K_TRACE_PAIR || k == K_TRACE_FUSED_PARKING);
+            p->in_rest[k] = !(k == K_TRACE_PAIR || k == K_TRACE_FUSED_PARKING || k == K_RENDER_ANALYTIC);   // (gr_render_analytic: shading.hip puts it beside gr_render)
         }
     }
     if (!p->fn[K_TRACE_FUSED] || !p->fn[K_RENDER] || !p->fn[K_PREPASS_FUSED] || !p->fn[K_ORDER_TILES])
@@ -1107,6 +1107,112 @@ int gr_render_strips(gr_program* p, void* stream, const void* rdata, void* out, 
     void* args[] = {&rdata, &rdata_count, &out, &bg1, &bg2, &bg_width, &bg_height, &bg_levels, &width, &height,
                     &max_probes, &cfg, &dfg, &num, &block_pixels, &strip_rank, &strip_count, &compact_out, &seams_only};
     return launch(p, K_RENDER, stream, blocks(num, 256), 1, 256, 1, args);
+}
+
+// ---- the analytic sky (geodesic_hip_internal.h, "Analytic sky") ------------------------------------------------------------------------
+int gr_analytic_sky_default(gr_analytic_sky* out) {
+    if (!out) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_analytic_sky_default: null argument");
+    static const float quadrants[2][4][3] = {{{0.16f, 0.30f, 0.62f}, {0.66f, 0.26f, 0.20f}, {0.20f, 0.52f, 0.32f}, {0.72f, 0.60f, 0.22f}},
+                                             {{0.52f, 0.24f, 0.58f}, {0.22f, 0.56f, 0.60f}, {0.76f, 0.46f, 0.18f}, {0.40f, 0.62f, 0.24f}}};
+    out->meridians = 36;
+    out->parallels = 18;
+    out->line_width = 0.08f;
+    memcpy(out->quadrant, quadrants, sizeof(quadrants));
+    for (int side = 0; side < 2; side++)
+        for (int c = 0; c < 3; c++) out->line[side][c] = 0.02f;
+    return GR_OK;
+}
+
+// what every entry point that takes a sky refuses of it, under its own name
+extern "C" int gr_internal_check_analytic_sky(const char* who, const gr_analytic_sky* sky) {
+    const std::string w = who;
+    if (!sky) return fail(GR_ERROR_INVALID_ARGUMENT, w + ": null sky");
+    if (sky->meridians < 2 || sky->meridians > 360) return fail(GR_ERROR_INVALID_ARGUMENT, w + ": meridians " + std::to_string(sky->meridians) + " (2 to 360)");
+    if (sky->parallels < 1 || sky->parallels > 180) return fail(GR_ERROR_INVALID_ARGUMENT, w + ": parallels " + std::to_string(sky->parallels) + " (1 to 180)");
+    if (!(sky->line_width >= 0.f && sky->line_width <= 0.5f)) return fail(GR_ERROR_INVALID_ARGUMENT, w + ": line_width " + std::to_string(sky->line_width) + " (0 to 0.5)");
+    for (int side = 0; side < 2; side++) {
+        for (int q = 0; q < 4; q++)
+            for (int c = 0; c < 3; c++)
+                if (!(sky->quadrant[side][q][c] >= 0.f && sky->quadrant[side][q][c] <= 1.f))
+                    return fail(GR_ERROR_INVALID_ARGUMENT, w + ": quadrant[" + std::to_string(side) + "][" + std::to_string(q) + "][" + std::to_string(c) + "] is not in [0, 1]");
+        for (int c = 0; c < 3; c++)
+            if (!(sky->line[side][c] >= 0.f && sky->line[side][c] <= 1.f))
+                return fail(GR_ERROR_INVALID_ARGUMENT, w + ": line[" + std::to_string(side) + "][" + std::to_string(c) + "] is not in [0, 1]");
+    }
+    return GR_OK;
+}
+
+int gr_render_analytic(gr_program* p, void* stream, const void* rdata, const void* rdata_count, int num_pixels, void* out, const gr_analytic_sky* sky,
+                       int width, int height, const void* cfg, const void* dfg) {
+    GR_NEED("gr_render_analytic", rdata, rdata_count, out);
+    int rc = gr_internal_check_analytic_sky("gr_render_analytic", sky);
+    if (rc != GR_OK) return rc;
+    gr_analytic_sky by_value = *sky;
+    int block_pixels = num_pixels > 0 ? num_pixels : 1, rank = 0, count = 1, compact = 0;
+    void* args[] = {&rdata, &rdata_count, &out, &by_value, &width, &height, &cfg, &dfg, &num_pixels, &block_pixels, &rank, &count, &compact};
+    return launch(p, K_RENDER_ANALYTIC, stream, blocks(num_pixels, 256), 1, 256, 1, args);
+}
+
+int gr_render_analytic_strips(gr_program* p, void* stream, const void* rdata, void* out, const gr_analytic_sky* sky, int width, int height,
+                              int block_rows, int strip_rank, int strip_count, int compact_out, const void* cfg, const void* dfg) {
+    GR_NEED("gr_render_analytic_strips", rdata, out);
+    int rc = gr_internal_check_analytic_sky("gr_render_analytic_strips", sky);
+    if (rc != GR_OK) return rc;
+    if (block_rows <= 0 || strip_count <= 0 || strip_rank < 0 || strip_rank >= strip_count)
+        return fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_analytic_strips: bad strip parameters");
+    gr_analytic_sky by_value = *sky;
+    int local_blocks = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count);
+    int block_pixels = block_rows * width;
+    int num = local_blocks * block_pixels;
+    const void* rdata_count = p ? p->huge_count : nullptr;
+    void* args[] = {&rdata, &rdata_count, &out, &by_value, &width, &height, &cfg, &dfg, &num, &block_pixels, &strip_rank, &strip_count, &compact_out};
+    return launch(p, K_RENDER_ANALYTIC, stream, blocks(num, 256), 1, 256, 1, args);
+}
+
+namespace {
+// steps 2 and 3 of the definition, in double
+double sky_line_coverage(double x, double h, int n, double w) {
+    const double t = x * n, a = h * n;
+    auto covered_below = [&](double at) { const double s = at + w / 2, k = std::floor(s); return k * w + std::min(s - k, w); };
+    return (covered_below(t + a) - covered_below(t - a)) / (2 * a);
+}
+double sky_upper_half_share(double x, double h, bool periodic) {
+    auto below = [&](double at) { const double k = periodic ? std::floor(at) : 0.0; return k / 2 + std::max(at - k - 0.5, 0.0); };
+    return (below(x + h) - below(x - h)) / (2 * h);
+}
+}   // namespace
+
+int gr_analytic_sky_image(const gr_analytic_sky* sky, int side, int width, int height, unsigned char* out_rgba8) {
+    int rc = gr_internal_check_analytic_sky("gr_analytic_sky_image", sky);
+    if (rc != GR_OK) return rc;
+    if (!out_rgba8) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_analytic_sky_image: null out_rgba8");
+    if (side != 0 && side != 1) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_analytic_sky_image: side " + std::to_string(side) + " (0 or 1)");
+    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_analytic_sky_image: width and height");
+    const double floor_h = std::ldexp(1.0, -14);
+    const double hu = std::max(0.5 / width, floor_h), hv = std::max(0.5 / height, floor_h);
+    std::vector<double> cu(width), fu(width);
+    for (int x = 0; x < width; x++) {
+        const double u = (x + 0.5) / width;
+        cu[x] = sky_line_coverage(u, hu, sky->meridians, sky->line_width);
+        fu[x] = sky_upper_half_share(u, hu, true);
+    }
+    for (int y = 0; y < height; y++) {
+        const double v = (y + 0.5) / height;
+        const double cv = sky_line_coverage(v, hv, sky->parallels, sky->line_width), fv = sky_upper_half_share(v, hv, false);
+        for (int x = 0; x < width; x++) {
+            const double g = 1 - (1 - cu[x]) * (1 - cv);
+            const double weight[4] = {(1 - fu[x]) * (1 - fv), fu[x] * (1 - fv), (1 - fu[x]) * fv, fu[x] * fv};
+            unsigned char* px = out_rgba8 + ((size_t)y * width + x) * 4;
+            for (int c = 0; c < 3; c++) {
+                double base = 0;
+                for (int q = 0; q < 4; q++) base += weight[q] * sky->quadrant[side][q][c];
+                const double value = base + (sky->line[side][c] - base) * g;
+                px[c] = (unsigned char)std::lround(std::min(std::max(value, 0.0), 1.0) * 255.0);
+            }
+            px[3] = 255;
+        }
+    }
+    return GR_OK;
 }
 
 // the pixels gr_trace_fused_launch's in-tile shading leaves: last column and last row of every 8x8 tile of this device's blocks

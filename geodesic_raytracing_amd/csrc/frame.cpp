@@ -22,6 +22,7 @@ using frame_plan::picture_motion;
 namespace switches = frame_plan::switches;
 
 extern "C" int gr_internal_fail(int code, const char* msg);   // capi.cpp
+extern "C" int gr_internal_check_analytic_sky(const char* who, const gr_analytic_sky* sky);   // capi.cpp: what every taker of a sky refuses
 
 #define HIP_CHECK(expr)                                                                                  \
     do {                                                                                                 \
@@ -91,6 +92,10 @@ struct gr_render_state {
     // through gr_resolve_filtered into filtered_frame (float4[out_width * out_height], allocated with the first frame that is not refused)
     int filter = GR_FILTER_BOX;
     void* filtered_frame = nullptr;
+    // gr_render_state_set_sky: with a sky every frame of the state is shaded by gr_render_analytic and reads no background; without
+    // one (the default) by gr_render / gr_render_strips, launch for launch as before.  Shading only: the records do not depend on it.
+    bool sky_set = false;
+    gr_analytic_sky sky{};
     hipEvent_t ev_resolve[2] = {};   // time_kernels = 1: around the resolve launch (gr_render_state_resolve_ms)
     bool resolve_timed = false;
     upload_ring uploads;
@@ -475,6 +480,18 @@ int gr_device_download_async(void* stream, void* host_dst, const void* device_sr
     return GR_OK;
 }
 
+// The states that exist (create_render_state adds one, gr_render_state_destroy takes it off).  Why a list: gr_render_frame and
+// gr_render_subframe promise to refuse a NULL background with an error code BEFORE they look inside any object they were handed - a
+// caller's mistake must not become a crash, and tests/test_shutter_abi.py holds them to it with pointers that are no states at all.
+// Whether a NULL background is a mistake now depends on the state (one with a sky reads none), so that one question is asked only of a
+// pointer found here.  It is asked only when a background is missing: a frame that brings its textures never takes the lock.
+static std::mutex live_states_lock;
+static std::vector<const gr_render_state*> live_states;
+static bool state_has_sky(const gr_render_state* s) {
+    std::lock_guard<std::mutex> guard(live_states_lock);
+    return std::find(live_states.begin(), live_states.end(), s) != live_states.end() && s->sky_set;
+}
+
 // a state whose frames are out_width x out_height and are traced at factor x that per axis (1: gr_render_state_create)
 static int create_render_state(int device, int out_width, int out_height, int factor, gr_render_state** out) {
     if (!out || out_width <= 0 || out_height <= 0) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "bad render state size");
@@ -556,6 +573,10 @@ static int create_render_state(int device, int out_width, int out_height, int fa
         gr_render_state_destroy(s);
         return gr_internal_fail(GR_ERROR_DEVICE, (std::string("render state allocation: ") + hipGetErrorString(e)).c_str());
     }
+    {
+        std::lock_guard<std::mutex> guard(live_states_lock);
+        live_states.push_back(s);
+    }
     *out = s;
     return GR_OK;
 }
@@ -586,6 +607,23 @@ int gr_render_state_set_filter(gr_render_state* s, int filter) {
 int gr_render_state_filter(const gr_render_state* s, int* filter) {
     if (!s || !filter) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_filter: null argument");
     *filter = s->filter;
+    return GR_OK;
+}
+
+int gr_render_state_set_sky(gr_render_state* s, const gr_analytic_sky* sky) {
+    if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_sky: null render state");
+    if (sky) {
+        GR_CHECK(gr_internal_check_analytic_sky("gr_render_state_set_sky", sky));
+        s->sky = *sky;
+    }
+    s->sky_set = sky != nullptr;
+    return GR_OK;
+}
+
+int gr_render_state_sky(const gr_render_state* s, gr_analytic_sky* out, int* is_set) {
+    if (!s || !out || !is_set) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_sky: null argument");
+    *is_set = s->sky_set ? 1 : 0;
+    if (s->sky_set) *out = s->sky;
     return GR_OK;
 }
 
@@ -625,6 +663,10 @@ void gr_render_state_destroy(gr_render_state* s) {
     for (int i = 0; i < GR_STAGE_COUNT; i++) {
         if (s->ev_start[i]) (void)hipEventDestroy(s->ev_start[i]);
         if (s->ev_stop[i]) (void)hipEventDestroy(s->ev_stop[i]);
+    }
+    {
+        std::lock_guard<std::mutex> guard(live_states_lock);
+        live_states.erase(std::remove(live_states.begin(), live_states.end(), s), live_states.end());
     }
     delete s;
 }
@@ -863,7 +905,7 @@ static int check_frame_arguments(const gr_render_state* s, const gr_program* p, 
     if (!s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
     // a frame that is to be shaded needs both skies and their shape (the texture pass reads them unchecked: a NULL sky is a device fault,
     // not an error code - tests/test_gpu_lifecycle.py found it); out == NULL stops after the render-data
-    if (out && (!bg1 || !bg2 || bg_width <= 0 || bg_height <= 0 || bg_levels <= 0))
+    if (out && (!bg1 || !bg2 || bg_width <= 0 || bg_height <= 0 || bg_levels <= 0) && !state_has_sky(s))   // (a state with a sky reads no background)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame: an output frame needs both background textures and their width, height and levels");
     if (num_cfg_values < 0 || (num_cfg_values > 0 && !cfg_values)) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame: cfg_values");
     return GR_OK;
@@ -1155,6 +1197,8 @@ static int fused_plan_frame(frame_context& f) {
     f.plan = frame_plan::plan_fused(in);
     if (f.plan.refused.code != GR_OK) return gr_internal_fail(f.plan.refused.code, f.plan.refused.message);
     if (f.plan.invalidate_tile_cost) s->tile_cost_valid = false;
+    // a frame with an analytic sky is shaded by fused_shade's one launch: the trace has no textures to shade tiles from
+    if (s->sky_set) f.plan.shade_in_trace = false;
     return GR_OK;
 }
 
@@ -1427,7 +1471,10 @@ static int fused_shade(frame_context& f) {
     const int compact_out = q.strip_count > 1 ? f.opt.compact_out : 0;
     if (!f.out) return GR_OK;
     GR_CHECK(f.begin(GR_STAGE_RENDER));
-    if (q.shade_in_trace)
+    if (s->sky_set)
+        GR_CHECK(gr_render_analytic_strips(f.p, f.stream, s->render_data, f.out, &s->sky, f.width, f.height, q.strip_count > 1 ? q.block_rows : f.height,
+                                           q.strip_rank, q.strip_count, compact_out, s->cfg, s->dfg));
+    else if (q.shade_in_trace)
         GR_CHECK(gr_render_seams(f.p, f.stream, s->render_data, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height, f.bg_levels, f.width, f.height, q.block_rows,
                                  q.strip_rank, q.strip_count, compact_out, f.opt.max_probes, s->cfg, s->dfg));
     else
@@ -1546,8 +1593,11 @@ static int render_reference_shaped(frame_context& f) {
 
     if (f.out) {
         GR_CHECK(f.begin(GR_STAGE_RENDER));
-        GR_CHECK(gr_render(p, stream, s->render_data, s->render_data_count, width * height, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height,
-                           f.bg_levels, width, height, f.opt.max_probes, s->cfg, s->dfg));
+        if (s->sky_set)
+            GR_CHECK(gr_render_analytic(p, stream, s->render_data, s->render_data_count, width * height, f.out, &s->sky, width, height, s->cfg, s->dfg));
+        else
+            GR_CHECK(gr_render(p, stream, s->render_data, s->render_data_count, width * height, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height,
+                               f.bg_levels, width, height, f.opt.max_probes, s->cfg, s->dfg));
         GR_CHECK(f.end(GR_STAGE_RENDER));
     }
     return GR_OK;
@@ -1703,7 +1753,7 @@ int gr_render_frame_yuv420p10(gr_render_state* s, gr_program* p, const gr_metric
 int gr_render_subframe(gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera, const gr_features* features,
                        const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2, int bg_width, int bg_height, int bg_levels,
                        float weight, int first, const gr_frame_options* options) {
-    if (!s || !p || !m || !camera || !bg1 || !bg2) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: null argument");
+    if (!s || !p || !m || !camera || ((!bg1 || !bg2) && !state_has_sky(s))) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: null argument");
     if (!std::isfinite(weight)) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: a weight that is not finite");
     if (options && options->strip_count > 1)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_subframe: whole frames only (strip_count > 1); a share of a split frame is not accumulated");

@@ -246,5 +246,100 @@ extern "C" __global__ void gr_render(const render_data* __restrict__ rdata, cons
     out[out_index] = shade_pixel(self, beside, last_column, below, last_row, near_sky, far_sky, most_probes, dfg);
     (void)cfg;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The analytic sky (no reference counterpart; defined in include/geodesic_hip_internal.h, "Analytic sky"): a coloured celestial sphere
+// with a latitude / longitude grid, integrated in closed form over a box the size of the pixel's footprint - no texels, no mips.
+// gr_analytic_sky of the C ABI, field for field; it travels in the kernel's argument block, and every index into it below is a
+// constant (a colour of the side a ray ended on is a select between two scalars, never an indexed copy in scratch).
+struct analytic_sky {
+    int meridians, parallels;
+    float line_width;
+    float quadrant[2][4][3];
+    float line[2][3];
+};
+
+// The share of [x - h, x + h] that the lines of a pulse train cover: n cells to the unit, a line of width w (in cells) centred on
+// every cell boundary.  Only the fraction of t = x n matters, and it comes from the exact product: in double, which holds it whole
+// and which the build's contraction and reassociation cannot hurt (they fold the fp32 pair x n, fma(x, n, -(x n)) into one rounding
+// and its low part counted twice); one rounding to fp32, the same value the pair gives under IEEE rules.  The integer parts of the
+// two ends are differenced before they meet w: the error is a few ulps of a cell, not of n cells.
+__device__ __forceinline__ float line_coverage(float x, float h, int n, float w) {
+    const float cells = (float)n;
+    const double t_exact = (double)x * (double)n;
+    const float t = (float)(t_exact - __builtin_floor(t_exact));
+    const float a = h * cells, half_line = 0.5f * w;
+    const float s_upper = t + (a + half_line), s_lower = t - (a - half_line);
+    const float k_upper = __builtin_floorf(s_upper), k_lower = __builtin_floorf(s_lower);
+    const float covered = (k_upper - k_lower) * w + (__builtin_fminf(s_upper - k_upper, w) - __builtin_fminf(s_lower - k_lower, w));
+    return covered / (2.f * a);
+}
+
+// ... and the share that lies in the upper half of a unit: of every unit for u (the sphere closes), of the one unit for v
+__device__ __forceinline__ float upper_half_share(float x, float h, bool periodic) {
+    const float upper = x + h, lower = x - h;
+    const float k_upper = periodic ? __builtin_floorf(upper) : 0.f, k_lower = periodic ? __builtin_floorf(lower) : 0.f;
+    const float inside = 0.5f * (k_upper - k_lower) + (__builtin_fmaxf((upper - k_upper) - 0.5f, 0.f) - __builtin_fmaxf((lower - k_lower) - 0.5f, 0.f));
+    return inside / (2.f * h);
+}
+
+// One pixel: `self`, `beside` and `below` as shade_pixel takes them.  Only the sizes of the differences enter, so a previous
+// neighbour (last column / row) needs no sign.
+__device__ __forceinline__ float4 shade_pixel_analytic(const render_data& self, float2 beside, float2 below, const analytic_sky& sky, dfg_t dfg) {
+    if (self.terminated != 1) return f4(0, 0, 0, 1);
+    const float floor_h = 6.103515625e-05f;   // 2^-14: keeps the result a continuous function of the record
+    const float hu = __builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(self.tex_coord.x, beside.x)) + __builtin_fabsf(wrapped_difference(self.tex_coord.x, below.x))), floor_h);
+    const float hv = __builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(self.tex_coord.y, beside.y)) + __builtin_fabsf(wrapped_difference(self.tex_coord.y, below.y))), floor_h);
+    const float u = self.tex_coord.x, v = self.tex_coord.y;
+    const float cu = line_coverage(u, hu, sky.meridians, sky.line_width), cv = line_coverage(v, hv, sky.parallels, sky.line_width);
+    const float grid = 1.f - (1.f - cu) * (1.f - cv);
+    const float fu = upper_half_share(u, hu, true), fv = upper_half_share(v, hv, false);
+    const float w0 = (1.f - fu) * (1.f - fv), w1 = fu * (1.f - fv), w2 = (1.f - fu) * fv, w3 = fu * fv;
+    const bool near_side = self.side >= 1;   // which side of a wormhole the ray ended on, as shade_pixel picks bg1 / bg2
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float q0 = near_side ? sky.quadrant[1][0][k] : sky.quadrant[0][0][k], q1 = near_side ? sky.quadrant[1][1][k] : sky.quadrant[0][1][k];
+        const float q2 = near_side ? sky.quadrant[1][2][k] : sky.quadrant[0][2][k], q3 = near_side ? sky.quadrant[1][3][k] : sky.quadrant[0][3][k];
+        const float line = near_side ? sky.line[1][k] : sky.line[0][k];
+        const float base = w0 * q0 + w1 * q1 + w2 * q2 + w3 * q3;
+        c[k] = base + (line - base) * grid;
+    }
+    float3 rgb = f3(c[0], c[1], c[2]);
+    if (GET_FEATURE(redshift, dfg)) {
+        rgb = apply_redshift(srgb_to_linear(rgb), self.z_shift, dfg);
+#ifndef LINEAR_FRAMEBUFFER
+        rgb = linear_to_srgb(rgb);
+#endif
+    } else {
+#ifdef LINEAR_FRAMEBUFFER
+        rgb = srgb_to_linear(rgb);
+#endif
+    }
+    return f4(rgb.x, rgb.y, rgb.z, 1.f);
+}
+
+// gr_render's launch, argument for argument, with the sky's description in place of its textures (and no seams_only: a frame with
+// an analytic sky is never shaded inside the trace)
+extern "C" __global__ void gr_render_analytic(const render_data* __restrict__ rdata, const int* __restrict__ rdata_count, float4* __restrict__ out,
+                                              analytic_sky sky, int width, int height, cfg_t cfg, dfg_t dfg,
+                                              int num_pixels, int block_pixels, int strip_rank, int strip_count, int compact_out) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= num_pixels) return;
+    const int lb = gid / block_pixels, off = gid - lb * block_pixels;
+    const int id = (lb * strip_count + strip_rank) * block_pixels + off;
+    if (id >= *rdata_count || id >= width * height) return;
+    const render_data self = rdata[id];
+    const int px = self.sx, py = self.sy;
+    const int out_index = compact_out ? lb * block_pixels + off : py * width + px;
+    const bool last_column = px == width - 1, last_row = py == height - 1;
+    float2 beside = make_float2(0, 0), below = make_float2(0, 0);
+    if (self.terminated == 1) {
+        beside = rdata[py * width + px + (last_column ? (width > 1 ? -1 : 0) : 1)].tex_coord;
+        below = rdata[(py + (last_row ? (height > 1 ? -1 : 0) : 1)) * width + px].tex_coord;
+    }
+    out[out_index] = shade_pixel_analytic(self, beside, below, sky, dfg);
+    (void)cfg;
+}
 #endif  // GR_FRAME_KERNELS
 

@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from . import (Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, FRAME_YUV420, FRAME_YUV420P10, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
+from . import (AnalyticSkyStruct, Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, FRAME_YUV420, FRAME_YUV420P10, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
                c_size_t, c_void_p, check, lib)
 
 LIGHTRAY_DTYPE = np.dtype([("position", "<f4", 4), ("velocity", "<f4", 4), ("initial_quat", "<f4", 4),
@@ -544,15 +544,64 @@ class JpegEncoder:
         self.close()
 
 
+class AnalyticSky:
+    """gr_analytic_sky: a coloured celestial sphere with a latitude / longitude grid, shaded on the device in closed form from the pixel's
+    footprint (include/geodesic_hip_internal.h, "Analytic sky").  The library's defaults, then the overrides: meridians (2 ... 360),
+    parallels (1 ... 180), line_width (0 ... 0.5 of a cell), quadrant [2][4][3] and line [2][3] (stored sRGB values in [0, 1];
+    [side][q][rgb], q = (u >= 0.5) + 2 (v >= 0.5), side 0 the far sky, side 1 the near one).  Hand it to RenderState(sky=...) or
+    RenderState.set_sky; the library refuses a field out of range there."""
+
+    def __init__(self, meridians=None, parallels=None, line_width=None, quadrant=None, line=None):
+        self.struct = AnalyticSkyStruct()
+        check(lib.gr_analytic_sky_default(ctypes.byref(self.struct)))
+        if meridians is not None:
+            self.struct.meridians = int(meridians)
+        if parallels is not None:
+            self.struct.parallels = int(parallels)
+        if line_width is not None:
+            self.struct.line_width = float(line_width)
+        if quadrant is not None:
+            self.quadrant = quadrant
+        if line is not None:
+            self.line = line
+
+    meridians = property(lambda self: self.struct.meridians)
+    parallels = property(lambda self: self.struct.parallels)
+    line_width = property(lambda self: self.struct.line_width)
+
+    @property
+    def quadrant(self):
+        return np.ctypeslib.as_array(self.struct.quadrant).copy()
+
+    @quadrant.setter
+    def quadrant(self, value):
+        np.ctypeslib.as_array(self.struct.quadrant)[...] = np.asarray(value, dtype=np.float32).reshape(2, 4, 3)
+
+    @property
+    def line(self):
+        return np.ctypeslib.as_array(self.struct.line).copy()
+
+    @line.setter
+    def line(self, value):
+        np.ctypeslib.as_array(self.struct.line)[...] = np.asarray(value, dtype=np.float32).reshape(2, 3)
+
+    def image(self, width, height, side=1):
+        """the same sky as an image, uint8 [height][width][4] (gr_analytic_sky_image: the definition in double at one texel's footprint)"""
+        out = np.empty((int(height), int(width), 4), dtype=np.uint8)
+        check(lib.gr_analytic_sky_image(ctypes.byref(self.struct), int(side), int(width), int(height), out.ctypes.data_as(c_void_p)))
+        return out
+
+
 class RenderState:
     """Per-frame device buffers + the frame sequence (render_state.hpp:97-197, main.cpp:2244-2526)."""
 
-    def __init__(self, width, height, device=0, supersample=1, filter=FILTER_BOX):
+    def __init__(self, width, height, device=0, supersample=1, filter=FILTER_BOX, sky=None):
         """supersample = f > 1 (gr_render_state_create_supersampled; 2, 3 or 4): frames are still width x height, traced at f x that per
         axis and box-averaged on the device (box_resolve says what that means).  Everything else about the state - buffer(), the
         prepass grid, tile history - is of traced_size.  filter (gr_render_state_set_filter): FILTER_BOX, or FILTER_TENT / _GAUSSIAN /
         _MITCHELL or their names - every frame of the state is then filter_frame of the traced frame with filter_taps' table, at
-        factor 1 too, whole frames only."""
+        factor 1 too, whole frames only.  sky (gr_render_state_set_sky): an AnalyticSky - every frame of the state is then shaded from
+        it by gr_render_analytic, and render() needs no background."""
         self.width, self.height, self.device = width, height, device
         self.handle = c_void_p()
         if supersample == 1:
@@ -564,6 +613,19 @@ class RenderState:
         self.supersample, self.traced_size = f.value, (tw.value, th.value)
         if filter != FILTER_BOX:
             self.set_filter(filter)
+        if sky is not None:
+            self.set_sky(sky)
+
+    def set_sky(self, sky):
+        """the analytic sky of the frames from here on (an AnalyticSky), or None: back to the background textures"""
+        check(lib.gr_render_state_set_sky(self.handle, ctypes.byref(sky.struct) if sky is not None else None))
+
+    @property
+    def sky(self):
+        """the state's AnalyticSky, or None"""
+        out, is_set = AnalyticSky(), c_int()
+        check(lib.gr_render_state_sky(self.handle, ctypes.byref(out.struct), ctypes.byref(is_set)))
+        return out if is_set.value else None
 
     def set_filter(self, filter):
         """the reconstruction filter of the frames from here on: a FILTER_* value or a name (box, tent, gaussian, mitchell)"""

@@ -162,8 +162,9 @@ def checked_png_stream(who, png, png_stream):
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
            parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box",
-           png="host", jpeg=None, quality=90, png_stream="literals"):
-    """Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
+           png="host", jpeg=None, quality=90, png_stream="literals", sky=None):
+    """sky: a gra.AnalyticSky - every frame is shaded from it in closed form (RenderState(sky=)); `background` and `mips` are then unused.
+    Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
     rgba8: the frames are uint8 [H, W, 4] in sRGB instead, encoded on the device (RenderState.render_rgba8) and fetched at 4 bytes a
@@ -220,13 +221,14 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     cfg_values = metric.cfg_values(**(cfg or {}))
     manager = ProgramManager(metric, device, feats, cfg_values)
     program = manager.current(wait=wait_for_static)
-    state = gra.RenderState(width, height, device, supersample=supersample, filter=filter)
-    rgba = background if background is not None else gra.synthetic_background(2048, 1024)
-    if mips == "device":
-        dbg, levels = gra.build_background(program, rgba, device)
-    else:
-        packed, levels = gra.pack_background(rgba)
-        dbg = DeviceBuffer.from_numpy(device, packed)
+    state = gra.RenderState(width, height, device, supersample=supersample, filter=filter, sky=sky)
+    if sky is None:
+        rgba = background if background is not None else gra.synthetic_background(2048, 1024)
+        if mips == "device":
+            dbg, levels = gra.build_background(program, rgba, device)
+        else:
+            packed, levels = gra.pack_background(rgba)
+            dbg = DeviceBuffer.from_numpy(device, packed)
     out_bytes = fmt.bytes(width, height)
     out = DeviceBuffer(device, out_bytes)
     encoder = (gra.PngEncoder(program, width, height, png_stream) if png == "device" else
@@ -234,7 +236,7 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     pinned = PinnedBuffer(out_bytes) if frame_format != gra.FRAME_F32 and encoder is None else None   # (a float frame is downloaded as it always was)
     cam = gra.default_camera(camera_pos, camera_quat)
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
-    bg = (dbg.ptr, rgba.shape[1], rgba.shape[0], levels)
+    bg = (dbg.ptr, rgba.shape[1], rgba.shape[0], levels) if sky is None else None   # (an analytic sky: no image, no mips, no upload)
 
     def fetch():
         if encoder is not None:
@@ -302,8 +304,9 @@ def split_block_rows(height, block_rows=16):
 
 def render_split(metric_name, width, height, devices, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, background=None,
                  fov=90.0, universe=20.0, wait_for_static=True, supersample=1, rgba8=False, mips="host", frames=1, block_rows=16, png="host", jpeg=None,
-                 quality=90, png_stream="literals"):
-    """render() of a Cartesian camera with the rows of every frame dealt to `devices` (TiledFrame.local: one process, peer copies, participant
+                 quality=90, png_stream="literals", sky=None):
+    """sky: as in render().
+    render() of a Cartesian camera with the rows of every frame dealt to `devices` (TiledFrame.local: one process, peer copies, participant
     r on devices[r]; a device may be named more than once, which is how a box with one GPU rehearses it).  Every device has its own program,
     sky (with mips="device" built there, once per device) and render state, traces its share at `supersample` x per axis, resolves it
     there and ships width x rows pixels to devices[0] - float4, or with rgba8 4 bytes each (TiledFrame.render_as).  Frame k is rendered
@@ -325,13 +328,16 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
     metric = gra.Metric(metric_name, scripts or os.path.join(HERE, "scripts"))
     feats = metric.features(adaptive_sampling=0, redshift=int(redshift), field_of_view=fov, universe_size=universe)
     cfg_values = metric.cfg_values(**(cfg or {}))
-    rgba = background if background is not None else gra.synthetic_background(2048, 1024)
+    rgba = (background if background is not None else gra.synthetic_background(2048, 1024)) if sky is None else None
     managers, programs, skies = {}, {}, {}
     for d in devices:   # once per device, however many participants it carries
         if d in programs:
             continue
         managers[d] = ProgramManager(metric, d, feats, cfg_values)
         programs[d] = managers[d].current(wait=wait_for_static)
+        if sky is not None:   # an analytic sky: every participant's state shades from it, no device holds an image
+            skies[d] = (None, None)
+            continue
         if mips == "device":
             dbg, levels = gra.build_background(programs[d], rgba, d)
         else:
@@ -340,7 +346,7 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
         skies[d] = (dbg, (dbg.ptr, rgba.shape[1], rgba.shape[0], levels))
     parts = gra.TiledFrame.local(devices, width, height, split_block_rows(height, block_rows))
     try:
-        states = [gra.RenderState(width, height, d, supersample=supersample) for d in devices]
+        states = [gra.RenderState(width, height, d, supersample=supersample, sky=sky) for d in devices]
         out = DeviceBuffer(devices[0], width * height * (4 if rgba8 else 16))
         cam = gra.default_camera(camera_pos, camera_quat)
         encoder = (gra.PngEncoder(programs[devices[0]], width, height, png_stream) if png == "device" else
@@ -362,6 +368,24 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
     finally:
         for part in parts:
             part.close()
+
+
+def parse_sky(text):
+    """--sky grid[:MxP[:WIDTH]] -> gra.AnalyticSky (the library refuses what is out of range)"""
+    parts = text.split(":")
+    if parts[0] != "grid" or len(parts) > 3:
+        raise ValueError("grid[:MxP[:WIDTH]], e.g. grid:36x18:0.08")
+    fields = {}
+    if len(parts) > 1:
+        cells = parts[1].split("x")
+        if len(cells) != 2:
+            raise ValueError("MxP: meridians a turn and cells between the poles, e.g. 36x18")
+        fields["meridians"], fields["parallels"] = int(cells[0]), int(cells[1])
+    if len(parts) > 2:
+        fields["line_width"] = float(parts[2])
+    sky = gra.AnalyticSky(**fields)
+    sky.image(1, 1)   # the library's own check of the fields, with its message
+    return sky
 
 
 def main(argv=None):
@@ -402,8 +426,11 @@ def main(argv=None):
                     "come back and one host thread encodes them; device = colour conversion, DCT, quantiser and Huffman coding run on the GPU and only "
                     "the file's bytes come back (the same bytes).  device implies --encode device; not with --out NAME.png or NAME.y4m")
     ap.add_argument("--quality", type=int, default=None, help="of a .jpg or .avi: 1 ... 100, the usual scaling of the standard quantisation tables (90)")
-    ap.add_argument("--mips", choices=["host", "device"], default="host", help="where the sky's mip slices are made: host = pack them on the CPU "
-                    "and upload all of them; device = upload the image and build the slices on the GPU (the same bytes)")
+    ap.add_argument("--sky", default=None, help="grid[:MxP[:WIDTH]]: the analytic sky - a coloured celestial sphere with M meridians a turn and P cells "
+                    "between the poles (36x18), lines of WIDTH of a cell (0.08), antialiased exactly on the device at any magnification; no "
+                    "image, no mips, no upload.  Not with --background or --mips")
+    ap.add_argument("--mips", choices=["host", "device"], default=None, help="where the sky's mip slices are made: host = pack them on the CPU "
+                    "and upload all of them (default: host); device = upload the image and build the slices on the GPU (the same bytes)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--filter", choices=sorted(gra.FILTER_NAMES, key=gra.FILTER_NAMES.get), default="box", help="the reconstruction filter of "
                     "--supersample's samples, applied on the device before any encode: box (the mean of the N x N samples behind a pixel), tent "
@@ -431,6 +458,15 @@ def main(argv=None):
         fps = parse_fps(a.fps)
     except ValueError as e:
         ap.error(f"--fps: {e}")
+    sky = None
+    if a.sky is not None:
+        if a.background is not None or a.mips is not None:
+            ap.error("--sky with --background / --mips: an analytic sky is no image and has no mip slices; give one or the other")
+        try:
+            sky = parse_sky(a.sky)
+        except (ValueError, gra.GeodesicError) as e:
+            ap.error(f"--sky {a.sky}: {e}")
+    a.mips = a.mips or "host"
     if a.bit_depth != 8 and not video:
         ap.error("--bit-depth 10 is a depth of video frames: it needs --out NAME.y4m (a PNG is 8-bit sRGB, and so is a JPEG or a Motion-JPEG file)")
     if a.png_stream is not None and a.png != "device":
@@ -494,7 +530,7 @@ def main(argv=None):
         result = render_split(a.metric, w, h, devices, a.scripts, cfg, [float(v) for v in a.camera.split(",")] if a.camera else None,
                               [float(v) for v in a.quat.split(",")] if a.quat else None, a.redshift, read_png(a.background) if a.background else None,
                               a.fov, a.universe, supersample=a.supersample, rgba8=a.encode == "device", mips=a.mips, frames=a.frames, png=a.png,
-                              jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream)
+                              jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream, sky=sky)
         if avi:
             with AviWriter(a.out, w, h, fps) as stream:
                 for frame in result:
@@ -520,7 +556,7 @@ def main(argv=None):
                     geodesic_times=[a.geodesic_time + float(t) * a.geodesic_dt for t in moments] if samples else times,
                     parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
                     rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples,
-                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream)
+                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream, sky=sky)
     if speed is None and cameras is None:
         result = [result]
     if video:

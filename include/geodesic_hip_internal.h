@@ -302,6 +302,67 @@ int gr_resolve_filtered(gr_program* p, void* stream, const void* src, void* dst,
 int gr_render_state_set_filter(gr_render_state* s, int filter);
 int gr_render_state_filter(const gr_render_state* s, int* filter);
 
+/* ---- Analytic sky -----------------------------------------------------------------------------------------------------------------------
+ * A coloured celestial sphere with a latitude / longitude grid, shaded on the device from the pixel's footprint in closed form: a second
+ * shading kernel beside gr_render (kernels/shading.hip: gr_render_analytic) that reads the same records and writes the same float4 frame,
+ * with no sky image, no mip pyramid and no gathers.  The grid is antialiased exactly at any magnification.  (Declared here and not in
+ * geodesic_hip.h only because the contract header keeps to 80 names and 350 lines; all of this is public.)
+ *
+ * Definition.  A pixel has the record `self` with sky coordinates (u, v) = render_data.tex_coord and the records of its neighbours
+ * `beside` and `below`, chosen exactly as gr_render chooses them: the next pixel of the row / column, the previous one at the last column
+ * / row, the pixel itself in a frame one pixel wide / high.
+ *   1. footprint   du_x, dv_x are the wrapped differences (b - a brought into half a turn either way, as gr_render forms them, without its
+ *                  shrink by 1.3) from self to beside, du_y, dv_y those from self to below.  hu = max((|du_x| + |du_y|) / 2, 2^-14),
+ *                  hv = max((|dv_x| + |dv_y|) / 2, 2^-14).  The floor makes the result a continuous function of the record.
+ *   2. lines       a pulse train filtered by a box of the footprint's size.  For n cells and a width w: t = x n, a = h n, s(t) = t + w/2,
+ *                  k = floor(s), f = s - k, L(t) = k w + min(f, w); the coverage is c = (L(t + a) - L(t - a)) / (2 a).  c_u takes
+ *                  (u, hu, meridians), c_v takes (v, hv, parallels); the pattern continues periodically past the poles.
+ *                  g = 1 - (1 - c_u)(1 - c_v).  (An fp32 evaluation differences the integer parts k before it multiplies them by w, and
+ *                  takes the fraction of t from the EXACT product x n, rounded once - by any means that is exact: the pair x n and
+ *                  fma(x, n, -(x n)) under IEEE rules, or the product in double, which the device kernel uses because its build
+ *                  contracts and reassociates fp32 - so that the error is a few ulps of a cell and not of n cells.)
+ *   3. quadrants   the same box.  H(x) = floor(x) / 2 + max(x - floor(x) - 1/2, 0), f_u = (H(u + hu) - H(u - hu)) / (2 hu);
+ *                  G(y) = max(y - 1/2, 0), f_v = (G(v + hv) - G(v - hv)) / (2 hv).  base = the mix of the side's four quadrant colours
+ *                  with the weights (1 - f_u)(1 - f_v), f_u (1 - f_v), (1 - f_u) f_v, f_u f_v for q = 0, 1, 2, 3.
+ *   4. colour      rgb = base + (line - base) g, alpha 1; from there gr_render's colour tail unchanged: with the redshift feature the
+ *                  colour is linearised, shifted by self.z_shift and, unless the program has a linear framebuffer, brought back to sRGB;
+ *                  without it the colour is linearised only under a linear framebuffer.
+ *   5. black       a record with terminated != 1 gives exactly (0, 0, 0, 1). */
+struct gr_analytic_sky {
+    int meridians;              /* lines of constant u per turn, 2 ... 360 */
+    int parallels;              /* cells between the poles, 1 ... 180 */
+    float line_width;           /* full width of a line as a fraction of its cell, 0 (no lines) ... 0.5 */
+    float quadrant[2][4][3];    /* [side][q][rgb], stored values in [0, 1] as a sky image's texels are (sRGB); q = (u >= 0.5) + 2 (v >= 0.5);
+                                 * side 0 = the far sky (render_data.side < 1, gr_render's background2), side 1 = the near sky (side >= 1,
+                                 * background1) */
+    float line[2][3];           /* the lines' colour per side */
+};
+/* 36 x 18 cells (10 degrees), line_width 0.08, four distinct quadrant colours per side - another palette on side 1 - and near-black lines */
+int gr_analytic_sky_default(struct gr_analytic_sky* out);
+/* gr_render with the sky's description in place of the textures: one launch of gr_render_analytic over num_pixels records, out as there.
+ * Everything below that takes a sky refuses, before any device call, with GR_ERROR_INVALID_ARGUMENT and a message that names the function
+ * and the field: a NULL; meridians, parallels or line_width out of range or not finite; a colour outside [0, 1] or not finite; and the
+ * launchers what gr_render / gr_render_strips refuse (a NULL buffer, bad strip parameters). */
+int gr_render_analytic(gr_program* p, void* stream, const void* render_data, const void* render_data_count, int num_pixels, void* out_rgba_f32,
+                       const struct gr_analytic_sky* sky, int width, int height, const void* cfg, const void* dfg);
+/* ... restricted to a device's row blocks: gr_render_strips' arguments, rows and compact_out */
+int gr_render_analytic_strips(gr_program* p, void* stream, const void* render_data, void* out_rgba_f32, const struct gr_analytic_sky* sky,
+                              int width, int height, int block_rows, int strip_rank, int strip_count, int compact_out, const void* cfg,
+                              const void* dfg);
+/* The host rasteriser of the same definition, in double, at the footprint of one texel: texel (x, y) of a width x height image has
+ * u = (x + 0.5) / width, v = (y + 0.5) / height, hu = 0.5 / width, hv = 0.5 / height (differences along the axes; the 2^-14 floor applies),
+ * the colour of steps 2 to 4 up to rgb = base + (line - base) g as it is stored (sRGB, no redshift), each channel rounded to the nearest of
+ * 255 steps, alpha 255.  side: 0 or 1.  out_rgba8: width * height * 4 bytes.  The same sky can so be sent down the texture path. */
+int gr_analytic_sky_image(const struct gr_analytic_sky* sky, int side, int width, int height, unsigned char* out_rgba8);
+/* The sky of a state's frames.  NULL (the default): every entry point is as it was, launch for launch.  With a sky set, every frame of the
+ * state - gr_render_frame and its three encoded forms, gr_render_subframe, gr_render_frame_tiled(_as), both modes, split and supersampled
+ * frames - is shaded by gr_render_analytic in place of gr_render / gr_render_strips; tile shading inside the trace
+ * (gr_frame_tuning.fused_shading) is not taken for such a frame; background1, background2 and their sizes are ignored and may be NULL / 0.
+ * May be called between frames; the traced records do not depend on it, so nothing of the still-camera reuse is invalidated.
+ * gr_render_state_sky: *is_set = 1 and the sky in *out, or 0 and *out untouched. */
+int gr_render_state_set_sky(gr_render_state* s, const struct gr_analytic_sky* sky_or_null);
+int gr_render_state_sky(const gr_render_state* s, struct gr_analytic_sky* out, int* is_set);
+
 /* ---- PNG frames -----------------------------------------------------------------------------------------------------------------------
  * A PNG encoder behind an RGBA8 frame that is already in device memory (gr_render_frame_rgba8, gr_deliver_accumulated(GR_FRAME_RGBA8),
  * participant 0's frame of gr_render_frame_tiled_as): filtering, histogram and bit-packing run on the device (kernels/png.hip, set-up
