@@ -31,10 +31,9 @@
 #include "builtin_metrics.hpp"
 #include "codeobject.hpp"
 #include "frame_format.hpp"
-#include "jpeg_stream.hpp"
+#include "internal.hpp"
 #include "jsfront.hpp"
 #include "metric_codegen.hpp"
-#include "png_stream.hpp"
 #include "program_build.hpp"
 
 namespace {
@@ -56,13 +55,6 @@ int fail(gr_status code, const std::string& msg) {
     catch (const std::exception& e) { return fail(GR_ERROR_SCRIPT, e.what()); }    \
     catch (...) { return fail(GR_ERROR_SCRIPT, "unknown exception"); }
 
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return fail(GR_ERROR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));         \
-    } while (0)
-
 std::string library_dir() {
     Dl_info info;
     if (dladdr((void*)&gr_last_error, &info) && info.dli_fname) {
@@ -80,11 +72,6 @@ const char* const KERNEL_NAMES[] = {
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
     "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack",
     "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather", "gr_png_histogram_runs", "gr_png_pack_runs", "gr_render_analytic"};
-enum KernelId {
-    K_CART_TO_GENERIC, K_INIT_BASIS, K_CLEAR_TERM, K_INIT_RAYS, K_DO_RAYS, K_CALC_SING, K_CALC_RDATA,
-    K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
-    K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_JPEG_BLOCKS, K_JPEG_PACK, K_JPEG_GATHER, K_PNG_HISTOGRAM_RUNS, K_PNG_PACK_RUNS, K_RENDER_ANALYTIC, K_COUNT
-};
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
 // filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and 8- and 10-bit Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
@@ -985,7 +972,8 @@ int gr_program_kernel_info(const gr_program* p, const char* kernel_name, int* vg
 
 // ---- launch helpers ---------------------------------------------------------------------------
 
-static int launch(gr_program* p, int k, void* stream, unsigned gx, unsigned gy, unsigned bx, unsigned by, void** args) {
+extern "C++" {   // (internal.hpp: device_encoders.cpp launches through these too)
+int gr_internal::launch(gr_program* p, int k, void* stream, unsigned gx, unsigned gy, unsigned bx, unsigned by, void** args) {
     if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, "null program");
     if (gx == 0 || gy == 0) return GR_OK;
     hipFunction_t f = function_of(p, k);
@@ -993,8 +981,9 @@ static int launch(gr_program* p, int k, void* stream, unsigned gx, unsigned gy, 
     HIP_CHECK(hipModuleLaunchKernel(f, gx, gy, 1, bx, by, 1, 0, (hipStream_t)stream, args, nullptr));
     return GR_OK;
 }
-
-static unsigned blocks(long long n, int b) { return n <= 0 ? 0u : (unsigned)((n + b - 1) / b); }
+int gr_internal::device_of(const gr_program* p) { return p->device; }
+}
+using gr_internal::blocks, gr_internal::launch;
 
 // A launcher refuses a NULL where its kernel dereferences unconditionally: the reference's clSetKernelArg returns CL_INVALID_MEM_OBJECT
 // for a null buffer, a HIP launch takes it and the device faults (and a device fault ends the process).  cfg / dfg are not checked:
@@ -1307,7 +1296,6 @@ int gr_shutter_accumulate(gr_program* p, void* stream, const void* src, void* ac
 // a filtered frame (kernels/filter.hip; geodesic_hip_internal.h, "Filtered frames"): one workgroup of 256 lanes per tile of 32 x 8 output
 // pixels (the kernel's GR_FILTER_TX x GR_FILTER_TY), the taps - host memory - copied into the argument block.  gr_filter_frame's refusals
 // (imageio.cpp) and the grid's, all before the first device call.
-extern "C" const char* gr_internal_filter_table_error(int factor, const float* taps, int count);
 int gr_resolve_filtered(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, const float* taps, int count) {
     const std::string who = "gr_resolve_filtered: ";
     if (!src || !dst || !taps) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required buffer is NULL");
@@ -1388,347 +1376,6 @@ int gr_build_mipped_background(gr_program* p, void* stream, const void* rgba8, i
     void* args[] = {&rgba8, &scratch, &packed_out, &width, &height, &levels_arg, &in_place_arg};
     rc = launch(p, K_BACKGROUND_SLICES, stream, blocks(((long long)width * height * levels + 3) / 4, 256), 1, 256, 1, args);
     return rc != GR_OK ? rc : levels;
-}
-
-// ---- PNG frames: the device encoder (kernels/png.hip; the stream and its host encoder: png_stream.cpp) ---------------------------
-
-struct gr_png_encoder {
-    gr_program* program = nullptr;
-    int width = 0, height = 0;
-    // the stream kind, and with it the bins of a histogram as the kernels store it (256, runs: 285) and the table's symbols (257, 285)
-    int stream_kind = GR_PNG_STREAM_LITERALS, bins = 256, symbols = png_stream::SYMBOLS;
-    // device: [frame histogram bins | rows' histograms height x bins | rows' sums height x 2] words, downloaded in one copy ...
-    unsigned int* statistics = nullptr;
-    size_t statistics_words = 0;
-    // ... [rows' offsets height + 1, 64 bit | table symbols | header png_stream::HEADER_WORDS] uploaded in one copy ...
-    unsigned char* placement = nullptr;
-    unsigned char* placement_host = nullptr;   // (pinned)
-    size_t placement_bytes = 0;
-    // ... and the stream: GUARD_WORDS, then stream_capacity_words, then GUARD_WORDS, all filled with GUARD_PATTERN at creation; an encode
-    // zeroes the words its stream takes and nothing else
-    static const size_t GUARD_WORDS = 64;
-    static const unsigned int GUARD_PATTERN = 0xa5c3e1f7u;
-    unsigned int* scratch = nullptr;
-    size_t stream_capacity_words = 0, most_stream_words = 0;   // (the longest stream of any encode so far)
-    unsigned char* staging = nullptr;   // pinned: the statistics, then the stream
-    size_t staging_bytes = 0;
-    bool time_launches = false, timed = false;
-    hipEvent_t events[4] = {};
-    ~gr_png_encoder() {
-        if (program) (void)hipSetDevice(program->device);
-        if (statistics) (void)hipFree(statistics);
-        if (placement) (void)hipFree(placement);
-        if (scratch) (void)hipFree(scratch);
-        if (placement_host) (void)hipHostFree(placement_host);
-        if (staging) (void)hipHostFree(staging);
-        for (hipEvent_t e : events)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
-namespace {
-int png_encoder_create(const std::string& who, gr_program* p, int width, int height, int stream_kind, gr_png_encoder** out) {
-    if (!p || !out) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
-    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
-    const uint64_t rows_bound = png_stream::rows_bound(width, height);
-    if (!rows_bound) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a frame of more than 2^31 - 1 raw bytes");
-    if (!png_stream::known_kind(stream_kind)) return fail(GR_ERROR_INVALID_ARGUMENT, who + "an unknown stream kind " + std::to_string(stream_kind));
-    HIP_CHECK(hipSetDevice(p->device));
-    auto e = std::make_unique<gr_png_encoder>();
-    e->program = p;
-    e->width = width;
-    e->height = height;
-    e->stream_kind = stream_kind;
-    e->bins = png_stream::row_bins_of(stream_kind);
-    e->symbols = png_stream::symbols_of(stream_kind);
-    e->statistics_words = (size_t)e->bins + (size_t)height * ((size_t)e->bins + 2);
-    e->placement_bytes = ((size_t)height + 1) * 8 + ((size_t)e->symbols + png_stream::HEADER_WORDS) * 4;
-    e->stream_capacity_words = (size_t)((rows_bound + 3) / 4);
-    e->staging_bytes = std::max(e->statistics_words * 4, e->stream_capacity_words * 4);
-    const size_t scratch_words = e->stream_capacity_words + 2 * gr_png_encoder::GUARD_WORDS;
-    HIP_CHECK(hipMalloc((void**)&e->statistics, e->statistics_words * 4));
-    HIP_CHECK(hipMalloc((void**)&e->placement, e->placement_bytes));
-    HIP_CHECK(hipMalloc((void**)&e->scratch, scratch_words * 4));
-    HIP_CHECK(hipHostMalloc((void**)&e->placement_host, e->placement_bytes, hipHostMallocDefault));
-    HIP_CHECK(hipHostMalloc((void**)&e->staging, e->staging_bytes, hipHostMallocDefault));
-    HIP_CHECK(hipMemsetD32((hipDeviceptr_t)e->scratch, (int)gr_png_encoder::GUARD_PATTERN, scratch_words));
-    HIP_CHECK(hipDeviceSynchronize());
-    *out = e.release();
-    return GR_OK;
-}
-}   // namespace
-
-int gr_png_encoder_create(gr_program* p, int width, int height, gr_png_encoder** out) {
-    return png_encoder_create("gr_png_encoder_create: ", p, width, height, GR_PNG_STREAM_LITERALS, out);
-}
-
-int gr_png_encoder_create_as(gr_program* p, int width, int height, int stream_kind, gr_png_encoder** out) {
-    return png_encoder_create("gr_png_encoder_create_as: ", p, width, height, stream_kind, out);
-}
-
-void gr_png_encoder_destroy(gr_png_encoder* e) { delete e; }
-
-int gr_png_encoder_time_launches(gr_png_encoder* e, int on) {
-    if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_png_encoder_time_launches: a required pointer is NULL");
-    HIP_CHECK(hipSetDevice(e->program->device));
-    if (on)
-        for (hipEvent_t& event : e->events)
-            if (!event) HIP_CHECK(hipEventCreate(&event));
-    e->time_launches = on != 0;
-    e->timed = false;
-    return GR_OK;
-}
-
-int gr_png_encoder_launch_ms(gr_png_encoder* e, float ms[2]) {
-    if (!e || !ms) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_png_encoder_launch_ms: a required pointer is NULL");
-    if (!e->timed) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_png_encoder_launch_ms: no encode was timed (gr_png_encoder_time_launches)");
-    HIP_CHECK(hipEventElapsedTime(&ms[0], e->events[0], e->events[1]));
-    HIP_CHECK(hipEventElapsedTime(&ms[1], e->events[2], e->events[3]));
-    return GR_OK;
-}
-
-int gr_png_encoder_scratch_intact(gr_png_encoder* e, int* intact) {
-    if (!e || !intact) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_png_encoder_scratch_intact: a required pointer is NULL");
-    HIP_CHECK(hipSetDevice(e->program->device));
-    const size_t G = gr_png_encoder::GUARD_WORDS, words = e->stream_capacity_words + 2 * G;
-    std::vector<unsigned int> host(words);
-    HIP_CHECK(hipMemcpy(host.data(), e->scratch, words * 4, hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (size_t i = 0; i < words; i++)
-        if ((i < G || i >= G + e->most_stream_words) && host[i] != gr_png_encoder::GUARD_PATTERN) *intact = 0;
-    return GR_OK;
-}
-
-int gr_png_encode_rgba8(gr_png_encoder* e, void* stream, const void* device_rgba8, unsigned char* out_file, size_t capacity, size_t* out_bytes) {
-    const std::string who = "gr_png_encode_rgba8: ";
-    if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
-    bool too_small = false;
-    const std::string wrong = png_stream::refusal(device_rgba8, e->width, e->height, out_file, capacity, out_bytes, &too_small);
-    if (!wrong.empty()) return fail(too_small ? GR_ERROR_BUFFER_TOO_SMALL : GR_ERROR_INVALID_ARGUMENT, who + wrong);
-    gr_program* p = e->program;
-    const int width = e->width, height = e->height;
-    const bool runs = e->stream_kind == GR_PNG_STREAM_RUNS;
-    const size_t bins = (size_t)e->bins;
-    hipStream_t on = (hipStream_t)stream;
-    HIP_CHECK(hipSetDevice(p->device));
-    // the first round trip: the frame's and the rows' histograms, the rows' Adler sums
-    unsigned int* frame_histogram = e->statistics;
-    unsigned int* row_histogram = e->statistics + bins;
-    unsigned int* row_sums = row_histogram + (size_t)height * bins;
-    HIP_CHECK(hipMemsetAsync(frame_histogram, 0, bins * 4, on));
-    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[0], on));
-    {
-        int w = width, h = height;
-        void* args[] = {&device_rgba8, &w, &h, &frame_histogram, &row_histogram, &row_sums};
-        int rc = launch(p, runs ? K_PNG_HISTOGRAM_RUNS : K_PNG_HISTOGRAM, stream, (unsigned)height, 1, 64, 4, args);
-        if (rc != GR_OK) return rc;
-    }
-    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[1], on));
-    HIP_CHECK(hipMemcpyAsync(e->staging, e->statistics, e->statistics_words * 4, hipMemcpyDeviceToHost, on));
-    HIP_CHECK(hipStreamSynchronize(on));
-    // the table from the frame's histogram - with what the device does not count: a filter-type byte and an end-of-block a row -, the rows'
-    // offsets from their own histograms, the Adler-32 from their sums
-    const unsigned int* got = (const unsigned int*)e->staging;
-    uint64_t histogram[png_stream::MAX_SYMBOLS] = {};
-    for (size_t v = 0; v < bins; v++) histogram[v] = got[v];
-    histogram[1] += 1;
-    histogram[2] += (uint64_t)height - 1;
-    histogram[png_stream::END_OF_BLOCK] = (uint64_t)height;
-    png_stream::table t;
-    png_stream::build_table(histogram, e->stream_kind, t);
-    uint64_t* offset = (uint64_t*)e->placement_host;
-    unsigned int* table_words = (unsigned int*)(e->placement_host + ((size_t)height + 1) * 8);
-    unsigned int* header_words = table_words + e->symbols;
-    std::vector<uint32_t> adlers(height);
-    offset[0] = 0;
-    for (int r = 0; r < height; r++) {
-        offset[r + 1] = offset[r] + png_stream::row_segment_bytes(png_stream::row_block_bits(t, r, got + bins + (size_t)r * bins));
-        const unsigned int* sums = got + bins + (size_t)height * bins + 2 * (size_t)r;
-        adlers[r] = png_stream::row_adler(r, width, sums[0], sums[1]);
-    }
-    const uint64_t rows_bytes = offset[height], stream_words = (rows_bytes + 3) / 4;
-    if (stream_words > e->stream_capacity_words) return fail(GR_ERROR_DEVICE, who + "the rows' sizes exceed the bound (the device's histograms are not a frame's)");
-    for (int s = 0; s < e->symbols; s++) table_words[s] = (unsigned int)t.code[s] | ((unsigned int)t.length[s] << 16);
-    std::copy(t.header, t.header + png_stream::HEADER_WORDS, header_words);
-    // the second: placement up, the stream zeroed (the pack ORs the words segments share), the pack, the stream down
-    unsigned int* stream_at = e->scratch + gr_png_encoder::GUARD_WORDS;
-    HIP_CHECK(hipMemcpyAsync(e->placement, e->placement_host, e->placement_bytes, hipMemcpyHostToDevice, on));
-    HIP_CHECK(hipMemsetAsync(stream_at, 0, (size_t)stream_words * 4, on));
-    e->most_stream_words = std::max(e->most_stream_words, (size_t)stream_words);
-    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[2], on));
-    {
-        int w = width, h = height, header_bits = t.header_bits;
-        const unsigned long long* offsets_on_device = (const unsigned long long*)e->placement;
-        const unsigned int* table_on_device = (const unsigned int*)(e->placement + ((size_t)height + 1) * 8);
-        const unsigned int* header_on_device = table_on_device + e->symbols;
-        unsigned long long word_count = stream_words;
-        void* args[] = {&device_rgba8, &w, &h, &table_on_device, &header_on_device, &header_bits, &offsets_on_device, &stream_at, &word_count};
-        int rc = launch(p, runs ? K_PNG_PACK_RUNS : K_PNG_PACK, stream, (unsigned)height, 1, 64, 4, args);
-        if (rc != GR_OK) return rc;
-    }
-    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[3], on));
-    HIP_CHECK(hipMemcpyAsync(e->staging, stream_at, (size_t)stream_words * 4, hipMemcpyDeviceToHost, on));
-    HIP_CHECK(hipStreamSynchronize(on));
-    e->timed = e->time_launches;
-    png_stream::write_container(out_file, width, height, e->staging, rows_bytes, png_stream::join_adler(adlers.data(), width, height));
-    *out_bytes = (size_t)png_stream::file_bytes(rows_bytes);
-    return GR_OK;
-}
-
-// ---- JPEG frames: the device encoder (kernels/jpeg.hip; the stream and its host encoder: jpeg_stream.cpp) ------------------------
-
-struct gr_jpeg_encoder {
-    gr_program* program = nullptr;
-    int width = 0, height = 0, quality = 0;
-    // device: one allocation of 32-bit words, every region with GUARD_WORDS in front of it and behind the last, all filled with
-    // GUARD_PATTERN at creation - [coefficients | rows' slots | rows' byte counts, rows' FF counts, the file's size (64 bit) | file];
-    // the file region starts with the headers, uploaded at creation and never written again
-    static const size_t GUARD_WORDS = 64;
-    static const unsigned int GUARD_PATTERN = 0xa5c3e1f7u;
-    unsigned int* scratch = nullptr;
-    size_t region_at[4] = {}, region_words[4] = {}, scratch_words = 0;
-    size_t most_file_bytes = jpeg_stream::HEADER_BYTES;   // (the longest file of any encode so far)
-    unsigned int* tables = nullptr;    // jpeg_stream::device_tables
-    unsigned char* staging = nullptr;  // pinned: the file's size, then the file
-    uint64_t file_capacity = 0;
-    bool time_launches = false, timed = false;
-    hipEvent_t events[4] = {};
-    ~gr_jpeg_encoder() {
-        if (program) (void)hipSetDevice(program->device);
-        if (scratch) (void)hipFree(scratch);
-        if (tables) (void)hipFree(tables);
-        if (staging) (void)hipHostFree(staging);
-        for (hipEvent_t e : events)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
-int gr_jpeg_encoder_create(gr_program* p, int width, int height, int quality, gr_jpeg_encoder** out) {
-    const std::string who = "gr_jpeg_encoder_create: ";
-    if (!p || !out) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
-    std::string wrong = jpeg_stream::size_refusal(width, height);
-    if (wrong.empty()) wrong = jpeg_stream::quality_refusal(quality);
-    if (!wrong.empty()) return fail(GR_ERROR_INVALID_ARGUMENT, who + wrong);
-    HIP_CHECK(hipSetDevice(p->device));
-    auto e = std::make_unique<gr_jpeg_encoder>();
-    e->program = p;
-    e->width = width;
-    e->height = height;
-    e->quality = quality;
-    const size_t rows = (size_t)jpeg_stream::mcu_rows(height), across = (size_t)jpeg_stream::mcus_across(width);
-    e->file_capacity = jpeg_stream::file_bound(width, height);
-    const size_t words[4] = {rows * across * jpeg_stream::BLOCKS_PER_MCU * 32, rows * (size_t)(jpeg_stream::row_slot_bytes(width) / 4), 2 * rows + 2,
-                             (size_t)((e->file_capacity + 3) / 4)};
-    size_t at = gr_jpeg_encoder::GUARD_WORDS;
-    for (int r = 0; r < 4; r++) {   // (every region starts at a multiple of 16 bytes)
-        e->region_at[r] = at;
-        e->region_words[r] = (words[r] + 3) / 4 * 4;
-        at += e->region_words[r] + gr_jpeg_encoder::GUARD_WORDS;
-    }
-    e->scratch_words = at;
-    HIP_CHECK(hipMalloc((void**)&e->scratch, e->scratch_words * 4));
-    HIP_CHECK(hipMalloc((void**)&e->tables, jpeg_stream::TABLE_WORDS * 4));
-    HIP_CHECK(hipHostMalloc((void**)&e->staging, 8 + e->region_words[3] * 4, hipHostMallocDefault));
-    HIP_CHECK(hipMemsetD32((hipDeviceptr_t)e->scratch, (int)gr_jpeg_encoder::GUARD_PATTERN, e->scratch_words));
-    uint32_t tables[jpeg_stream::TABLE_WORDS];
-    uint8_t headers[jpeg_stream::HEADER_BYTES];
-    jpeg_stream::device_tables(quality, tables);
-    jpeg_stream::write_headers(headers, width, height, quality);
-    HIP_CHECK(hipMemcpy(e->tables, tables, sizeof(tables), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(e->scratch + e->region_at[3], headers, sizeof(headers), hipMemcpyHostToDevice));
-    HIP_CHECK(hipDeviceSynchronize());
-    *out = e.release();
-    return GR_OK;
-}
-
-void gr_jpeg_encoder_destroy(gr_jpeg_encoder* e) { delete e; }
-
-int gr_jpeg_encoder_time_launches(gr_jpeg_encoder* e, int on) {
-    if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_jpeg_encoder_time_launches: a required pointer is NULL");
-    HIP_CHECK(hipSetDevice(e->program->device));
-    if (on)
-        for (hipEvent_t& event : e->events)
-            if (!event) HIP_CHECK(hipEventCreate(&event));
-    e->time_launches = on != 0;
-    e->timed = false;
-    return GR_OK;
-}
-
-int gr_jpeg_encoder_launch_ms(gr_jpeg_encoder* e, float ms[3]) {
-    if (!e || !ms) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_jpeg_encoder_launch_ms: a required pointer is NULL");
-    if (!e->timed) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_jpeg_encoder_launch_ms: no encode was timed (gr_jpeg_encoder_time_launches)");
-    for (int k = 0; k < 3; k++) HIP_CHECK(hipEventElapsedTime(&ms[k], e->events[k], e->events[k + 1]));
-    return GR_OK;
-}
-
-int gr_jpeg_encoder_scratch_intact(gr_jpeg_encoder* e, int* intact) {
-    if (!e || !intact) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_jpeg_encoder_scratch_intact: a required pointer is NULL");
-    HIP_CHECK(hipSetDevice(e->program->device));
-    const size_t G = gr_jpeg_encoder::GUARD_WORDS;
-    *intact = 1;
-    // the five guards, the last of them together with what the file region holds behind the longest file so far
-    const size_t file_words_used = (e->most_file_bytes + 3) / 4;
-    for (int r = 0; r <= 4; r++) {
-        const size_t from = r < 4 ? e->region_at[r] - G : e->region_at[3] + file_words_used, to = r < 4 ? e->region_at[r] : e->scratch_words;
-        std::vector<unsigned int> host(to - from);
-        HIP_CHECK(hipMemcpy(host.data(), e->scratch + from, host.size() * 4, hipMemcpyDeviceToHost));
-        for (unsigned int word : host)
-            if (word != gr_jpeg_encoder::GUARD_PATTERN) *intact = 0;
-    }
-    return GR_OK;
-}
-
-int gr_jpeg_encode_rgba8(gr_jpeg_encoder* e, void* stream, const void* device_rgba8, unsigned char* out_file, size_t capacity, size_t* out_bytes) {
-    const std::string who = "gr_jpeg_encode_rgba8: ";
-    if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
-    bool too_small = false;
-    const std::string wrong = jpeg_stream::refusal(device_rgba8, e->width, e->height, e->quality, out_file, capacity, out_bytes, &too_small);
-    if (!wrong.empty()) return fail(too_small ? GR_ERROR_BUFFER_TOO_SMALL : GR_ERROR_INVALID_ARGUMENT, who + wrong);
-    gr_program* p = e->program;
-    hipStream_t on = (hipStream_t)stream;
-    HIP_CHECK(hipSetDevice(p->device));
-    int width = e->width, height = e->height, rows = jpeg_stream::mcu_rows(height);
-    unsigned int* coefficients = e->scratch + e->region_at[0];
-    unsigned int* slots = e->scratch + e->region_at[1];
-    unsigned int* row_bytes = e->scratch + e->region_at[2];
-    unsigned int* row_ff = row_bytes + rows;
-    unsigned long long* file_bytes = (unsigned long long*)(e->scratch + e->region_at[2] + e->region_words[2] - 2);   // the region's last two words: 8-byte aligned
-    unsigned char* file = (unsigned char*)(e->scratch + e->region_at[3]);
-    unsigned int slot_words = (unsigned int)(jpeg_stream::row_slot_bytes(width) / 4), header_bytes = jpeg_stream::HEADER_BYTES;
-    unsigned long long file_capacity = e->file_capacity;
-    const unsigned int* tables = e->tables;
-    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[0], on));
-    {
-        void* args[] = {&device_rgba8, &width, &height, &tables, &coefficients};
-        int rc = launch(p, K_JPEG_BLOCKS, stream, blocks(jpeg_stream::mcus_across(width), 4), (unsigned)rows, 64, 4, args);
-        if (rc != GR_OK) return rc;
-    }
-    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[1], on));
-    {
-        void* args[] = {&coefficients, &width, &height, &tables, &slots, &slot_words, &row_bytes, &row_ff};
-        int rc = launch(p, K_JPEG_PACK, stream, (unsigned)rows, 1, 64, 6, args);
-        if (rc != GR_OK) return rc;
-    }
-    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[2], on));
-    {
-        void* args[] = {&slots, &slot_words, &row_bytes, &row_ff, &rows, &file, &header_bytes, &file_capacity, &file_bytes};
-        int rc = launch(p, K_JPEG_GATHER, stream, (unsigned)rows, 1, 64, 4, args);
-        if (rc != GR_OK) return rc;
-    }
-    if (e->time_launches) HIP_CHECK(hipEventRecord(e->events[3], on));
-    // the first synchronisation: the file's size; the second: that many bytes
-    HIP_CHECK(hipMemcpyAsync(e->staging, file_bytes, 8, hipMemcpyDeviceToHost, on));
-    HIP_CHECK(hipStreamSynchronize(on));
-    e->timed = e->time_launches;
-    unsigned long long bytes = 0;
-    memcpy(&bytes, e->staging, 8);
-    if (bytes <= header_bytes || bytes > file_capacity) return fail(GR_ERROR_DEVICE, who + "the device's file size is not a file's of this frame size");
-    e->most_file_bytes = std::max(e->most_file_bytes, (size_t)bytes);
-    HIP_CHECK(hipMemcpyAsync(e->staging + 8, file, (size_t)bytes, hipMemcpyDeviceToHost, on));
-    HIP_CHECK(hipStreamSynchronize(on));
-    memcpy(out_file, e->staging + 8, (size_t)bytes);
-    *out_bytes = (size_t)bytes;
-    return GR_OK;
 }
 
 int gr_internal_fail(int code, const char* msg) { return fail((gr_status)code, msg ? msg : ""); }

@@ -13,28 +13,13 @@
 #include <vector>
 #include <mutex>
 
-#include "../../include/geodesic_hip_internal.h"
 #include "frame_format.hpp"
 #include "frame_plan.hpp"
+#include "internal.hpp"
 
 using frame_plan::origin_on_screen;
 using frame_plan::picture_motion;
 namespace switches = frame_plan::switches;
-
-extern "C" int gr_internal_fail(int code, const char* msg);   // capi.cpp
-extern "C" int gr_internal_check_analytic_sky(const char* who, const gr_analytic_sky* sky);   // capi.cpp: what every taker of a sky refuses
-
-#define HIP_CHECK(expr)                                                                                  \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess)                                                                            \
-            return gr_internal_fail(GR_ERROR_DEVICE, (std::string(#expr) + ": " + hipGetErrorString(_e)).c_str()); \
-    } while (0)
-#define GR_CHECK(expr)            \
-    do {                          \
-        int _rc = (expr);         \
-        if (_rc != GR_OK) return _rc; \
-    } while (0)
 
 // Small host -> device uploads (camera, $cfg values, features) go through PINNED memory of the library's own: hipMemcpyAsync from
 // pageable memory may read its source when the stream gets there, not when it is called - and the sources here are locals of

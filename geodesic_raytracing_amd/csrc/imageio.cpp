@@ -16,10 +16,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/geodesic_hip_internal.h"
 #include "frame_format.hpp"
-
-extern "C" int gr_internal_fail(int code, const char* msg);
+#include "internal.hpp"
 
 namespace {
 

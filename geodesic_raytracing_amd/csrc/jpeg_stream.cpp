@@ -5,7 +5,7 @@
 #include <algorithm>
 #include <cstring>
 
-extern "C" int gr_internal_fail(int code, const char* msg);
+#include "internal.hpp"
 
 namespace jpeg_stream {
 
@@ -263,11 +263,7 @@ std::string refusal(const void* rgba8, int width, int height, int quality, const
 
 namespace js = jpeg_stream;
 
-namespace {
-int refuse(const char* who, const std::string& wrong, bool too_small = false) {
-    return gr_internal_fail(too_small ? GR_ERROR_BUFFER_TOO_SMALL : GR_ERROR_INVALID_ARGUMENT, (std::string(who) + ": " + wrong).c_str());
-}
-}   // namespace
+using gr_internal::refuse;
 
 extern "C" {
 

@@ -1,6 +1,6 @@
 // jpeg_stream.hpp — the one JPEG stream both JPEG encoders write (geodesic_hip_internal.h, "JPEG frames"): colour conversion, the integer
 // DCT, the quantiser, the Annex K Huffman tables, the headers, the sizes.  Host only (no HIP): jpeg_stream.cpp compiles alone and holds
-// gr_jpeg_encode_rgba8_host, the definition kernels/jpeg.hip is held to byte for byte.  capi.cpp reads it.
+// gr_jpeg_encode_rgba8_host, the definition kernels/jpeg.hip is held to byte for byte.  device_encoders.cpp reads it.
 #pragma once
 
 #include <cstddef>

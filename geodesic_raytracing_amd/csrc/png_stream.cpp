@@ -8,7 +8,7 @@
 #include <cstring>
 #include <queue>
 
-extern "C" int gr_internal_fail(int code, const char* msg);
+#include "internal.hpp"
 
 namespace png_stream {
 
@@ -288,11 +288,9 @@ std::string refusal(const void* rgba8, int width, int height, const void* out_fi
 
 namespace ps = png_stream;
 
-namespace {
-int refuse(const char* who, const std::string& wrong, bool too_small) {
-    return gr_internal_fail(too_small ? GR_ERROR_BUFFER_TOO_SMALL : GR_ERROR_INVALID_ARGUMENT, (std::string(who) + ": " + wrong).c_str());
-}
+using gr_internal::refuse;
 
+namespace {
 // the filtered pixel bytes of one row (4 * width; the filter-type byte is not among them): Sub with bpp = 4 for row 0, Up for the others
 void filter_row(const unsigned char* rgba8, int width, int row, uint8_t* out) {
     const size_t n = 4 * (size_t)width;

@@ -1,7 +1,7 @@
 // png_stream.hpp — the PNG streams both PNG encoders write (geodesic_hip_internal.h, "PNG frames"; two kinds: literals only, and literals
 // with previous-pixel run matches): the length-limited Huffman table of a frame, its block header as a bit string, the tokens of a row, the
 // sizes of the row segments, the container.  Host only (no HIP): png_stream.cpp compiles alone and holds gr_png_encode_rgba8_host and
-// gr_png_encode_rgba8_host_as, the definition kernels/png.hip is held to byte for byte.  capi.cpp reads it.
+// gr_png_encode_rgba8_host_as, the definition kernels/png.hip is held to byte for byte.  device_encoders.cpp reads it.
 #pragma once
 
 #include <cstddef>

@@ -38,24 +38,12 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/geodesic_hip_internal.h"
 #include "frame_format.hpp"
+#include "internal.hpp"
 
-extern "C" int gr_internal_fail(int code, const char* msg);
-extern "C" int gr_internal_render_state_size(const gr_render_state* s, int* width, int* height);
-// frame.cpp: gr_render_frame and its three encoded kin by the format's value (a share is rendered through it)
-extern "C" int gr_internal_render_frame_as(int format, int layout, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
-                                           const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
-                                           int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* options);
 struct gr_tiled;
 
 namespace {
-
-#define HIP_CHECK(expr)                                                                                             \
-    do {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                     \
-        if (e_ != hipSuccess) return gr_internal_fail(GR_ERROR_DEVICE, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 // the part of the RCCL API used here (rccl.h: ncclUniqueId is 128 bytes, ncclFloat = 7, ncclSuccess = 0)
 struct rccl_api {

@@ -417,25 +417,23 @@ def png_encode_host(pixels, stream_kind=None):
     return out[:size.value].tobytes()
 
 
-class PngEncoder:
-    """A PNG encoder behind RGBA8 frames of one size that are already on the program's device (gr_png_encoder): filtering, histogram and
-    bit-packing run there, the compressed bytes come back.  encode() synchronises the stream it is given.  The program must outlive it.
-    stream_kind ("literals", "runs" or PNG_STREAM_*): the stream its files are written in (gr_png_encoder_create_as); None: literals."""
+class _DeviceEncoder:
+    """what PngEncoder and JpegEncoder share: the handle of a gr_png_encoder or gr_jpeg_encoder (_prefix: "gr_png_" or "gr_jpeg_"), the
+    output array of the encoder's bound, and the calls both kinds answer alike (_launches: the times launch_ms returns)"""
 
-    def __init__(self, program, width, height, stream_kind=None):
-        self.program, self.width, self.height = program, int(width), int(height)   # (the program is borrowed: kept alive here)
+    def _create(self, bound, create, *args):
         self.handle = c_void_p()
-        self.stream_kind = 0 if stream_kind is None else png_stream_kind(stream_kind)
-        if stream_kind is None:
-            check(lib.gr_png_encoder_create(program.handle, self.width, self.height, ctypes.byref(self.handle)))
-        else:
-            check(lib.gr_png_encoder_create_as(program.handle, self.width, self.height, self.stream_kind, ctypes.byref(self.handle)))
-        self._out = np.empty(png_encode_bound(self.width, self.height), dtype=np.uint8)
+        check(create(self.program.handle, self.width, self.height, *args, ctypes.byref(self.handle)))
+        self._out = np.empty(bound(self.width, self.height), dtype=np.uint8)
+
+    def _call(self, name, *args):
+        check(getattr(lib, self._prefix + name)(self.handle, *args))
 
     def encode(self, device_ptr, stream=None):
-        """the PNG file of the frame at device_ptr (width x height RGBA8 pixels) as bytes: png_encode_host's of the same pixels and kind"""
+        """the file of the frame at device_ptr (width x height RGBA8 pixels) as bytes: the host encoder's (png_encode_host of the same kind,
+        jpeg_encode_host of the same quality) of the same pixels"""
         size = ctypes.c_size_t()
-        check(lib.gr_png_encode_rgba8(self.handle, stream, device_ptr, self._out.ctypes.data_as(c_void_p), self._out.nbytes, ctypes.byref(size)))
+        self._call("encode_rgba8", stream, device_ptr, self._out.ctypes.data_as(c_void_p), self._out.nbytes, ctypes.byref(size))
         return self._out[:size.value].tobytes()
 
     def write(self, path, device_ptr, stream=None):
@@ -446,27 +444,44 @@ class PngEncoder:
         return len(data)
 
     def time_launches(self, on=True):
-        check(lib.gr_png_encoder_time_launches(self.handle, int(bool(on))))
+        self._call("encoder_time_launches", int(bool(on)))
 
     def launch_ms(self):
-        """(gr_png_histogram, gr_png_pack - or their _runs instances) of the last encode after time_launches(), in milliseconds"""
-        ms = (c_float * 2)()
-        check(lib.gr_png_encoder_launch_ms(self.handle, ms))
-        return ms[0], ms[1]
+        """the encoder's launches of the last encode after time_launches(), in milliseconds: (gr_png_histogram, gr_png_pack - or their _runs
+        instances), or (gr_jpeg_blocks, gr_jpeg_pack, gr_jpeg_gather)"""
+        ms = (c_float * self._launches)()
+        self._call("encoder_launch_ms", ms)
+        return tuple(ms)
 
     def scratch_intact(self):
-        """True when nothing outside the longest stream this encoder has made was written in its stream scratch, the guard words included"""
+        """True when nothing was written in the encoder's scratch outside what its encodes may write: the guard words, and what lies behind
+        the longest stream (PNG) or file (JPEG) it has made"""
         intact = c_int()
-        check(lib.gr_png_encoder_scratch_intact(self.handle, ctypes.byref(intact)))
+        self._call("encoder_scratch_intact", ctypes.byref(intact))
         return bool(intact.value)
 
     def close(self):
         handle, self.handle = getattr(self, "handle", None), None
         if handle:
-            lib.gr_png_encoder_destroy(handle)
+            getattr(lib, self._prefix + "encoder_destroy")(handle)
 
     def __del__(self):
         self.close()
+
+
+class PngEncoder(_DeviceEncoder):
+    """A PNG encoder behind RGBA8 frames of one size that are already on the program's device (gr_png_encoder): filtering, histogram and
+    bit-packing run there, the compressed bytes come back.  encode() synchronises the stream it is given.  The program must outlive it.
+    stream_kind ("literals", "runs" or PNG_STREAM_*): the stream its files are written in (gr_png_encoder_create_as); None: literals."""
+    _prefix, _launches = "gr_png_", 2
+
+    def __init__(self, program, width, height, stream_kind=None):
+        self.program, self.width, self.height = program, int(width), int(height)   # (the program is borrowed: kept alive here)
+        self.stream_kind = 0 if stream_kind is None else png_stream_kind(stream_kind)
+        if stream_kind is None:
+            self._create(png_encode_bound, lib.gr_png_encoder_create)
+        else:
+            self._create(png_encode_bound, lib.gr_png_encoder_create_as, self.stream_kind)
 
 
 def jpeg_encode_bound(width, height):
@@ -496,52 +511,15 @@ def jpeg_encode_host(pixels, quality=90):
     return out[:size.value].tobytes()
 
 
-class JpegEncoder:
+class JpegEncoder(_DeviceEncoder):
     """A JPEG encoder behind RGBA8 frames of one size that are already on the program's device (gr_jpeg_encoder): colour conversion, DCT,
     quantiser, Huffman coding and byte stuffing run there, the file's bytes come back.  encode() synchronises the stream it is given.  The
     program must outlive it."""
+    _prefix, _launches = "gr_jpeg_", 3
 
     def __init__(self, program, width, height, quality=90):
         self.program, self.width, self.height, self.quality = program, int(width), int(height), int(quality)   # (the program is borrowed: kept alive here)
-        self.handle = c_void_p()
-        check(lib.gr_jpeg_encoder_create(program.handle, self.width, self.height, self.quality, ctypes.byref(self.handle)))
-        self._out = np.empty(jpeg_encode_bound(self.width, self.height), dtype=np.uint8)
-
-    def encode(self, device_ptr, stream=None):
-        """the JPEG file of the frame at device_ptr (width x height RGBA8 pixels) as bytes: jpeg_encode_host's of the same pixels"""
-        size = ctypes.c_size_t()
-        check(lib.gr_jpeg_encode_rgba8(self.handle, stream, device_ptr, self._out.ctypes.data_as(c_void_p), self._out.nbytes, ctypes.byref(size)))
-        return self._out[:size.value].tobytes()
-
-    def write(self, path, device_ptr, stream=None):
-        """encode() into a file; returns its size"""
-        data = self.encode(device_ptr, stream)
-        with open(path, "wb") as f:
-            f.write(data)
-        return len(data)
-
-    def time_launches(self, on=True):
-        check(lib.gr_jpeg_encoder_time_launches(self.handle, int(bool(on))))
-
-    def launch_ms(self):
-        """(gr_jpeg_blocks, gr_jpeg_pack, gr_jpeg_gather) of the last encode after time_launches(), in milliseconds"""
-        ms = (c_float * 3)()
-        check(lib.gr_jpeg_encoder_launch_ms(self.handle, ms))
-        return ms[0], ms[1], ms[2]
-
-    def scratch_intact(self):
-        """True when the guard words of the encoder's scratch and the file region behind the longest file it has made are untouched"""
-        intact = c_int()
-        check(lib.gr_jpeg_encoder_scratch_intact(self.handle, ctypes.byref(intact)))
-        return bool(intact.value)
-
-    def close(self):
-        handle, self.handle = getattr(self, "handle", None), None
-        if handle:
-            lib.gr_jpeg_encoder_destroy(handle)
-
-    def __del__(self):
-        self.close()
+        self._create(jpeg_encode_bound, lib.gr_jpeg_encoder_create, self.quality)
 
 
 class AnalyticSky:
