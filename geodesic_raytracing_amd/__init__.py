@@ -103,6 +103,11 @@ class AnalyticSkyStruct(ctypes.Structure):
     _fields_ = [("meridians", c_int), ("parallels", c_int), ("line_width", c_float), ("quadrant", c_float * 3 * 4 * 2), ("line", c_float * 3 * 2)]
 
 
+class StarSkyStruct(ctypes.Structure):
+    """gr_star_sky (include/geodesic_hip_internal.h, "Star sky"); pipeline.StarSky wraps it"""
+    _fields_ = [("min_footprint", c_float), ("background", c_float * 3 * 2)]
+
+
 class ParkingLot(ctypes.Structure):
     """gr_parking_lot (gr_trace_fused_parking)"""
     _fields_ = [("records", c_void_p), ("words", c_void_p), ("lanes", c_int), ("trips", c_int), ("slots", c_int), ("groups", c_int)]
@@ -352,6 +357,17 @@ _SIGNATURES = {
     "gr_analytic_sky_image": (c_int, [ctypes.POINTER(AnalyticSkyStruct), c_int, c_int, c_int, c_void_p]),
     "gr_render_state_set_sky": (c_int, [c_void_p, ctypes.POINTER(AnalyticSkyStruct)]),
     "gr_render_state_sky": (c_int, [c_void_p, ctypes.POINTER(AnalyticSkyStruct), ctypes.POINTER(c_int)]),
+    "gr_star_sky_default": (c_int, [ctypes.POINTER(StarSkyStruct)]),
+    "gr_star_catalogue_create": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "gr_star_catalogue_destroy": (None, [c_void_p]),
+    "gr_star_catalogue_info": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "gr_star_catalogue_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gr_star_field_random": (c_int, [ctypes.c_ulonglong, c_int, c_void_p, c_void_p]),
+    "gr_render_stars": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(StarSkyStruct), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gr_render_stars_strips": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(StarSkyStruct), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_void_p, c_void_p]),
+    "gr_render_state_set_stars": (c_int, [c_void_p, ctypes.POINTER(StarSkyStruct), c_void_p, c_void_p]),
+    "gr_render_state_stars": (c_int, [c_void_p, ctypes.POINTER(StarSkyStruct), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_int)]),
     "gr_png_encode_bound": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "gr_png_encode_rgba8_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
     "gr_png_encode_rgba8_host_as": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_int]),
@@ -403,4 +419,4 @@ from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderStat
                        default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background, rgba8_to_yuv420,
                        yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes, accumulate_frame, filter_taps,
                        filter_frame, PngEncoder, png_encode_bound, png_encode_host, JpegEncoder, jpeg_encode_bound, jpeg_encode_host, jpeg_quant_tables,
-                       AviWriter, AnalyticSky)
+                       AviWriter, AnalyticSky, StarCatalogue, StarSky, star_field_random)

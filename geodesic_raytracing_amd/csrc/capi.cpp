@@ -71,19 +71,20 @@ const char* const KERNEL_NAMES[] = {
     "gr_handle_adaptive_sampling", "gr_render", "gr_trace_fused", "gr_trace_fused_lattice", "gr_trace_pair", "gr_trace_compact", "gr_prepass_fused", "gr_camera_setup", "gr_order_tiles", "gr_adaptive_refine", "gr_trace_pending", "gr_apply_guessed", "gr_do_generic_rays_scheduled", "gr_sort_tiles_count", "gr_sort_tiles_place", "gr_trace_fused_parking", "gr_boost_tetrad", "gr_init_inertial_ray",
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
     "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack",
-    "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather", "gr_png_histogram_runs", "gr_png_pack_runs", "gr_render_analytic"};
+    "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather", "gr_png_histogram_runs", "gr_png_pack_runs", "gr_render_analytic",
+    "gr_render_stars", "gr_stars_count", "gr_stars_scan", "gr_stars_scatter", "gr_stars_order", "gr_stars_gather", "gr_stars_sums", "gr_stars_prefix"};
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
 // filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and 8- and 10-bit Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
 // (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation - and the two integer kernels of the
 // PNG encoder (kernels/png.hip; each in two instances, one a stream kind) and the three of the JPEG encoder (kernels/jpeg.hip), which want
-// no part in it either
+// no part in it either - and the seven that build a star catalogue (kernels/stars.hip), whose sums are taken in the order they are written
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
            k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE || k == K_RESOLVE_FILTERED ||
            k == K_PNG_HISTOGRAM || k == K_PNG_PACK || k == K_JPEG_BLOCKS || k == K_JPEG_PACK || k == K_JPEG_GATHER || k == K_PNG_HISTOGRAM_RUNS ||
-           k == K_PNG_PACK_RUNS;
+           k == K_PNG_PACK_RUNS || (k >= K_STARS_COUNT && k <= K_STARS_PREFIX);
 }
 
 namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files
@@ -690,7 +691,7 @@ int gr_program_create(const char* argument_string, int device, gr_program** out)
         if (hipModuleGetFunction(&p->fn[k], p->module, KERNEL_NAMES[k]) != hipSuccess) {
             p->fn[k] = nullptr;
             (void)hipGetLastError();
-            p->in_rest[k] = !(k == K_TRACE_PAIR || k == K_TRACE_FUSED_PARKING || k == K_RENDER_ANALYTIC);   // (gr_render_analytic: shading.hip puts it beside gr_render)
+            p->in_rest[k] = !(k == K_TRACE_PAIR || k == K_TRACE_FUSED_PARKING || k == K_RENDER_ANALYTIC || k == K_RENDER_STARS);   // (gr_render_analytic, gr_render_stars: shading.hip puts them beside gr_render)
         }
     }
     if (!p->fn[K_TRACE_FUSED] || !p->fn[K_RENDER] || !p->fn[K_PREPASS_FUSED] || !p->fn[K_ORDER_TILES])
@@ -982,6 +983,7 @@ int gr_internal::launch(gr_program* p, int k, void* stream, unsigned gx, unsigne
     return GR_OK;
 }
 int gr_internal::device_of(const gr_program* p) { return p->device; }
+const void* gr_internal::no_count_of(const gr_program* p) { return p->huge_count; }
 }
 using gr_internal::blocks, gr_internal::launch;
 

@@ -81,6 +81,11 @@ struct gr_render_state {
     // one (the default) by gr_render / gr_render_strips, launch for launch as before.  Shading only: the records do not depend on it.
     bool sky_set = false;
     gr_analytic_sky sky{};
+    // gr_render_state_set_stars: likewise shaded by gr_render_stars, from catalogues the caller keeps alive; never both (the setters refuse)
+    bool stars_set = false;
+    gr_star_sky star_sky{};
+    const gr_star_catalogue* near_stars = nullptr;
+    const gr_star_catalogue* far_stars = nullptr;
     hipEvent_t ev_resolve[2] = {};   // time_kernels = 1: around the resolve launch (gr_render_state_resolve_ms)
     bool resolve_timed = false;
     upload_ring uploads;
@@ -474,7 +479,7 @@ static std::mutex live_states_lock;
 static std::vector<const gr_render_state*> live_states;
 static bool state_has_sky(const gr_render_state* s) {
     std::lock_guard<std::mutex> guard(live_states_lock);
-    return std::find(live_states.begin(), live_states.end(), s) != live_states.end() && s->sky_set;
+    return std::find(live_states.begin(), live_states.end(), s) != live_states.end() && (s->sky_set || s->stars_set);
 }
 
 // a state whose frames are out_width x out_height and are traced at factor x that per axis (1: gr_render_state_create)
@@ -598,7 +603,8 @@ int gr_render_state_filter(const gr_render_state* s, int* filter) {
 int gr_render_state_set_sky(gr_render_state* s, const gr_analytic_sky* sky) {
     if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_sky: null render state");
     if (sky) {
-        GR_CHECK(gr_internal_check_analytic_sky("gr_render_state_set_sky", sky));
+        GR_CHECK(gr_internal_check_analytic_sky("gr_render_state_set_sky", sky));   // (the sky is looked at before the state)
+        if (s->stars_set) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_sky: the state has stars (gr_render_state_set_stars); the two are not composed");
         s->sky = *sky;
     }
     s->sky_set = sky != nullptr;
@@ -609,6 +615,26 @@ int gr_render_state_sky(const gr_render_state* s, gr_analytic_sky* out, int* is_
     if (!s || !out || !is_set) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_sky: null argument");
     *is_set = s->sky_set ? 1 : 0;
     if (s->sky_set) *out = s->sky;
+    return GR_OK;
+}
+
+int gr_render_state_set_stars(gr_render_state* s, const gr_star_sky* sky, const gr_star_catalogue* near, const gr_star_catalogue* far) {
+    if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_stars: null render state");
+    if (sky) {
+        GR_CHECK(gr_internal_check_star_sky("gr_render_state_set_stars", sky, near, far, nullptr));   // (likewise)
+        if (s->sky_set) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_stars: the state has an analytic sky (gr_render_state_set_sky); the two are not composed");
+        s->star_sky = *sky;
+    }
+    s->stars_set = sky != nullptr;
+    s->near_stars = sky ? near : nullptr;
+    s->far_stars = sky ? far : nullptr;
+    return GR_OK;
+}
+
+int gr_render_state_stars(const gr_render_state* s, gr_star_sky* out, const gr_star_catalogue** near, const gr_star_catalogue** far, int* is_set) {
+    if (!s || !out || !near || !far || !is_set) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_stars: null argument");
+    *is_set = s->stars_set ? 1 : 0;
+    if (s->stars_set) *out = s->star_sky, *near = s->near_stars, *far = s->far_stars;
     return GR_OK;
 }
 
@@ -1183,7 +1209,7 @@ static int fused_plan_frame(frame_context& f) {
     if (f.plan.refused.code != GR_OK) return gr_internal_fail(f.plan.refused.code, f.plan.refused.message);
     if (f.plan.invalidate_tile_cost) s->tile_cost_valid = false;
     // a frame with an analytic sky is shaded by fused_shade's one launch: the trace has no textures to shade tiles from
-    if (s->sky_set) f.plan.shade_in_trace = false;
+    if (s->sky_set || s->stars_set) f.plan.shade_in_trace = false;
     return GR_OK;
 }
 
@@ -1456,7 +1482,10 @@ static int fused_shade(frame_context& f) {
     const int compact_out = q.strip_count > 1 ? f.opt.compact_out : 0;
     if (!f.out) return GR_OK;
     GR_CHECK(f.begin(GR_STAGE_RENDER));
-    if (s->sky_set)
+    if (s->stars_set)
+        GR_CHECK(gr_render_stars_strips(f.p, f.stream, s->render_data, f.out, &s->star_sky, s->near_stars, s->far_stars, f.width, f.height,
+                                        q.strip_count > 1 ? q.block_rows : f.height, q.strip_rank, q.strip_count, compact_out, s->cfg, s->dfg));
+    else if (s->sky_set)
         GR_CHECK(gr_render_analytic_strips(f.p, f.stream, s->render_data, f.out, &s->sky, f.width, f.height, q.strip_count > 1 ? q.block_rows : f.height,
                                            q.strip_rank, q.strip_count, compact_out, s->cfg, s->dfg));
     else if (q.shade_in_trace)
@@ -1578,7 +1607,10 @@ static int render_reference_shaped(frame_context& f) {
 
     if (f.out) {
         GR_CHECK(f.begin(GR_STAGE_RENDER));
-        if (s->sky_set)
+        if (s->stars_set)
+            GR_CHECK(gr_render_stars(p, stream, s->render_data, s->render_data_count, width * height, f.out, &s->star_sky, s->near_stars, s->far_stars, width, height,
+                                     s->cfg, s->dfg));
+        else if (s->sky_set)
             GR_CHECK(gr_render_analytic(p, stream, s->render_data, s->render_data_count, width * height, f.out, &s->sky, width, height, s->cfg, s->dfg));
         else
             GR_CHECK(gr_render(p, stream, s->render_data, s->render_data_count, width * height, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height,

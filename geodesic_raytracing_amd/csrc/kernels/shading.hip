@@ -341,5 +341,157 @@ extern "C" __global__ void gr_render_analytic(const render_data* __restrict__ rd
     out[out_index] = shade_pixel_analytic(self, beside, below, sky, dfg);
     (void)cfg;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The star sky (no reference counterpart; defined in include/geodesic_hip_internal.h, "Star sky"): point stars gathered from a catalogue
+// that kernels/stars.hip built - cell_start[cells + 1], the stars' records cell by cell (two float4 a star: u, v, r, g | b), and a
+// float64 summed-area table of the cells' flux.  A pixel whose footprint spans at most 4 x 4 cells (NEAR) sums tents over the stars
+// themselves; a wider one (FAR) takes the box integral of the table.  gr_star_sky and a view of each side's catalogue travel in the
+// kernel's argument block (a NULL catalogue: n = 0 and no pointers).
+struct star_sky {
+    float min_footprint;
+    float background[2][3];
+};
+struct star_catalogue_view {
+    const int* cell_start;
+    const float4* stars;
+    const double* table;
+    int n, cells_u, cells_v;
+};
+
+// NEAR, step 3: the sum of flux x tent x tent, not yet divided by the footprint's area.  The cells i0 ... i1 of a row are one run of
+// consecutive cells, or two where the run crosses the seam of u (cells are taken modulo cells_u, a power of two), and the stars of a
+// run of cells are one run of records: cell_start of its first cell to cell_start behind its last - four loads a row, issued together
+// ahead of the stars.  A run `turn` turns away from the pixel has its stars at u_s + turn: the difference is formed as (u_s - a) - b
+// with (a, b) = (0, u), (1, u) for turn -1 (u_s - 1 is exact for a star in front of the seam) or (0, u - 1) for turn +1 (u - 1 is
+// exact for a pixel there), and the pragma keeps the two subtractions apart: folded into u_s - (a + b) they would round a position
+// against the turn, 2^-24 of a tent that may be 2^-19 wide.  Per star: those two, v_s - v, two tents and three multiply-adds.
+__device__ __forceinline__ float3 star_sum_near(const star_catalogue_view& cat, float u, float v, float hu, float hv, int i0, int i1, int j0, int j1) {
+#pragma clang fp reassociate(off)
+    const float inverse_u = 1.f / (2.f * hu), inverse_v = 1.f / (2.f * hv);
+    const int shift = 31 - __builtin_clz(cat.cells_u), mask = cat.cells_u - 1;
+    const int seam = ((i0 >> shift) + 1) << shift;        // the first cell of the next turn
+    const int last = min(i1, seam - 1);
+    const bool two_runs = i1 >= seam;
+    const int turn = i0 >> shift;                          // of the first run: -1, 0 (or 1 for u = 1); the second run is one further
+    const float a0 = turn < 0 ? 1.f : 0.f, b0 = turn > 0 ? u - 1.f : u;
+    const float a1 = turn + 1 < 0 ? 1.f : 0.f, b1 = turn + 1 > 0 ? u - 1.f : u;
+    float r = 0.f, g = 0.f, b = 0.f;
+    for (int j = max(j0, 0); j <= min(j1, cat.cells_v - 1); j++) {
+        const int* row = cat.cell_start + j * cat.cells_u;
+        const int begin0 = row[i0 & mask], end0 = row[(last & mask) + 1];
+        const int begin1 = two_runs ? row[0] : 0, end1 = two_runs ? row[(i1 & mask) + 1] : 0;
+#pragma unroll
+        for (int run = 0; run < 2; run++) {
+            const int begin = run ? begin1 : begin0, end = min(run ? end1 : end0, cat.n);
+            const float a = run ? a1 : a0, from = run ? b1 : b0;
+            for (int s = max(begin, 0); s < end; s++) {
+                const float4 first = cat.stars[2 * s], second = cat.stars[2 * s + 1];
+                const float du = (first.x - a) - from, dv = first.y - v;
+                const float tent_u = __builtin_fmaxf(1.f - __builtin_fabsf(du) * inverse_u, 0.f), tent_v = __builtin_fmaxf(1.f - __builtin_fabsf(dv) * inverse_v, 0.f);
+                const float weight = tent_u * tent_v;
+                r += first.z * weight;
+                g += first.w * weight;
+                b += second.x * weight;
+            }
+        }
+    }
+    return f3(r, g, b);
+}
+
+// I(x, y) of step 4 for one channel's plane, x in [-1, 2], y in [0, 1]
+__device__ __forceinline__ double star_table_at(const double* plane, int cells_u, int cells_v, double x, double y) {
+    const double turns = __builtin_floor(x);
+    const double X = (x - turns) * cells_u, Y = y * cells_v;
+    const int i = min(max((int)X, 0), cells_u - 1), j = min(max((int)Y, 0), cells_v - 1);
+    const double a = X - i, b = Y - j;
+    const double* lower = plane + (size_t)j * (cells_u + 1);
+    const double* upper = lower + (cells_u + 1);
+    const double inside = (1 - a) * (1 - b) * lower[i] + a * (1 - b) * lower[i + 1] + (1 - a) * b * upper[i] + a * b * upper[i + 1];
+    return inside + turns * ((1 - b) * lower[cells_u] + b * upper[cells_u]);
+}
+
+// FAR, step 4: the stars as a glow, in double (the four terms cancel), already divided by the footprint's area.  Few pixels come
+// here.  A channel at a time, so that sixteen doubles are in flight and not forty-eight.  Inlined on purpose: as a noinline function
+// the kernel took the callee's registers anyway (120 VGPRs against 108) and 84 bytes of scratch for what it keeps across the call.
+__device__ __forceinline__ float3 star_glow_far(const double* table, int cells_u, int cells_v, float u, float v, float hu, float hv) {
+    const double left = (double)u - (double)hu, right = (double)u + (double)hu;
+    const double v0 = __builtin_fmax((double)v - (double)hv, 0.0), v1 = __builtin_fmin((double)v + (double)hv, 1.0);
+    const double area = 4.0 * (double)hu * (double)hv;
+    const size_t plane = (size_t)(cells_v + 1) * (size_t)(cells_u + 1);
+    float r = 0.f, g = 0.f, b = 0.f;
+#pragma unroll 1   // a channel at a time: sixteen doubles in flight, not forty-eight
+    for (int k = 0; k < 3; k++) {
+        const double* t = table + k * plane;
+        const double sum = star_table_at(t, cells_u, cells_v, right, v1) - star_table_at(t, cells_u, cells_v, left, v1) -
+                           star_table_at(t, cells_u, cells_v, right, v0) + star_table_at(t, cells_u, cells_v, left, v0);
+        const float value = (float)(sum / area);
+        r = k == 0 ? value : r;
+        g = k == 1 ? value : g;
+        b = k == 2 ? value : b;
+    }
+    return f3(r, g, b);
+}
+
+// One pixel: `self`, `beside` and `below` as shade_pixel_analytic takes them
+__device__ __forceinline__ float4 shade_pixel_stars(const render_data& self, float2 beside, float2 below, const star_sky& sky, const star_catalogue_view& near_stars,
+                                                    const star_catalogue_view& far_stars, dfg_t dfg) {
+    if (self.terminated != 1) return f4(0, 0, 0, 1);
+    const float u = self.tex_coord.x, v = self.tex_coord.y;
+    const float hu = __builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(u, beside.x)) + __builtin_fabsf(wrapped_difference(u, below.x))), sky.min_footprint);
+    const float hv = __builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(v, beside.y)) + __builtin_fabsf(wrapped_difference(v, below.y))), sky.min_footprint);
+    const bool near_side = self.side >= 1;   // which side of a wormhole the ray ended on, as shade_pixel picks bg1 / bg2
+    const star_catalogue_view cat = near_side ? near_stars : far_stars;
+    float3 stars = f3(0.f, 0.f, 0.f);
+    if (cat.n > 0) {
+        // step 2: single IEEE operations and multiplications by powers of two - what contraction makes of them is the same value.  The
+        // clamp only keeps a coordinate that is no coordinate (not finite) from overflowing the conversion.
+        const float margin = 2.384185791015625e-07f;   // 2^-22
+        const float reach_u = 2.f * hu + margin, reach_v = 2.f * hv + margin;
+        const float cells_u = (float)cat.cells_u, cells_v = (float)cat.cells_v, most = 16777216.f;
+        const int i0 = (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf((u - reach_u) * cells_u), -most), most);
+        const int i1 = (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf((u + reach_u) * cells_u), -most), most);
+        const int j0 = (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf((v - reach_v) * cells_v), -most), most);
+        const int j1 = (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf((v + reach_v) * cells_v), -most), most);
+        if (i1 - i0 <= 3 && j1 - j0 <= 3) {
+            const float3 sum = star_sum_near(cat, u, v, hu, hv, i0, i1, j0, j1);
+            const float per_area = 1.f / (4.f * hu * hv);
+            stars = f3(sum.x * per_area, sum.y * per_area, sum.z * per_area);
+        } else {
+            stars = star_glow_far(cat.table, cat.cells_u, cat.cells_v, u, v, hu, hv);
+        }
+    }
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = srgb_to_linear(near_side ? sky.background[1][k] : sky.background[0][k]);
+    float3 rgb = f3(c[0] + stars.x, c[1] + stars.y, c[2] + stars.z);
+    if (GET_FEATURE(redshift, dfg)) rgb = apply_redshift(rgb, self.z_shift, dfg);   // (gr_render's colour tail, entered in linear light)
+#ifndef LINEAR_FRAMEBUFFER
+    rgb = linear_to_srgb(rgb);
+#endif
+    return f4(rgb.x, rgb.y, rgb.z, 1.f);
+}
+
+// gr_render_analytic's launch, argument for argument, with the star sky and the two catalogues in place of the analytic sky
+extern "C" __global__ void gr_render_stars(const render_data* __restrict__ rdata, const int* __restrict__ rdata_count, float4* __restrict__ out,
+                                           star_sky sky, star_catalogue_view near_stars, star_catalogue_view far_stars, int width, int height,
+                                           cfg_t cfg, dfg_t dfg, int num_pixels, int block_pixels, int strip_rank, int strip_count, int compact_out) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= num_pixels) return;
+    const int lb = gid / block_pixels, off = gid - lb * block_pixels;
+    const int id = (lb * strip_count + strip_rank) * block_pixels + off;
+    if (id >= *rdata_count || id >= width * height) return;
+    const render_data self = rdata[id];
+    const int px = self.sx, py = self.sy;
+    const int out_index = compact_out ? lb * block_pixels + off : py * width + px;
+    const bool last_column = px == width - 1, last_row = py == height - 1;
+    float2 beside = make_float2(0, 0), below = make_float2(0, 0);
+    if (self.terminated == 1) {
+        beside = rdata[py * width + px + (last_column ? (width > 1 ? -1 : 0) : 1)].tex_coord;
+        below = rdata[(py + (last_row ? (height > 1 ? -1 : 0) : 1)) * width + px].tex_coord;
+    }
+    out[out_index] = shade_pixel_stars(self, beside, below, sky, near_stars, far_stars, dfg);
+    (void)cfg;
+}
 #endif  // GR_FRAME_KERNELS
 

@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from . import (AnalyticSkyStruct, Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, FRAME_YUV420, FRAME_YUV420P10, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
+from . import (AnalyticSkyStruct, StarSkyStruct, Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, FRAME_YUV420, FRAME_YUV420P10, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
                c_size_t, c_void_p, check, lib)
 
 LIGHTRAY_DTYPE = np.dtype([("position", "<f4", 4), ("velocity", "<f4", 4), ("initial_quat", "<f4", 4),
@@ -570,16 +570,82 @@ class AnalyticSky:
         return out
 
 
+def star_field_random(seed, n):
+    """gr_star_field_random: n stars uniform on the sphere from a splitmix64 stream, a power law of brightness, colours by spectral class
+    (the recipe: include/geodesic_hip_internal.h, "Star sky") -> (uv float32 [n][2], flux float32 [n][3], already per unit of (u, v) area)"""
+    uv, flux = np.empty((int(n), 2), dtype=np.float32), np.empty((int(n), 3), dtype=np.float32)
+    check(lib.gr_star_field_random(int(seed), int(n), uv.ctypes.data_as(c_void_p), flux.ctypes.data_as(c_void_p)))
+    return uv, flux
+
+
+class StarCatalogue:
+    """gr_star_catalogue: n point stars - uv [n][2] in tex_coord's sky coordinates, flux [n][3] linear RGB per unit of (u, v) area - binned,
+    ordered and summed on the program's device (kernels/stars.hip).  cells_u x cells_v: powers of two, 16 ... 4096 (None: 1024 x 512).
+    The program is borrowed for the build only.  Hand it to RenderState(stars=(StarSky, near, far)) and keep it alive while frames render."""
+
+    def __init__(self, program, uv, flux, cells_u=None, cells_v=None):
+        uv, flux = np.ascontiguousarray(uv, dtype=np.float32), np.ascontiguousarray(flux, dtype=np.float32)
+        if uv.ndim != 2 or uv.shape[1] != 2 or flux.shape != (uv.shape[0], 3):
+            raise ValueError("uv [n][2] and flux [n][3]")
+        self.handle = c_void_p()
+        check(lib.gr_star_catalogue_create(program.handle, uv.shape[0], uv.ctypes.data_as(c_void_p), flux.ctypes.data_as(c_void_p), int(cells_u or 0),
+                                           int(cells_v or 0), ctypes.byref(self.handle)))
+        n, cu, cv = c_int(), c_int(), c_int()
+        check(lib.gr_star_catalogue_info(self.handle, ctypes.byref(n), ctypes.byref(cu), ctypes.byref(cv)))
+        self.n, self.cells_u, self.cells_v = n.value, cu.value, cv.value
+
+    @classmethod
+    def random(cls, program, seed, n, cells_u=None, cells_v=None):
+        return cls(program, *star_field_random(seed, n), cells_u=cells_u, cells_v=cells_v)
+
+    def download(self):
+        """(cell_start int32 [cells + 1], order int32 [n], table float64 [3][cells_v + 1][cells_u + 1]) as the device holds them"""
+        cell_start = np.empty(self.cells_u * self.cells_v + 1, dtype=np.int32)
+        order = np.empty(self.n, dtype=np.int32)
+        table = np.empty((3, self.cells_v + 1, self.cells_u + 1), dtype=np.float64)
+        check(lib.gr_star_catalogue_download(self.handle, cell_start.ctypes.data_as(c_void_p), order.ctypes.data_as(c_void_p), table.ctypes.data_as(c_void_p)))
+        return cell_start, order, table
+
+    def close(self):
+        if self.handle:
+            lib.gr_star_catalogue_destroy(self.handle)
+            self.handle = c_void_p()
+
+    def __del__(self):
+        self.close()
+
+
+class StarSky:
+    """gr_star_sky: min_footprint (a power of two, 2^-20 ... 2^-8; the angular size below which a star is no longer a point) and
+    background [2][3] (stored sRGB values in [0, 1] behind the stars; side 0 the far sky, side 1 the near one).  The library's defaults
+    (2^-16, black), then the overrides."""
+
+    def __init__(self, min_footprint=None, background=None):
+        self.struct = StarSkyStruct()
+        check(lib.gr_star_sky_default(ctypes.byref(self.struct)))
+        if min_footprint is not None:
+            self.struct.min_footprint = float(min_footprint)
+        if background is not None:
+            np.ctypeslib.as_array(self.struct.background)[...] = np.asarray(background, dtype=np.float32).reshape(2, 3)
+
+    min_footprint = property(lambda self: self.struct.min_footprint)
+
+    @property
+    def background(self):
+        return np.ctypeslib.as_array(self.struct.background).copy()
+
+
 class RenderState:
     """Per-frame device buffers + the frame sequence (render_state.hpp:97-197, main.cpp:2244-2526)."""
 
-    def __init__(self, width, height, device=0, supersample=1, filter=FILTER_BOX, sky=None):
+    def __init__(self, width, height, device=0, supersample=1, filter=FILTER_BOX, sky=None, stars=None):
         """supersample = f > 1 (gr_render_state_create_supersampled; 2, 3 or 4): frames are still width x height, traced at f x that per
         axis and box-averaged on the device (box_resolve says what that means).  Everything else about the state - buffer(), the
         prepass grid, tile history - is of traced_size.  filter (gr_render_state_set_filter): FILTER_BOX, or FILTER_TENT / _GAUSSIAN /
         _MITCHELL or their names - every frame of the state is then filter_frame of the traced frame with filter_taps' table, at
         factor 1 too, whole frames only.  sky (gr_render_state_set_sky): an AnalyticSky - every frame of the state is then shaded from
-        it by gr_render_analytic, and render() needs no background."""
+        it by gr_render_analytic, and render() needs no background.  stars (gr_render_state_set_stars): (StarSky, near StarCatalogue or None, far
+        StarCatalogue or None) - every frame is shaded by gr_render_stars from the catalogues; not together with sky."""
         self.width, self.height, self.device = width, height, device
         self.handle = c_void_p()
         if supersample == 1:
@@ -593,6 +659,25 @@ class RenderState:
             self.set_filter(filter)
         if sky is not None:
             self.set_sky(sky)
+        if stars is not None:
+            self.set_stars(*stars)
+
+    def set_stars(self, star_sky, near=None, far=None):
+        """the stars of the frames from here on: a StarSky and the catalogues of the near and the far side (either may be None: no stars
+        there), or set_stars(None): back to the background textures.  The state keeps the catalogues alive."""
+        check(lib.gr_render_state_set_stars(self.handle, ctypes.byref(star_sky.struct) if star_sky is not None else None,
+                                            near.handle if near is not None and star_sky is not None else None,
+                                            far.handle if far is not None and star_sky is not None else None))
+        self._stars = (star_sky, near, far) if star_sky is not None else None
+
+    @property
+    def stars(self):
+        """(StarSky, near, far) as set, or None"""
+        out, near, far, is_set = StarSky(), c_void_p(), c_void_p(), c_int()
+        check(lib.gr_render_state_stars(self.handle, ctypes.byref(out.struct), ctypes.byref(near), ctypes.byref(far), ctypes.byref(is_set)))
+        if not is_set.value:
+            return None
+        return (out,) + tuple(getattr(self, "_stars", None)[1:])
 
     def set_sky(self, sky):
         """the analytic sky of the frames from here on (an AnalyticSky), or None: back to the background textures"""

@@ -29,6 +29,7 @@
 """
 import argparse
 import ctypes
+import math
 import os
 import sys
 
@@ -163,7 +164,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
            parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box",
            png="host", jpeg=None, quality=90, png_stream="literals", sky=None):
-    """sky: a gra.AnalyticSky - every frame is shaded from it in closed form (RenderState(sky=)); `background` and `mips` are then unused.
+    """sky: a gra.AnalyticSky - every frame is shaded from it in closed form (RenderState(sky=)) - or a StarField - point stars, lensed on the
+    device (RenderState(stars=)); `background` and `mips` are then unused.
     Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
     at f x the size per axis and box-averaged on the device (the reference's supersample setting, graphics_settings.hpp:23-24).
@@ -221,7 +223,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     cfg_values = metric.cfg_values(**(cfg or {}))
     manager = ProgramManager(metric, device, feats, cfg_values)
     program = manager.current(wait=wait_for_static)
-    state = gra.RenderState(width, height, device, supersample=supersample, filter=filter, sky=sky)
+    stars = sky.on(program) if isinstance(sky, StarField) else None   # (point stars: a catalogue built on this device, the same on both sides)
+    state = gra.RenderState(width, height, device, supersample=supersample, filter=filter, sky=sky if stars is None else None, stars=stars)
     if sky is None:
         rgba = background if background is not None else gra.synthetic_background(2048, 1024)
         if mips == "device":
@@ -346,7 +349,11 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
         skies[d] = (dbg, (dbg.ptr, rgba.shape[1], rgba.shape[0], levels))
     parts = gra.TiledFrame.local(devices, width, height, split_block_rows(height, block_rows))
     try:
-        states = [gra.RenderState(width, height, d, supersample=supersample, sky=sky) for d in devices]
+        if isinstance(sky, StarField):   # a catalogue per device, built once however many participants the device carries
+            fields = {d: sky.on(programs[d]) for d in programs}
+            states = [gra.RenderState(width, height, d, supersample=supersample, stars=fields[d]) for d in devices]
+        else:
+            states = [gra.RenderState(width, height, d, supersample=supersample, sky=sky) for d in devices]
         out = DeviceBuffer(devices[0], width * height * (4 if rgba8 else 16))
         cam = gra.default_camera(camera_pos, camera_quat)
         encoder = (gra.PngEncoder(programs[devices[0]], width, height, png_stream) if png == "device" else
@@ -370,9 +377,30 @@ def render_split(metric_name, width, height, devices, scripts=None, cfg=None, ca
             part.close()
 
 
+class StarField:
+    """--sky stars:N[:SEED[:MIN_FOOTPRINT]]: N generated stars (gra.star_field_random), the same catalogue on both sides, black behind them"""
+
+    def __init__(self, n, seed=1, min_footprint=2.0 ** -16):
+        if not 1 <= n <= 1 << 24:
+            raise ValueError("N: 1 to 16777216 stars")
+        mantissa, exponent = math.frexp(min_footprint)
+        if mantissa != 0.5 or not -20 <= exponent - 1 <= -8:
+            raise ValueError("MIN_FOOTPRINT: a power of two from 2^-20 to 2^-8, e.g. 1.52587890625e-05")
+        self.n, self.seed, self.min_footprint = n, seed, min_footprint
+
+    def on(self, program):
+        """RenderState(stars=...) for a state of the program's device"""
+        catalogue = gra.StarCatalogue.random(program, self.seed, self.n)
+        return gra.StarSky(min_footprint=self.min_footprint), catalogue, catalogue
+
+
 def parse_sky(text):
-    """--sky grid[:MxP[:WIDTH]] -> gra.AnalyticSky (the library refuses what is out of range)"""
+    """--sky grid[:MxP[:WIDTH]] -> gra.AnalyticSky (the library refuses what is out of range); --sky stars:N[:SEED[:MIN_FOOTPRINT]] -> StarField"""
     parts = text.split(":")
+    if parts[0] == "stars":
+        if not 2 <= len(parts) <= 4:
+            raise ValueError("stars:N[:SEED[:MIN_FOOTPRINT]], e.g. stars:200000:7")
+        return StarField(int(parts[1]), int(parts[2]) if len(parts) > 2 else 1, float(parts[3]) if len(parts) > 3 else 2.0 ** -16)
     if parts[0] != "grid" or len(parts) > 3:
         raise ValueError("grid[:MxP[:WIDTH]], e.g. grid:36x18:0.08")
     fields = {}
@@ -426,7 +454,9 @@ def main(argv=None):
                     "come back and one host thread encodes them; device = colour conversion, DCT, quantiser and Huffman coding run on the GPU and only "
                     "the file's bytes come back (the same bytes).  device implies --encode device; not with --out NAME.png or NAME.y4m")
     ap.add_argument("--quality", type=int, default=None, help="of a .jpg or .avi: 1 ... 100, the usual scaling of the standard quantisation tables (90)")
-    ap.add_argument("--sky", default=None, help="grid[:MxP[:WIDTH]]: the analytic sky - a coloured celestial sphere with M meridians a turn and P cells "
+    ap.add_argument("--sky", default=None, help="stars:N[:SEED[:MIN_FOOTPRINT]]: N point stars, generated, binned on the GPU and lensed there - a star's "
+                    "brightness in a pixel goes as the inverse of the sky the pixel covers, down to MIN_FOOTPRINT (a power of two, 2^-16).  "
+                    "grid[:MxP[:WIDTH]]: the analytic sky - a coloured celestial sphere with M meridians a turn and P cells "
                     "between the poles (36x18), lines of WIDTH of a cell (0.08), antialiased exactly on the device at any magnification; no "
                     "image, no mips, no upload.  Not with --background or --mips")
     ap.add_argument("--mips", choices=["host", "device"], default=None, help="where the sky's mip slices are made: host = pack them on the CPU "
@@ -461,7 +491,7 @@ def main(argv=None):
     sky = None
     if a.sky is not None:
         if a.background is not None or a.mips is not None:
-            ap.error("--sky with --background / --mips: an analytic sky is no image and has no mip slices; give one or the other")
+            ap.error("--sky with --background / --mips: an analytic sky or a star field is no image and has no mip slices; give one or the other")
         try:
             sky = parse_sky(a.sky)
         except (ValueError, gra.GeodesicError) as e:

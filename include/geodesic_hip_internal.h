@@ -363,6 +363,105 @@ int gr_analytic_sky_image(const struct gr_analytic_sky* sky, int side, int width
 int gr_render_state_set_sky(gr_render_state* s, const struct gr_analytic_sky* sky_or_null);
 int gr_render_state_sky(const gr_render_state* s, struct gr_analytic_sky* out, int* is_set);
 
+/* ---- Star sky -------------------------------------------------------------------------------------------------------------------------
+ * Point stars lensed on the device.  A star is unresolved: its brightness in a pixel goes as the inverse of the solid angle the pixel's rays
+ * cover on the sky, which no sky image can carry.  A third shading kernel beside gr_render and gr_render_analytic (kernels/shading.hip:
+ * gr_render_stars) reads the same records and writes the same float4 frame, and gathers from a star catalogue that is built on the device
+ * (kernels/stars.hip, csrc/star_catalogue.cpp).  (Declared here for the reason "Analytic sky" gives; all of this is public.)
+ *
+ * A catalogue is n stars, 1 <= n <= 2^24.  Star s has a position (u_s, v_s) in the sky coordinates of render_data.tex_coord - u periodic in
+ * [0, 1), v in [0, 1] - and flux_s[3] >= 0: linear-light RGB per unit of (u, v) area.  Whoever makes the catalogue divides a star's flux per
+ * steradian by 2 pi^2 sin(pi v) once, on the host.  A catalogue has cells_u x cells_v cells, both powers of two from 16 to 4096 (0: the
+ * defaults, 1024 x 512).  Star s lies in cell (min(floor(u_s cells_u), cells_u - 1), min(floor(v_s cells_v), cells_v - 1)) - exact in fp32,
+ * the cell counts being powers of two; cell (i, j) has the number j cells_u + i.
+ *
+ * Definition.  A pixel has `self` with (u, v) = tex_coord (finite, in [0, 1]), `beside` and `below`, chosen exactly as gr_render and
+ * gr_render_analytic choose them.
+ *   1. footprint   hu = max((|du_x| + |du_y|) / 2, min_footprint), hv alike from dv_x, dv_y: the wrapped differences of "Analytic sky"
+ *                  step 1.  min_footprint is a field of the star sky, a power of two from 2^-20 to 2^-8, default 2^-16: the angular size
+ *                  below which a star is no longer a point - the cap on magnification and the knob against twinkling.  (The analytic sky's
+ *                  fixed 2^-14 is above an ordinary 4K pixel's half-size and would smear every star.)
+ *   2. regime      in fp32, every operation a single IEEE operation or a multiplication by a power of two, so that no contraction or
+ *                  reassociation changes it and a model repeats the decision bit for bit:
+ *                      r_u = 2 hu + 2^-22,  i0 = floor((u - r_u) cells_u),  i1 = floor((u + r_u) cells_u),
+ *                      r_v = 2 hv + 2^-22,  j0 = floor((v - r_v) cells_v),  j1 = floor((v + r_v) cells_v).
+ *                  NEAR if i1 - i0 <= 3 and j1 - j0 <= 3, otherwise FAR.
+ *   3. near        the stars themselves.  S = sum_s flux_s T(d_u / (2 hu)) T(d_v / (2 hv)) / (4 hu hv), T(x) = max(1 - |x|, 0);
+ *                  d_v = v_s - v, d_u = the difference u_s - u brought into half a turn either way, d - rint(d) (an fp32 evaluation forms
+ *                  it without rounding a position against the turn: (u_s - 1) - u for a star in front of the seam seen from behind it,
+ *                  u_s - (u - 1) the other way round).  The sum runs over the stars of the cells i0 ... i1 (taken modulo cells_u: the
+ *                  sphere closes in u) x max(j0, 0) ... min(j1, cells_v - 1) (clipped: nothing is mirrored across a pole), rows in
+ *                  ascending j, within a row cells in the order i0 ... i1, within a cell stars in ascending catalogue index.  The tent's
+ *                  half-width is the spacing of the neighbours: on a regular lattice of pixels the weights of a star add up to one, so
+ *                  no star falls between pixels.  The margin of 2^-22 makes the cells visited a superset of the tent's support whatever
+ *                  the rounding.
+ *   4. far         the stars as a glow.  S = (I(u + hu, v1) - I(u - hu, v1) - I(u + hu, v0) + I(u - hu, v0)) / (4 hu hv),
+ *                  v0 = max(v - hv, 0), v1 = min(v + hv, 1).  I is the bilinear interpolation of the catalogue's summed-area table: per
+ *                  channel, float64, (cells_v + 1) x (cells_u + 1), a zero first row and column, entry [j][i] the summed flux of the cells
+ *                  below i and j.  A cell's sum is taken in ascending catalogue index, the prefixes run along u, then along v.  For
+ *                  0 <= x <= 1: X = x cells_u, i = min(floor(X), cells_u - 1), a = X - i, likewise j, b from y and cells_v,
+ *                  I(x, y) = (1 - a)(1 - b) t[j][i] + a (1 - b) t[j][i + 1] + (1 - a) b t[j + 1][i] + a b t[j + 1][i + 1];
+ *                  I continues periodically in u: I(x + k, y) = I(x, y) + k I(1, y) for x in [0, 1) and whole k.  Evaluated in double on the
+ *                  device: few pixels are far, and the four terms cancel (over an empty stretch of sky they leave a residue of either
+ *                  sign, some 2^-53 of the table's total over the footprint's area).
+ *   5. colour      L = srgb_to_linear(background[side]) + S, alpha 1.  With the redshift feature apply_redshift(L, z_shift), then
+ *                  linear_to_srgb unless the program has a linear framebuffer; without it L under a linear framebuffer, linear_to_srgb(L)
+ *                  otherwise (gr_render's colour tail, entered in linear light).  Values above 1 stay in the float4 frame; the 8-bit and
+ *                  video sinks clamp, as they do for any frame.
+ *   6. side        self.side >= 1 takes the near catalogue and background[1], otherwise the far one and background[0] (background1 and
+ *                  background2 of gr_render).  A NULL catalogue on a side means S = 0 there.
+ *   7. black       a record with terminated != 1 gives exactly (0, 0, 0, 1). */
+typedef struct gr_star_catalogue gr_star_catalogue;
+struct gr_star_sky {
+    float min_footprint;       /* step 1: a power of two, 2^-20 ... 2^-8 */
+    float background[2][3];    /* [side][rgb], stored (sRGB) values in [0, 1] behind the stars; side as in gr_analytic_sky */
+};
+/* min_footprint 2^-16, both backgrounds black */
+int gr_star_sky_default(struct gr_star_sky* out);
+/* Uploads the 20 bytes a star (uv[2 n], flux[3 n]) to the program's device and builds everything else there: a cell histogram, an
+ * exclusive scan (cell_start[cells + 1]), a scatter, a per-cell ordering that leaves every cell's stars in ascending catalogue index, the
+ * stars' records in that order, the per-cell float64 sums and the two prefix passes.  The result is a function of the inputs alone: two
+ * builds give the same bytes.  The catalogue borrows the program (its set-up module holds the kernels) for the length of this call only,
+ * and lives on the program's device.  The ordering is a sorting network a cell: its cost grows as m log^2 m with the m stars of the
+ * fullest cell.  Refused before any device call, with GR_ERROR_INVALID_ARGUMENT and a message that names the function and the field: a
+ * NULL; n, cells_u or cells_v out of range or no power of two; a uv outside its range or not finite; a flux that is negative or not finite. */
+int gr_star_catalogue_create(gr_program* p, int n, const float* uv, const float* flux, int cells_u, int cells_v, gr_star_catalogue** out);
+void gr_star_catalogue_destroy(gr_star_catalogue* c);
+int gr_star_catalogue_info(const gr_star_catalogue* c, int* n, int* cells_u, int* cells_v);
+/* for tests: cell_start[cells_u cells_v + 1], order[n] (the catalogue indices as the device holds the stars, cell by cell) and
+ * table[3][cells_v + 1][cells_u + 1]; any of the three may be NULL */
+int gr_star_catalogue_download(const gr_star_catalogue* c, int* cell_start, int* order, double* table);
+/* A random field, on the host and in double: n stars uniform on the sphere from one splitmix64 stream.
+ *   next():  state += 0x9E3779B97F4A7C15 (state starts as seed); z = state; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *            z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^= z >> 31; x = (z >> 11) * 2^-53.
+ *   star s draws x1, x2, x3, x4 in that order (draws 4 s + 1 ... 4 s + 4 of the stream).
+ *   u = x1, stored as float (a float of 1 is stored as 0);  V = acos(1 - 2 x2) / pi, stored as float.
+ *   brightness: a power law of slope -5/2 above f0 = 2e-9 per steradian (the Euclidean counts N(> f) ~ f^-3/2), cut at 10^4 f0:
+ *            f = f0 min((1 - x3)^(-2/3), 1e4).
+ *   colour:  class k = min(floor(7 x4), 6) of O B A F G K M, linear RGB (0.61, 0.71, 1), (0.68, 0.77, 1), (0.80, 0.85, 1), (0.97, 0.96, 1),
+ *            (1, 0.92, 0.82), (1, 0.78, 0.56), (1, 0.58, 0.33).
+ *   flux[c] = f colour[k][c] / (2 pi^2 max(sin(pi V), 1e-3)), stored as float.
+ * out_uv[2 n], out_flux[3 n]; 1 <= n <= 2^24. */
+int gr_star_field_random(unsigned long long seed, int n, float* out_uv, float* out_flux);
+/* gr_render_analytic with the star sky in place of the analytic one: one launch of gr_render_stars over num_pixels records.  near / far:
+ * the catalogues of side 1 / side 0, either may be NULL (step 6), both must live on the program's device.  The launchers and the state's
+ * setter refuse, before any device call and by the function's and the field's name: a NULL sky, min_footprint out of range or no power
+ * of two, a background outside [0, 1] or not finite, a catalogue of another device, and what gr_render / gr_render_strips refuse. */
+int gr_render_stars(gr_program* p, void* stream, const void* render_data, const void* render_data_count, int num_pixels, void* out_rgba_f32,
+                    const struct gr_star_sky* sky, const gr_star_catalogue* near_or_null, const gr_star_catalogue* far_or_null, int width,
+                    int height, const void* cfg, const void* dfg);
+int gr_render_stars_strips(gr_program* p, void* stream, const void* render_data, void* out_rgba_f32, const struct gr_star_sky* sky,
+                           const gr_star_catalogue* near_or_null, const gr_star_catalogue* far_or_null, int width, int height, int block_rows,
+                           int strip_rank, int strip_count, int compact_out, const void* cfg, const void* dfg);
+/* The stars of a state's frames.  sky NULL (the default): every entry point is as it was, launch for launch.  With stars set, every frame
+ * of the state - on every path gr_render_state_set_sky lists - is shaded by gr_render_stars; it never shades inside the trace and reads
+ * no background image (background1, background2 may be NULL).  The catalogues are borrowed: they must outlive the state's frames.  A state
+ * that has an analytic sky refuses stars, and a state with stars refuses an analytic sky: composing the two is not defined.
+ * gr_render_state_stars: *is_set = 1 and the three in *out, *near, *far, or 0 and those untouched. */
+int gr_render_state_set_stars(gr_render_state* s, const struct gr_star_sky* sky_or_null, const gr_star_catalogue* near_or_null,
+                              const gr_star_catalogue* far_or_null);
+int gr_render_state_stars(const gr_render_state* s, struct gr_star_sky* out, const gr_star_catalogue** near, const gr_star_catalogue** far, int* is_set);
+
 /* ---- PNG frames -----------------------------------------------------------------------------------------------------------------------
  * A PNG encoder behind an RGBA8 frame that is already in device memory (gr_render_frame_rgba8, gr_deliver_accumulated(GR_FRAME_RGBA8),
  * participant 0's frame of gr_render_frame_tiled_as): filtering, histogram and bit-packing run on the device (kernels/png.hip, set-up
