@@ -130,12 +130,18 @@ class Transport(ctypes.Structure):
     _fields_ = [("user", c_void_p), ("group_begin", GROUP), ("group_end", GROUP), ("send", SEND), ("recv", RECV)]
 
 
+class GlareStruct(ctypes.Structure):
+    """struct gr_glare (include/geodesic_hip_internal.h, "Glare"): a PSF of a core plus up to four separable components"""
+    _fields_ = [("core", c_float), ("components", c_int), ("weight", c_float * 4), ("taps", c_int * 4), ("tap", (c_float * 129) * 4)]
+
+
 MODE_REFERENCE, MODE_FUSED = 0, 1
 FRAME_F32, FRAME_RGBA8 = 0, 1
 FRAME_YUV420, FRAME_YUV420P10 = 2, 3   # GR_FRAME_YUV420 / _YUV420P10: the video formats of gr_deliver_accumulated (include/geodesic_hip_internal.h)
 FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN, FILTER_MITCHELL = 0, 1, 2, 3   # GR_FILTER_*: the reconstruction filter of a state's frames (include/geodesic_hip_internal.h, "Filtered frames")
 FILTER_NAMES = {"box": FILTER_BOX, "tent": FILTER_TENT, "gaussian": FILTER_GAUSSIAN, "mitchell": FILTER_MITCHELL}
 FILTER_MAX_TAPS = 16
+GLARE_MAX_COMPONENTS, GLARE_MAX_TAPS = 4, 129   # GR_GLARE_*: the PSF of a state's frames (include/geodesic_hip_internal.h, "Glare")
 PNG_STREAM_LITERALS, PNG_STREAM_RUNS = 0, 1   # GR_PNG_STREAM_*: the stream kind of a device-made PNG (include/geodesic_hip_internal.h, "PNG frames")
 PNG_STREAM_NAMES = {"literals": PNG_STREAM_LITERALS, "runs": PNG_STREAM_RUNS}
 YUV420_I420, YUV420_NV12 = 0, 1   # GR_YUV420_*: the layouts of an 8-bit Y'CbCr 4:2:0 frame (include/geodesic_hip.h, "video frames")
@@ -350,6 +356,13 @@ _SIGNATURES = {
     "gr_resolve_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
     "gr_render_state_set_filter": (c_int, [c_void_p, c_int]),
     "gr_render_state_filter": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "gr_glare_gaussians": (c_int, [ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_int, ctypes.POINTER(GlareStruct)]),
+    "gr_glare_exposure": (c_int, [ctypes.POINTER(GlareStruct), c_float]),
+    "gr_glare_frame": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(GlareStruct), c_void_p]),
+    "gr_glare_scratch_bytes": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "gr_apply_glare": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, ctypes.POINTER(GlareStruct)]),
+    "gr_render_state_set_glare": (c_int, [c_void_p, ctypes.POINTER(GlareStruct)]),
+    "gr_render_state_glare": (c_int, [c_void_p, ctypes.POINTER(GlareStruct), ctypes.POINTER(c_int)]),
     "gr_analytic_sky_default": (c_int, [ctypes.POINTER(AnalyticSkyStruct)]),
     "gr_render_analytic": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(AnalyticSkyStruct), c_int, c_int, c_void_p, c_void_p]),
     "gr_render_analytic_strips": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(AnalyticSkyStruct), c_int, c_int, c_int, c_int, c_int, c_int,
@@ -418,5 +431,5 @@ def check(rc):
 from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, build_background,  # noqa: E402,F401
                        default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background, rgba8_to_yuv420,
                        yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes, accumulate_frame, filter_taps,
-                       filter_frame, PngEncoder, png_encode_bound, png_encode_host, JpegEncoder, jpeg_encode_bound, jpeg_encode_host, jpeg_quant_tables,
+                       filter_frame, glare_gaussians, glare_exposure, glare_frame, glare_scratch_bytes, apply_glare, PngEncoder, png_encode_bound, png_encode_host, JpegEncoder, jpeg_encode_bound, jpeg_encode_host, jpeg_quant_tables,
                        AviWriter, AnalyticSky, StarCatalogue, StarSky, star_field_random)

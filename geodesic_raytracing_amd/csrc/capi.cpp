@@ -72,19 +72,21 @@ const char* const KERNEL_NAMES[] = {
     "gr_get_geodesic_path", "gr_parallel_transport_quantity", "gr_handle_interpolating_geodesic", "gr_resolve_supersampled", "gr_present_rgba8",
     "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack",
     "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather", "gr_png_histogram_runs", "gr_png_pack_runs", "gr_render_analytic",
-    "gr_render_stars", "gr_stars_count", "gr_stars_scan", "gr_stars_scatter", "gr_stars_order", "gr_stars_gather", "gr_stars_sums", "gr_stars_prefix"};
+    "gr_render_stars", "gr_stars_count", "gr_stars_scan", "gr_stars_scatter", "gr_stars_order", "gr_stars_gather", "gr_stars_sums", "gr_stars_prefix",
+    "gr_glare_rows", "gr_glare_columns", "gr_glare_scale"};
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
 // filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and 8- and 10-bit Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
 // (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation - and the two integer kernels of the
 // PNG encoder (kernels/png.hip; each in two instances, one a stream kind) and the three of the JPEG encoder (kernels/jpeg.hip), which want
-// no part in it either - and the seven that build a star catalogue (kernels/stars.hip), whose sums are taken in the order they are written
+// no part in it either - and the seven that build a star catalogue (kernels/stars.hip), whose sums are taken in the order they are written -
+// and the three of the glare (kernels/glare.hip), which are held to a host definition bit for bit
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
            k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE || k == K_RESOLVE_FILTERED ||
            k == K_PNG_HISTOGRAM || k == K_PNG_PACK || k == K_JPEG_BLOCKS || k == K_JPEG_PACK || k == K_JPEG_GATHER || k == K_PNG_HISTOGRAM_RUNS ||
-           k == K_PNG_PACK_RUNS || (k >= K_STARS_COUNT && k <= K_STARS_PREFIX);
+           k == K_PNG_PACK_RUNS || (k >= K_STARS_COUNT && k <= K_STARS_PREFIX) || k == K_GLARE_ROWS || k == K_GLARE_COLUMNS || k == K_GLARE_SCALE;
 }
 
 namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files
@@ -1312,6 +1314,62 @@ int gr_resolve_filtered(gr_program* p, void* stream, const void* src, void* dst,
     std::copy(taps, taps + count, table.tap);
     void* args[] = {&src, &dst, &width, &height, &factor, &count, &table};
     return launch(p, K_RESOLVE_FILTERED, stream, blocks(width, 32), gy, 256, 1, args);
+}
+
+// ---- glare (kernels/glare.hip; geodesic_hip_internal.h, "Glare") -----------------------------------------------------------------------
+
+int gr_glare_scratch_bytes(int width, int height, size_t* bytes) {
+    if (!bytes) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_glare_scratch_bytes: null argument");
+    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_glare_scratch_bytes: a size below 1");
+    if ((long long)width * height > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_glare_scratch_bytes: more than 2^31 - 1 pixels");
+    *bytes = (size_t)width * (size_t)height * 4 * sizeof(float);   // h_k of the one component in flight
+    return GR_OK;
+}
+
+// No component: one elementwise launch.  Otherwise, per component, gr_glare_rows (256 pixels of a row a workgroup) from src into scratch
+// and gr_glare_columns (16 x 64 pixels a workgroup) from scratch into dst, which adds the component to core * src (the first) or to what
+// dst holds (the others); the component's taps - host memory - are copied into the argument block.  The grids are one-dimensional and at
+// most 2^20 workgroups: a workgroup walks the tiles with the grid's stride.  gr_glare_frame's refusals (imageio.cpp) and the buffers', all
+// before the first device call.
+int gr_apply_glare(gr_program* p, void* stream, const void* src, void* dst, void* scratch, size_t scratch_bytes, int width, int height,
+                   const gr_glare* g) {
+    const std::string who = "gr_apply_glare: ";
+    if (!src || !dst || !scratch || !g) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null argument");
+    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
+    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
+    if ((long long)width * height > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, who + "more than 2^31 - 1 pixels");
+    if (src == dst) return fail(GR_ERROR_INVALID_ARGUMENT, who + "src and dst are one buffer");
+    if (int rc = gr_internal_check_glare("gr_apply_glare", g)) return rc;
+    const size_t frame_bytes = (size_t)width * (size_t)height * 4 * sizeof(float);
+    if (scratch_bytes < frame_bytes)
+        return fail(GR_ERROR_INVALID_ARGUMENT, who + "scratch of " + std::to_string(scratch_bytes) + " bytes is too short (gr_glare_scratch_bytes: " + std::to_string(frame_bytes) + ")");
+    if ((uintptr_t)scratch % 16) return fail(GR_ERROR_INVALID_ARGUMENT, who + "scratch is not aligned to 16 bytes");
+    const auto overlap = [](const void* a, size_t na, const void* b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; };
+    if (overlap(src, frame_bytes, dst, frame_bytes) || overlap(src, frame_bytes, scratch, scratch_bytes) || overlap(dst, frame_bytes, scratch, scratch_bytes))
+        return fail(GR_ERROR_INVALID_ARGUMENT, who + "src, dst and scratch overlap");
+    const unsigned long long pixels = (unsigned long long)width * (unsigned long long)height;
+    const auto grid = [](unsigned long long tiles) { return (unsigned)std::min<unsigned long long>(tiles, 1ull << 20); };
+    if (g->components == 0) {
+        float scale = g->core;
+        unsigned long long count = pixels;
+        void* args[] = {&src, &dst, &count, &scale};
+        return launch(p, K_GLARE_SCALE, stream, grid((pixels + 255) / 256), 1, 256, 1, args);
+    }
+    const unsigned long long row_tiles = (((unsigned long long)width + 255) / 256) * (unsigned long long)height;
+    const unsigned long long column_tiles = (((unsigned long long)width + 15) / 16) * (((unsigned long long)height + 63) / 64);
+    for (int k = 0; k < g->components; k++) {
+        struct { float tap[GR_GLARE_MAX_TAPS]; } table = {};
+        std::copy(g->tap[k], g->tap[k] + g->taps[k], table.tap);
+        int count = g->taps[k], first = k == 0 ? 1 : 0;
+        float scale = g->core, weight = g->weight[k];
+        const void* rows = scratch;
+        const void* previous = first ? src : dst;
+        void* row_args[] = {&src, &scratch, &width, &height, &count, &table};
+        if (int rc = launch(p, K_GLARE_ROWS, stream, grid(row_tiles), 1, 256, 1, row_args)) return rc;
+        void* column_args[] = {&rows, &previous, &dst, &width, &height, &count, &scale, &weight, &first, &table};
+        if (int rc = launch(p, K_GLARE_COLUMNS, stream, grid(column_tiles), 1, 256, 1, column_args)) return rc;
+    }
+    return GR_OK;
 }
 
 // ---- the sky's mip slices on the device (kernels/background.hip) ------------------------------------

@@ -77,6 +77,14 @@ struct gr_render_state {
     // through gr_resolve_filtered into filtered_frame (float4[out_width * out_height], allocated with the first frame that is not refused)
     int filter = GR_FILTER_BOX;
     void* filtered_frame = nullptr;
+    // gr_render_state_set_glare (geodesic_hip_internal.h, "Glare"): with a glare the frame is resolved into filtered_frame (by the filter,
+    // or by the box at a factor above 1; a factor-1 box state's traced frame serves as it is), gr_apply_glare writes glare_frame (or the
+    // caller's float4 memory) through glare_scratch, and the sink reads glare_frame at factor 1.  All float4[out_width * out_height],
+    // allocated with the first frame that is not refused.
+    bool glare_set = false;
+    gr_glare glare{};
+    void* glare_frame = nullptr;
+    void* glare_scratch = nullptr;
     // gr_render_state_set_sky: with a sky every frame of the state is shaded by gr_render_analytic and reads no background; without
     // one (the default) by gr_render / gr_render_strips, launch for launch as before.  Shading only: the records do not depend on it.
     bool sky_set = false;
@@ -600,6 +608,23 @@ int gr_render_state_filter(const gr_render_state* s, int* filter) {
     return GR_OK;
 }
 
+int gr_render_state_set_glare(gr_render_state* s, const gr_glare* glare) {
+    if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_glare: null render state");
+    if (glare) {
+        GR_CHECK(gr_internal_check_glare("gr_render_state_set_glare", glare));
+        s->glare = *glare;
+    }
+    s->glare_set = glare != nullptr;
+    return GR_OK;
+}
+
+int gr_render_state_glare(const gr_render_state* s, gr_glare* out, int* is_set) {
+    if (!s || !out || !is_set) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_glare: null argument");
+    *is_set = s->glare_set ? 1 : 0;
+    if (s->glare_set) *out = s->glare;
+    return GR_OK;
+}
+
 int gr_render_state_set_sky(gr_render_state* s, const gr_analytic_sky* sky) {
     if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_sky: null render state");
     if (sky) {
@@ -656,7 +681,7 @@ void gr_render_state_destroy(gr_render_state* s) {
                                s->tetrad[3], s->rays_count_in, s->rays_adaptive_count, s->render_data_count, s->cfg, s->dfg,
                                s->attempts, s->rays_in, s->rays_adaptive, s->render_data, s->termination_buffer, s->tile_order,
                                s->tile_cost, s->lattice_rays, s->guessed[0], s->guessed[1], s->pending_list, s->block_cost, s->block_cost_before, s->ref_cost[0], s->ref_cost[1], s->ref_order, s->ref_sort_work, s->parking_records, s->parking_words,
-                               s->traced_frame, s->accumulation, s->filtered_frame};
+                               s->traced_frame, s->accumulation, s->filtered_frame, s->glare_frame, s->glare_scratch};
     for (auto& slot : s->pre) {
         if (slot.stream) { (void)hipStreamSynchronize(slot.stream); (void)hipStreamDestroy(slot.stream); }
         if (slot.ready) (void)hipEventDestroy(slot.ready);
@@ -1667,6 +1692,14 @@ static int refuse_output(const char* name, int format, int layout, const void* o
 // where a delivered frame goes: encoded as (format, layout) into out, or - accumulate - weight x the frame into the accumulation frame
 struct sink { int format, layout; void* out; bool accumulate; float weight; int first; };
 
+// the two frames a glare works in (gr_render_state: glare_frame, glare_scratch), on the state's device, which the caller has set
+static int allocate_glare_frames(gr_render_state* s) {
+    const size_t bytes = (size_t)s->out_width * s->out_height * 4 * sizeof(float);
+    if (!s->glare_frame) HIP_CHECK(hipMalloc(&s->glare_frame, bytes));
+    if (!s->glare_scratch) HIP_CHECK(hipMalloc(&s->glare_scratch, bytes));
+    return GR_OK;
+}
+
 // The delivery core (`name`: the entry point's, for its refusals).  What needs no device is refused first; nothing is allocated for a call that is refused.
 static int deliver_frame(const char* name, const sink& to, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream,
                          const gr_camera* camera, const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1,
@@ -1682,8 +1715,14 @@ static int deliver_frame(const char* name, const sink& to, gr_render_state* s, g
     if (filtered && opt.strip_count > 1)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": a state with a filter renders whole frames only (strip_count > 1): a filter "
                                                                                 "wider than a pixel reads across strip borders").c_str());
+    // a glare is applied to a delivered frame; a sub-frame is accumulated without it and gr_deliver_accumulated applies it to the sum
+    const bool glared = s->glare_set && !to.accumulate;
+    if (s->glare_set && opt.strip_count > 1)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": a state with a glare renders whole frames only (strip_count > 1): the PSF "
+                                                                                "reads across strip borders").c_str());
     GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, to.accumulate ? s : to.out));   // (s: any non-NULL out)
-    const bool allocates = !s->traced_frame || (to.accumulate && !s->accumulation) || (filtered && !s->filtered_frame);
+    const bool resolves = filtered || (glared && factor > 1);   // into filtered_frame: by the filter, or by the box in front of a glare
+    const bool allocates = !s->traced_frame || (to.accumulate && !s->accumulation) || (resolves && !s->filtered_frame) || (glared && (!s->glare_frame || !s->glare_scratch));
     if (allocates) HIP_CHECK(hipSetDevice(s->device));   // (render_traced_frame sets it for everything else)
     if (!s->traced_frame) {   // a factor-1 state's first frame that does not go straight to the caller
         HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
@@ -1695,8 +1734,9 @@ static int deliver_frame(const char* name, const sink& to, gr_render_state* s, g
     int tap_count = 0;
     if (filtered) {   // the frame a state with a filter resolves into (geodesic_hip_internal.h, "Filtered frames"): allocated once, freed with the state
         GR_CHECK(gr_filter_taps(s->filter, factor, taps, &tap_count));
-        if (!s->filtered_frame) HIP_CHECK(hipMalloc(&s->filtered_frame, (size_t)w * h * 4 * sizeof(float)));
     }
+    if (resolves && !s->filtered_frame) HIP_CHECK(hipMalloc(&s->filtered_frame, (size_t)w * h * 4 * sizeof(float)));
+    if (glared) GR_CHECK(allocate_glare_frames(s));
     if (to.accumulate && to.first) s->accumulated = 0;   // (a sub-frame that fails below leaves nothing to deliver)
     GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
                                  s->traced_frame, &traced));
@@ -1704,11 +1744,22 @@ static int deliver_frame(const char* name, const sink& to, gr_render_state* s, g
     const bool timed = opt.time_kernels == 1;
     if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
     // a state with a filter: the filtered frame - straight into the caller's memory where that is float4 - and the sink from it at factor 1
+    if (glared) {
+        // a state with a glare: the resolved frame at the output size, the glare of it - straight into the caller's memory where that is
+        // float4 - and the sink from the glare's frame at factor 1
+        if (filtered) GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, s->filtered_frame, w, h, factor, taps, tap_count));
+        else if (factor > 1) GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, s->filtered_frame, w, h, factor, 0, 0, 1, 0));
+        const void* resolved = resolves ? s->filtered_frame : s->traced_frame;
+        const bool into_out = to.format == GR_FRAME_F32;
+        GR_CHECK(gr_apply_glare(p, stream, resolved, into_out ? to.out : s->glare_frame, s->glare_scratch, (size_t)w * h * 4 * sizeof(float), w, h, &s->glare));
+        if (!into_out) GR_CHECK(encode_frame(p, stream, to.format, to.layout, s->glare_frame, w, h, 1, nullptr, to.out));
+    } else {
     const bool direct = filtered && !to.accumulate && to.format == GR_FRAME_F32;
     if (filtered) GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, direct ? to.out : s->filtered_frame, w, h, factor, taps, tap_count));
     const void* src = filtered ? s->filtered_frame : s->traced_frame;
     if (to.accumulate) GR_CHECK(gr_shutter_accumulate(p, stream, src, s->accumulation, w, h, filtered ? 1 : factor, to.weight, to.first));
     else if (!direct) GR_CHECK(encode_frame(p, stream, to.format, to.layout, src, w, h, filtered ? 1 : factor, strips ? &opt : nullptr, to.out));
+    }
     if (timed) {
         HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
         s->resolve_timed = true;
@@ -1728,8 +1779,8 @@ int gr_internal_render_frame_as(int format, int layout, gr_render_state* s, gr_p
         GR_CHECK(refuse_output(f.entry, format, layout, out, s, options ? options->strip_count : 1));
     }
     if (s) s->resolve_timed = false;
-    // (a factor-1 box state's float4 frame goes straight to the caller; out == NULL stops after the records: nothing was shaded, nothing to resolve)
-    if (format == GR_FRAME_F32 && (!s || (s->supersample == 1 && s->filter == GR_FILTER_BOX) || !out))
+    // (a factor-1 box state's float4 frame goes straight to the caller unless a glare is set; out == NULL stops after the records: nothing was shaded, nothing to resolve)
+    if (format == GR_FRAME_F32 && (!s || (s->supersample == 1 && s->filter == GR_FILTER_BOX && !s->glare_set) || !out))
         return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out, options);
     return deliver_frame(f.entry, sink{format, layout, out, false, 0.f, 0}, s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2,
                          bg_width, bg_height, bg_levels, options);
@@ -1792,6 +1843,13 @@ int gr_deliver_accumulated(gr_render_state* s, gr_program* p, void* stream, int 
     if (!s->accumulated || !s->accumulation)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: the state holds no accumulation (gr_render_subframe first)");
     HIP_CHECK(hipSetDevice(s->device));
+    if (s->glare_set) {   // the glare of the accumulation - into the state's own frame, or the caller's float4 memory -, then the encode of that
+        const int w = s->out_width, h = s->out_height;
+        GR_CHECK(allocate_glare_frames(s));
+        const bool into_out = format == GR_FRAME_F32;
+        GR_CHECK(gr_apply_glare(p, stream, s->accumulation, into_out ? out : s->glare_frame, s->glare_scratch, (size_t)w * h * 4 * sizeof(float), w, h, &s->glare));
+        return into_out ? GR_OK : encode_frame(p, stream, format, layout, s->glare_frame, w, h, 1, nullptr, out);
+    }
     return encode_frame(p, stream, format, layout, s->accumulation, s->out_width, s->out_height, 1, nullptr, out);
 }
 

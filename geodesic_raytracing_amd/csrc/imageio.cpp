@@ -627,4 +627,124 @@ GR_NO_CONTRACTION int gr_filter_frame(const float* src, int width, int height, i
     return GR_OK;
 }
 
+// ---- glare: a PSF and an exposure on the resolved frame - the host statement (geodesic_hip_internal.h, "Glare"; kernels/glare.hip's launches
+// behind gr_apply_glare are held to gr_glare_frame bit for bit).
+// what gr_glare_frame, gr_apply_glare (capi.cpp) and gr_render_state_set_glare (frame.cpp) refuse about a glare, under the caller's name and by the field's
+int gr_internal_check_glare(const char* who, const gr_glare* g) {
+    std::string wrong;
+    if (!std::isfinite(g->core)) wrong = "core is not finite";
+    else if (g->components < 0 || g->components > GR_GLARE_MAX_COMPONENTS) wrong = "components " + std::to_string(g->components) + " (0 to 4)";
+    for (int k = 0; wrong.empty() && k < g->components; k++) {
+        const std::string at = "[" + std::to_string(k) + "]";
+        if (!std::isfinite(g->weight[k])) wrong = "weight" + at + " is not finite";
+        else if (g->taps[k] < 1 || g->taps[k] > GR_GLARE_MAX_TAPS || g->taps[k] % 2 == 0) wrong = "taps" + at + " = " + std::to_string(g->taps[k]) + " (odd, 1 to 129)";
+        for (int t = 0; wrong.empty() && t < g->taps[k]; t++)
+            if (!std::isfinite(g->tap[k][t])) wrong = "tap" + at + "[" + std::to_string(t) + "] is not finite";
+    }
+    return wrong.empty() ? GR_OK : gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(who) + ": " + wrong).c_str());
+}
+
+int gr_glare_gaussians(const float* sigma, const float* weight, int count, gr_glare* out) {
+    const std::string who = "gr_glare_gaussians: ";
+    if (!sigma || !weight || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "null argument").c_str());
+    if (count < 0 || count > GR_GLARE_MAX_COMPONENTS) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "count " + std::to_string(count) + " (0 to 4)").c_str());
+    double total = 0.0;
+    for (int k = 0; k < count; k++) {
+        const std::string at = "[" + std::to_string(k) + "]";
+        if (!std::isfinite(sigma[k]) || !(sigma[k] > 0.f) || sigma[k] > 64.f)
+            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "sigma" + at + " is not in (0, 64]").c_str());
+        if (!std::isfinite(weight[k]) || weight[k] < 0.f || weight[k] > 1.f)
+            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "weight" + at + " is not in [0, 1]").c_str());
+        total += (double)weight[k];
+    }
+    if (total > 1.0) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "the weights sum to more than 1").c_str());
+    gr_glare made;
+    std::memset(&made, 0, sizeof made);
+    made.core = (float)(1.0 - total);
+    made.components = count;
+    for (int k = 0; k < count; k++) {
+        const double s = (double)sigma[k];
+        const int radius = std::min((int)std::ceil(3.0 * s), (GR_GLARE_MAX_TAPS - 1) / 2);
+        const int n = 2 * radius + 1;
+        double value[GR_GLARE_MAX_TAPS], sum = 0.0;
+        for (int t = 0; t < n; t++) {
+            const double d = (double)(t - radius);
+            value[t] = std::exp(-d * d / (2.0 * s * s));
+            sum += value[t];
+        }
+        for (int t = 0; t < n; t++) made.tap[k][t] = (float)(value[t] / sum);
+        made.taps[k] = n;
+        made.weight[k] = weight[k];
+    }
+    *out = made;
+    return GR_OK;
+}
+
+GR_NO_CONTRACTION int gr_glare_exposure(gr_glare* g, float stops) {
+    if (!g) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_glare_exposure: null argument");
+    if (!std::isfinite(stops) || stops < -32.f || stops > 32.f)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_glare_exposure: stops is not in -32 to 32");
+    const float gain = (float)std::exp2((double)stops);
+    g->core = g->core * gain;
+    for (int k = 0; k < GR_GLARE_MAX_COMPONENTS; k++) g->weight[k] = g->weight[k] * gain;
+    return GR_OK;
+}
+
+// Per component: the rows pass into an intermediate of width x height x 3 floats, rounded to fp32, the columns pass, then the component's
+// step of the combine into dst; every product a float object of its own and the function compiled without contraction, as gr_filter_frame is.
+GR_NO_CONTRACTION int gr_glare_frame(const float* src, int width, int height, const gr_glare* g, float* dst) {
+    const std::string who = "gr_glare_frame: ";
+    if (!src || !g || !dst) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "null argument").c_str());
+    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "a size below 1").c_str());
+    if (src == dst) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "src and dst are one buffer").c_str());
+    GR_CHECK(gr_internal_check_glare("gr_glare_frame", g));
+    const long long w = width, h = height;
+    const size_t pixels = (size_t)w * (size_t)h;
+    std::vector<float> rows;
+    try {
+        if (g->components) rows.resize(pixels * 3);
+    } catch (const std::exception&) {
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "no memory for the intermediate frame").c_str());
+    }
+    for (size_t i = 0; i < pixels; i++) {
+        for (int c = 0; c < 3; c++) dst[4 * i + c] = g->core * src[4 * i + c];
+        dst[4 * i + 3] = src[4 * i + 3];
+    }
+    for (int k = 0; k < g->components; k++) {
+        const int n = g->taps[k];
+        const long long radius = (n - 1) / 2;
+        const float* tap = g->tap[k];
+        for (long long y = 0; y < h; y++)
+            for (long long X = 0; X < w; X++) {
+                float* o = &rows[((size_t)y * w + X) * 3];
+                for (int t = 0; t < n; t++) {
+                    const long long cx = std::min(std::max(X - radius + t, 0ll), w - 1);
+                    const float* s = src + ((size_t)y * w + cx) * 4;
+                    for (int c = 0; c < 3; c++) {
+                        const float product = tap[t] * s[c];
+                        o[c] = t ? o[c] + product : product;
+                    }
+                }
+            }
+        for (long long Y = 0; Y < h; Y++)
+            for (long long X = 0; X < w; X++) {
+                float column[3];
+                for (int t = 0; t < n; t++) {
+                    const long long cy = std::min(std::max(Y - radius + t, 0ll), h - 1);
+                    const float* r = &rows[((size_t)cy * w + X) * 3];
+                    for (int c = 0; c < 3; c++) {
+                        const float product = tap[t] * r[c];
+                        column[c] = t ? column[c] + product : product;
+                    }
+                }
+                float* o = dst + ((size_t)Y * w + X) * 4;
+                for (int c = 0; c < 3; c++) {
+                    const float product = g->weight[k] * column[c];
+                    o[c] = o[c] + product;
+                }
+            }
+    }
+    return GR_OK;
+}
+
 }  // extern "C"

@@ -289,6 +289,13 @@ int next_slot(gr_tiled* t, hipStream_t stream, frame_slot** out) {
     return GR_OK;
 }
 
+// whether the state's frames go through a PSF (gr_render_state_set_glare): such a state renders whole frames only
+bool state_has_glare(const gr_render_state* s) {
+    auto glare = std::make_unique<gr_glare>();
+    int is_set = 0;
+    return gr_render_state_glare(s, glare.get(), &is_set) == GR_OK && is_set;
+}
+
 }  // namespace
 
 extern "C" {
@@ -568,6 +575,8 @@ int gr_render_frame_tiled_as(gr_tiled* t, gr_render_state* s, gr_program* p, con
         gr_render_state_filter(s, &filter);
         if (filter != GR_FILTER_BOX)
             return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled_as: a render state with a filter (gr_render_state_set_filter) renders whole frames only; a split frame takes GR_FILTER_BOX");
+        if (state_has_glare(s))
+            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled_as: a render state with a glare (gr_render_state_set_glare) renders whole frames only: the PSF reads across strip borders");
     }
     {   // (the staging buffers and the blocks' places in the root's frame are those of the participant's frame size: the size of the
         // state's frames, which a supersampled state traces at factor x that)
@@ -632,6 +641,8 @@ int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const 
     gr_render_state_filter(s, &filter);
     if (filter != GR_FILTER_BOX)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a render state with a filter (gr_render_state_set_filter) renders whole frames only; a split frame takes GR_FILTER_BOX");
+    if (state_has_glare(s))
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a render state with a glare (gr_render_state_set_glare) renders whole frames only: the PSF reads across strip borders");
     if (factor != 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a supersampled render state (gr_render_state_create_supersampled) renders its split frames through gr_render_frame_tiled_as; this entry point takes a state of factor 1");
     return gr_render_frame_tiled_as(t, s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
                                     frame_on_root, options, rotation, GR_FRAME_F32);

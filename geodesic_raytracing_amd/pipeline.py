@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from . import (AnalyticSkyStruct, StarSkyStruct, Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, FRAME_YUV420, FRAME_YUV420P10, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
+from . import (AnalyticSkyStruct, GlareStruct, GLARE_MAX_COMPONENTS, StarSkyStruct, Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, FRAME_YUV420, FRAME_YUV420P10, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
                c_size_t, c_void_p, check, lib)
 
 LIGHTRAY_DTYPE = np.dtype([("position", "<f4", 4), ("velocity", "<f4", 4), ("initial_quat", "<f4", 4),
@@ -638,14 +638,16 @@ class StarSky:
 class RenderState:
     """Per-frame device buffers + the frame sequence (render_state.hpp:97-197, main.cpp:2244-2526)."""
 
-    def __init__(self, width, height, device=0, supersample=1, filter=FILTER_BOX, sky=None, stars=None):
+    def __init__(self, width, height, device=0, supersample=1, filter=FILTER_BOX, sky=None, stars=None, glare=None):
         """supersample = f > 1 (gr_render_state_create_supersampled; 2, 3 or 4): frames are still width x height, traced at f x that per
         axis and box-averaged on the device (box_resolve says what that means).  Everything else about the state - buffer(), the
         prepass grid, tile history - is of traced_size.  filter (gr_render_state_set_filter): FILTER_BOX, or FILTER_TENT / _GAUSSIAN /
         _MITCHELL or their names - every frame of the state is then filter_frame of the traced frame with filter_taps' table, at
         factor 1 too, whole frames only.  sky (gr_render_state_set_sky): an AnalyticSky - every frame of the state is then shaded from
         it by gr_render_analytic, and render() needs no background.  stars (gr_render_state_set_stars): (StarSky, near StarCatalogue or None, far
-        StarCatalogue or None) - every frame is shaded by gr_render_stars from the catalogues; not together with sky."""
+        StarCatalogue or None) - every frame is shaded by gr_render_stars from the catalogues; not together with sky.  glare
+        (gr_render_state_set_glare): a GlareStruct (glare_gaussians, glare_exposure) - every frame delivered is then glare_frame of the
+        frame the state would have delivered as float4, applied on the device before the encode; whole frames only."""
         self.width, self.height, self.device = width, height, device
         self.handle = c_void_p()
         if supersample == 1:
@@ -661,6 +663,19 @@ class RenderState:
             self.set_sky(sky)
         if stars is not None:
             self.set_stars(*stars)
+        if glare is not None:
+            self.set_glare(glare)
+
+    def set_glare(self, glare):
+        """the PSF and exposure of the frames from here on (a GlareStruct), or None: frames as they were"""
+        check(lib.gr_render_state_set_glare(self.handle, ctypes.byref(glare) if glare is not None else None))
+
+    @property
+    def glare(self):
+        """the state's GlareStruct, or None"""
+        out, is_set = GlareStruct(), c_int()
+        check(lib.gr_render_state_glare(self.handle, ctypes.byref(out), ctypes.byref(is_set)))
+        return out if is_set.value else None
 
     def set_stars(self, star_sky, near=None, far=None):
         """the stars of the frames from here on: a StarSky and the catalogues of the near and the far side (either may be None: no stars
@@ -950,6 +965,51 @@ def filter_frame(frame, factor, taps):
     check(lib.gr_filter_frame(frame.ctypes.data_as(c_void_p), out.shape[1], out.shape[0], f, taps.ctypes.data_as(c_void_p), taps.size,
                               out.ctypes.data_as(c_void_p)))
     return out
+
+
+def glare_gaussians(sigma=(), weight=()):
+    """The named PSF (gr_glare_gaussians): up to four Gaussians of `sigma` output pixels and `weight` in [0, 1] -> a GlareStruct with
+    n = 2 min(ceil(3 sigma), 64) + 1 taps a component, normalised in float64 and rounded once, and core = 1 - the sum of the weights.  None
+    given: core 1 and no component, the identity."""
+    sigma, weight = np.atleast_1d(np.asarray(sigma, dtype=np.float32)), np.atleast_1d(np.asarray(weight, dtype=np.float32))
+    if sigma.ndim != 1 or sigma.shape != weight.shape:
+        raise ValueError("glare_gaussians: as many sigmas as weights")
+    room = max(len(sigma), GLARE_MAX_COMPONENTS)   # (a count above 4 is the library's to refuse)
+    s, w, out = (c_float * room)(*sigma), (c_float * room)(*weight), GlareStruct()
+    check(lib.gr_glare_gaussians(s, w, len(sigma), ctypes.byref(out)))
+    return out
+
+
+def glare_exposure(glare, stops):
+    """gr_glare_exposure: the core and the weights of `glare` times 2^stops (-32 ... 32), in place; returns it"""
+    check(lib.gr_glare_exposure(ctypes.byref(glare), float(stops)))
+    return glare
+
+
+def glare_frame(frame, glare):
+    """The host statement of the glare (gr_glare_frame): float32 [H, W, 4] -> [H, W, 4]; per component the rows pass, the columns pass
+    and weight x that added to core x the frame, tap t on the sample at offset t - R, samples past an edge taken from the edge; every
+    product and every sum one rounded float32 operation in the order written; alpha passes bit for bit.  What a RenderState with a glare
+    delivers, bit for bit, of the frame it delivers without."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.ndim != 3 or frame.shape[2] != 4 or not frame.size:
+        raise ValueError(f"glare_frame: a frame of shape {frame.shape} is not [H, W, 4]")
+    out = np.empty_like(frame)
+    check(lib.gr_glare_frame(frame.ctypes.data_as(c_void_p), frame.shape[1], frame.shape[0], ctypes.byref(glare), out.ctypes.data_as(c_void_p)))
+    return out
+
+
+def glare_scratch_bytes(width, height):
+    """the scratch apply_glare needs for a frame of that size (gr_glare_scratch_bytes)"""
+    n = c_size_t()
+    check(lib.gr_glare_scratch_bytes(int(width), int(height), ctypes.byref(n)))
+    return n.value
+
+
+def apply_glare(program, src_ptr, dst_ptr, scratch_ptr, scratch_bytes, width, height, glare, stream=None):
+    """glare_frame on the program's device (gr_apply_glare), bit for bit, asynchronous on `stream`: src, dst and scratch are device
+    pointers to float4[width * height] frames (scratch: glare_scratch_bytes, aligned to 16) that do not overlap"""
+    check(lib.gr_apply_glare(program.handle, stream, src_ptr, dst_ptr, scratch_ptr, int(scratch_bytes), int(width), int(height), ctypes.byref(glare)))
 
 
 def yuv420p10_bytes(width, height):

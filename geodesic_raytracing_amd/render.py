@@ -26,6 +26,8 @@
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --jpeg device --quality 90 --out kerr_4k.jpg
     # ... and the pan as one Motion-JPEG file that every player opens, an order of magnitude smaller than the .y4m
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --fps 30000/1001 --jpeg device --out pan.avi
+    # lensed point stars with glare: a sharp core inside two Gaussian halos and one stop more exposure, so that a star of 400 outshines a star of 1 in 8 bits
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --sky stars:200000:7 --glare 0.06:1.5,0.03:10 --exposure 1 --out stars.png
 """
 import argparse
 import ctypes
@@ -150,6 +152,31 @@ def camera_path_at(position, quat, position_to=None, quat_to=None, frames=1, tim
     return poses
 
 
+def glare_of(glare=None, exposure=0.0):
+    """render()'s two arguments as one gra.GlareStruct of its own, or None where they ask for nothing"""
+    if glare is None and not exposure:
+        return None
+    if isinstance(glare, gra.GlareStruct):
+        made = gra.GlareStruct.from_buffer_copy(glare)
+    else:
+        pairs = list(glare or [])
+        made = gra.glare_gaussians([sigma for _, sigma in pairs], [weight for weight, _ in pairs])
+    return gra.glare_exposure(made, exposure) if exposure else made
+
+
+def parse_glare(text):
+    """'W:SIGMA[,W:SIGMA...]' -> [(weight, sigma)], at most four pairs; ValueError otherwise"""
+    pairs = []
+    for part in text.split(","):
+        fields = part.split(":")
+        if len(fields) != 2:
+            raise ValueError("W:SIGMA[,W:SIGMA...], e.g. 0.06:1.5,0.03:10")
+        pairs.append((float(fields[0]), float(fields[1])))
+    if len(pairs) > gra.GLARE_MAX_COMPONENTS:
+        raise ValueError(f"{len(pairs)} components (at most {gra.GLARE_MAX_COMPONENTS})")
+    return pairs
+
+
 def checked_png_stream(who, png, png_stream):
     """the PNG stream kind as gra.PNG_STREAM_*; a kind other than literals is a property of device-made files"""
     if png_stream not in gra.PNG_STREAM_NAMES and png_stream not in gra.PNG_STREAM_NAMES.values():
@@ -163,8 +190,12 @@ def checked_png_stream(who, png, png_stream):
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
            parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box",
-           png="host", jpeg=None, quality=90, png_stream="literals", sky=None):
-    """sky: a gra.AnalyticSky - every frame is shaded from it in closed form (RenderState(sky=)) - or a StarField - point stars, lensed on the
+           png="host", jpeg=None, quality=90, png_stream="literals", sky=None, glare=None, exposure=0.0):
+    """glare: a gra.GlareStruct (pipeline.glare_gaussians) or [(weight, sigma)], up to four Gaussians of sigma output pixels - every frame
+    goes through that point-spread function on the device, in linear light, after the resolve and before any encode (RenderState(glare=):
+    pipeline.glare_frame of the frame rendered without it, bit for bit): a star far above 1 keeps a halo in an 8-bit file.  exposure:
+    stops, -32 ... 32 - a gain of 2^exposure on the same stage (pipeline.glare_exposure); works alone.  Whole frames only.
+    sky: a gra.AnalyticSky - every frame is shaded from it in closed form (RenderState(sky=)) - or a StarField - point stars, lensed on the
     device (RenderState(stars=)); `background` and `mips` are then unused.
     Returns the linear-light float32 frame [H, W, 4]; with geodesic_speed (camera on its own timelike geodesic,
     main.cpp:2675-2760) a list of frames, one per entry of geodesic_times (proper time along the path).  supersample = f (2, 3, 4): traced
@@ -224,7 +255,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     manager = ProgramManager(metric, device, feats, cfg_values)
     program = manager.current(wait=wait_for_static)
     stars = sky.on(program) if isinstance(sky, StarField) else None   # (point stars: a catalogue built on this device, the same on both sides)
-    state = gra.RenderState(width, height, device, supersample=supersample, filter=filter, sky=sky if stars is None else None, stars=stars)
+    state = gra.RenderState(width, height, device, supersample=supersample, filter=filter, sky=sky if stars is None else None, stars=stars,
+                            glare=glare_of(glare, exposure))
     if sky is None:
         rgba = background if background is not None else gra.synthetic_background(2048, 1024)
         if mips == "device":
@@ -467,6 +499,11 @@ def main(argv=None):
                     "(radius 1 pixel), gaussian or mitchell (Mitchell-Netravali, B = C = 1/3; both radius 2) - wider separable filters that fold "
                     "less of what the extra rays resolved back as aliasing.  Works at --supersample 1 too (gaussian and mitchell are a mild "
                     "post-filter there, tent changes nothing).  Not with --devices")
+    ap.add_argument("--glare", default=None, metavar="W:SIGMA[,W:SIGMA...]", help="a point-spread function applied on the device in linear light, after the "
+                    "resolve and before any encode: up to four Gaussians of SIGMA output pixels, each holding the share W of a pixel's light (the "
+                    "core keeps the rest), e.g. 0.06:1.5,0.03:10 - a star far above 1 keeps a halo in an 8-bit file.  Not with --devices")
+    ap.add_argument("--exposure", type=float, default=None, metavar="STOPS", help="a gain of 2^STOPS on the same stage, -32 ... 32; works alone.  Not "
+                    "with --devices")
     ap.add_argument("--devices", default=None, help="0,1,2,3: deal the rows of every frame to these GPUs (one process, peer copies; a device may "
                     "repeat); each traces, resolves and - with --encode device - encodes its share, the share rotating over --frames")
     ap.add_argument("--fps", default="24", help="frame rate of a .y4m or .avi file: N or N/D (24; 30000/1001)")
@@ -533,6 +570,15 @@ def main(argv=None):
     if a.filter != "box" and a.devices is not None:
         ap.error(f"--filter {a.filter} with --devices: a filter wider than a pixel reads across the strips of a split frame; render filtered "
                  "frames on one device (a split frame takes --filter box)")
+    glare = None
+    if a.glare is not None or a.exposure is not None:
+        if a.devices is not None:
+            ap.error(f"{'--glare' if a.glare is not None else '--exposure'} with --devices: the point-spread function reads across the strips of a split "
+                     "frame, and the gain is a part of that stage; render such frames on one device")
+        try:
+            glare = glare_of(parse_glare(a.glare) if a.glare is not None else [], a.exposure or 0.0) or gra.glare_gaussians()
+        except (ValueError, gra.GeodesicError) as e:
+            ap.error(f"--glare {a.glare} --exposure {a.exposure}: {e}")
     if video and a.devices is not None:
         ap.error("--out NAME.y4m with --devices: a split frame travels as float4 or RGBA8, not as 4:2:0 planes; render the video on one device")
     if (a.camera_to or a.quat_to) and a.geodesic_speed:
@@ -586,7 +632,7 @@ def main(argv=None):
                     geodesic_times=[a.geodesic_time + float(t) * a.geodesic_dt for t in moments] if samples else times,
                     parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
                     rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples,
-                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream, sky=sky)
+                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream, sky=sky, glare=glare)
     if speed is None and cameras is None:
         result = [result]
     if video:

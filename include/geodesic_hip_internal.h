@@ -462,6 +462,76 @@ int gr_render_state_set_stars(gr_render_state* s, const struct gr_star_sky* sky_
                               const gr_star_catalogue* far_or_null);
 int gr_render_state_stars(const gr_render_state* s, struct gr_star_sky* out, const gr_star_catalogue** near, const gr_star_catalogue** far, int* is_set);
 
+/* ---- Glare ------------------------------------------------------------------------------------------------------------------------------
+ * A point-spread function and an exposure, applied to the resolved frame on the device in linear light, between the resolve (box or
+ * filter) and the sink.  A lensed point star reaches hundreds (Star sky, step 5) and the 8-bit and video sinks clamp at 1: without this
+ * stage a star of brightness 1 and one of 400 are the same white pixel in every file.  A camera, an eye or a telescope shows a bright
+ * point as a sharp core inside a halo - the frame convolved with a PSF - and that is how a bright star reads as bright in 8 bits.  The
+ * PSF is a core plus up to four separable components; a plain gain is the PSF with no components.  (Declared here and not in
+ * geodesic_hip.h only because the contract header keeps to 80 names and 350 lines, so that header gains nothing; all of this is public.)
+ *
+ * Definition.  s is the source, float4, W x H.  For the channels r, g and b, for every component k in ascending order, with n_k taps and
+ * R_k = (n_k - 1) / 2:
+ *   h_k(y, X) = acc after: acc = tap_k[0] * s(y, cx(X,0));    for t = 1 ... n_k-1: acc = acc + (tap_k[t] * s(y, cx(X,t)))     every row y
+ *   g_k(Y, X) = acc after: acc = tap_k[0] * h_k(cy(Y,0), X);  for t = 1 ... n_k-1: acc = acc + (tap_k[t] * h_k(cy(Y,t), X))
+ *   cx(X,t) = clamp(X - R_k + t, 0, W - 1)      cy(Y,t) = clamp(Y - R_k + t, 0, H - 1)
+ * then
+ *   out(Y, X) = acc after: acc = core * s(Y, X);  for k = 0 ... K-1: acc = acc + (weight[k] * g_k(Y, X))
+ * Every product and every sum is one fp32 operation rounded to nearest even - NEVER a fused multiply-add - in the order written, and h_k
+ * and g_k are rounded to fp32.  Tap t multiplies the sample at offset t - R_k: the correlation form, as in "Filtered frames", so a single
+ * bright pixel comes out as the table reversed.  A sample past an edge is the edge sample, so a uniform frame stays uniform.  Alpha is
+ * not convolved: out.w is s.w, bit for bit.  The first term is core * s and not 0 + ...: with core 1.0f and K = 0 every r, g and b value
+ * passes unchanged, the sign of a zero included.  Taps and weights of 0 are not skipped.  NaN and infinity propagate as IEEE arithmetic has
+ * them: a NaN pixel spreads over the whole footprint of the PSF (a cross of 2 R_k + 1 rows and columns becomes a square of NaN), and an
+ * infinity next to a tap of 0 is a NaN. */
+#define GR_GLARE_MAX_COMPONENTS 4
+#define GR_GLARE_MAX_TAPS 129
+struct gr_glare {
+    float core;                                   /* finite */
+    int components;                               /* K, 0 ... 4 */
+    float weight[GR_GLARE_MAX_COMPONENTS];        /* finite */
+    int taps[GR_GLARE_MAX_COMPONENTS];            /* n_k: odd, 1 ... 129; R_k = (n_k - 1) / 2 */
+    float tap[GR_GLARE_MAX_COMPONENTS][GR_GLARE_MAX_TAPS];   /* finite; the first n_k of a row are read */
+};
+/* Every function below refuses, before any device call and before it writes anything, with GR_ERROR_INVALID_ARGUMENT and a message that
+ * names the function and the field.  Of a struct gr_glare only core, components and the first `components` weights, counts and rows are
+ * looked at. */
+/* The named PSF: `count` Gaussians, 0 ... 4.  Component k has R_k = min(ceil(3 sigma_k), 64) and the taps (float)(exp(-d^2 / (2 sigma_k^2)) /
+ * sum), d = t - R_k, evaluated in double, the sum taken in ascending t; core = (float)(1 - the sum of the weights, in double).  The taps
+ * are NOT renormalised after rounding (they sum to 1 within n_k 2^-24).  Everything of *out that the PSF does not use is zero.  Refused: a
+ * NULL; a count outside 0 ... 4; a sigma not in (0, 64] or not finite; a weight outside [0, 1] or not finite; weights that sum to more
+ * than 1. */
+int gr_glare_gaussians(const float* sigma, const float* weight, int count, struct gr_glare* out);
+/* Exposure: core and all four weights times (float)exp2((double)stops), each one fp32 product.  Refused: a NULL, stops that are not
+ * finite or lie outside -32 ... 32. */
+int gr_glare_exposure(struct gr_glare* g, float stops);
+/* The host statement of the definition: src and dst are float[4 * width * height]; compiled so that nothing is contracted.  Refused before
+ * anything is written: a NULL; a size below 1; src == dst; a field of *g out of its range. */
+int gr_glare_frame(const float* src, int width, int height, const struct gr_glare* g, float* dst);
+/* The same on the device, bit for bit (kernels/glare.hip, set-up module: IEEE arithmetic, no contraction), asynchronous on `stream`: src,
+ * dst and scratch are device memory, *g is HOST memory (the one table a launch applies travels in its argument block).  K = 0 is one
+ * elementwise launch; otherwise a rows launch into scratch and a columns launch that adds the component into dst, 2 K in all.  Whole
+ * frames only.  gr_glare_scratch_bytes: what scratch must hold for a frame of that size - one float4 frame.  Refused: what gr_glare_frame
+ * refuses; a NULL program; scratch that is NULL, shorter than that or not aligned to 16 bytes; any overlap of src, dst and scratch; more
+ * than 2^31 - 1 pixels. */
+int gr_glare_scratch_bytes(int width, int height, size_t* bytes);
+int gr_apply_glare(gr_program* p, void* stream, const void* src, void* dst, void* scratch, size_t scratch_bytes, int width, int height,
+                   const struct gr_glare* g);
+/* The glare of a state's frames.  NULL (the default): every entry point is as it was, launch for launch.  With a glare set,
+ * gr_render_frame, gr_render_frame_rgba8, gr_render_frame_yuv420 and gr_render_frame_yuv420p10 deliver gr_glare_frame of the frame they
+ * would have delivered as float4: the frame is resolved into a frame the state owns (gr_resolve_supersampled or gr_resolve_filtered; a
+ * factor-1 box state's traced frame is the source as it is - it no longer renders straight into `out`, but for out == NULL), then
+ * gr_apply_glare into a second frame of the state - a float4 delivery goes straight into `out` -, then the format's own kernel at factor 1.
+ * The state's frames and scratch are allocated with the first frame that is not refused and freed with the state; all these launches lie
+ * between the events of gr_render_state_resolve_ms.  gr_render_subframe accumulates the frame WITHOUT the glare and
+ * gr_deliver_accumulated applies it to the accumulation, into the state's own frame, before the encode: the glare is linear, so that is
+ * one application a frame, it is the definition, and the accumulation stays as it is.  A state with a glare renders whole frames only:
+ * strip_count > 1 and gr_render_frame_tiled / _tiled_as are refused before anything is rendered (the PSF reads across strip borders).
+ * gr_render_state_set_glare refuses a NULL state and a field out of range; it may be called between frames.  gr_render_state_glare:
+ * *is_set = 1 and the glare in *out, or 0 and *out untouched. */
+int gr_render_state_set_glare(gr_render_state* s, const struct gr_glare* glare_or_null);
+int gr_render_state_glare(const gr_render_state* s, struct gr_glare* out, int* is_set);
+
 /* ---- PNG frames -----------------------------------------------------------------------------------------------------------------------
  * A PNG encoder behind an RGBA8 frame that is already in device memory (gr_render_frame_rgba8, gr_deliver_accumulated(GR_FRAME_RGBA8),
  * participant 0's frame of gr_render_frame_tiled_as): filtering, histogram and bit-packing run on the device (kernels/png.hip, set-up
