@@ -393,6 +393,16 @@ _SIGNATURES = {
     "gr_png_encoder_time_launches": (c_int, [c_void_p, c_int]),
     "gr_png_encoder_launch_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     "gr_png_encoder_scratch_intact": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "gr_exr_encode_bound": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "gr_exr_half_bits": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "gr_exr_encode_f32_host": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
+    "gr_write_frame_exr": (c_int, [c_char_p, c_void_p, c_int, c_int]),
+    "gr_exr_encoder_create": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "gr_exr_encoder_destroy": (None, [c_void_p]),
+    "gr_exr_encode_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
+    "gr_exr_encoder_time_launches": (c_int, [c_void_p, c_int]),
+    "gr_exr_encoder_launch_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
+    "gr_exr_encoder_scratch_intact": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "gr_jpeg_encode_bound": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "gr_jpeg_quant_tables": (c_int, [c_int, c_void_p, c_void_p]),
     "gr_jpeg_encode_rgba8_host": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t)]),
@@ -431,5 +441,5 @@ def check(rc):
 from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, build_background,  # noqa: E402,F401
                        default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background, rgba8_to_yuv420,
                        yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes, accumulate_frame, filter_taps,
-                       filter_frame, glare_gaussians, glare_exposure, glare_frame, glare_scratch_bytes, apply_glare, PngEncoder, png_encode_bound, png_encode_host, JpegEncoder, jpeg_encode_bound, jpeg_encode_host, jpeg_quant_tables,
+                       filter_frame, glare_gaussians, glare_exposure, glare_frame, glare_scratch_bytes, apply_glare, PngEncoder, png_encode_bound, png_encode_host, ExrEncoder, exr_encode_bound, exr_encode_host, exr_half_bits, JpegEncoder, jpeg_encode_bound, jpeg_encode_host, jpeg_quant_tables,
                        AviWriter, AnalyticSky, StarCatalogue, StarSky, star_field_random)

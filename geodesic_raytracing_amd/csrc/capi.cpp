@@ -73,20 +73,22 @@ const char* const KERNEL_NAMES[] = {
     "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack",
     "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather", "gr_png_histogram_runs", "gr_png_pack_runs", "gr_render_analytic",
     "gr_render_stars", "gr_stars_count", "gr_stars_scan", "gr_stars_scatter", "gr_stars_order", "gr_stars_gather", "gr_stars_sums", "gr_stars_prefix",
-    "gr_glare_rows", "gr_glare_columns", "gr_glare_scale"};
+    "gr_glare_rows", "gr_glare_columns", "gr_glare_scale", "gr_exr_histogram", "gr_exr_pack"};
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
 // filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and 8- and 10-bit Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
 // (kernels/background.hip), which want the same arithmetic and no part in the ray kernels' compilation - and the two integer kernels of the
 // PNG encoder (kernels/png.hip; each in two instances, one a stream kind) and the three of the JPEG encoder (kernels/jpeg.hip), which want
 // no part in it either - and the seven that build a star catalogue (kernels/stars.hip), whose sums are taken in the order they are written -
-// and the three of the glare (kernels/glare.hip), which are held to a host definition bit for bit
+// and the three of the glare (kernels/glare.hip), which are held to a host definition bit for bit - and the two integer kernels of the
+// EXR encoder (kernels/exr.hip), which use the PNG encoder's bit-packer
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
            k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE || k == K_RESOLVE_FILTERED ||
            k == K_PNG_HISTOGRAM || k == K_PNG_PACK || k == K_JPEG_BLOCKS || k == K_JPEG_PACK || k == K_JPEG_GATHER || k == K_PNG_HISTOGRAM_RUNS ||
-           k == K_PNG_PACK_RUNS || (k >= K_STARS_COUNT && k <= K_STARS_PREFIX) || k == K_GLARE_ROWS || k == K_GLARE_COLUMNS || k == K_GLARE_SCALE;
+           k == K_PNG_PACK_RUNS || (k >= K_STARS_COUNT && k <= K_STARS_PREFIX) || k == K_GLARE_ROWS || k == K_GLARE_COLUMNS || k == K_GLARE_SCALE || k == K_EXR_HISTOGRAM ||
+           k == K_EXR_PACK;
 }
 
 namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files

@@ -1,5 +1,5 @@
-// device_encoders.cpp — the two file encoders that run on the device, gr_png_encoder (kernels/png.hip; its stream and host encoder:
-// png_stream.cpp) and gr_jpeg_encoder (kernels/jpeg.hip; jpeg_stream.cpp), on one core: a borrowed program, a fenced scratch
+// device_encoders.cpp — the three file encoders that run on the device, gr_png_encoder (kernels/png.hip; its stream and host encoder:
+// png_stream.cpp), gr_exr_encoder (kernels/exr.hip; exr_stream.cpp) and gr_jpeg_encoder (kernels/jpeg.hip; jpeg_stream.cpp), on one core: a borrowed program, a fenced scratch
 // (guarded_scratch.hpp), a pinned staging buffer and a launch timer.  An encoder adds its region sizes, its own buffers and its encode.
 #include <hip/hip_runtime_api.h>
 
@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "exr_stream.hpp"
 #include "guarded_scratch.hpp"
 #include "internal.hpp"
 #include "jpeg_stream.hpp"
@@ -58,7 +59,7 @@ struct encoder_core {
     int elapsed(float* ms, int from, int to) { HIP_CHECK(hipEventElapsedTime(ms, events[from], events[to])); return GR_OK; }
 };
 
-// the three calls both kinds of encoder answer alike; `kind` is "gr_png_encoder" or "gr_jpeg_encoder"
+// the three calls every kind of encoder answers alike; `kind` is "gr_png_encoder", "gr_exr_encoder" or "gr_jpeg_encoder"
 int set_time_launches(const std::string& kind, encoder_core* e, int on) {
     if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, kind + "_time_launches: a required pointer is NULL");
     HIP_CHECK(hipSetDevice(e->device));
@@ -213,6 +214,123 @@ int gr_png_encode_rgba8(gr_png_encoder* e, void* stream, const void* device_rgba
     e->timed = e->time_launches;
     png_stream::write_container(out_file, width, height, e->staging, rows_bytes, png_stream::join_adler(adlers.data(), width, height));
     *out_bytes = (size_t)png_stream::file_bytes(rows_bytes);
+    return GR_OK;
+}
+
+// ---- EXR frames --------------------------------------------------------------------------------------------------------------------
+
+struct gr_exr_encoder : encoder_core {
+    // device: [frame histogram 256 | rows' histograms height x 256 | rows' sums height x 2] words, downloaded in one copy ...
+    unsigned int* statistics = nullptr;
+    size_t statistics_words = 0;
+    // ... [chunks' offsets height + 1, 64 bit | rows' words height x 2: Adler-32, raw | table 257 | header png_stream::HEADER_WORDS] uploaded in one ...
+    unsigned char* placement = nullptr;
+    unsigned char* placement_host = nullptr;   // (pinned)
+    size_t placement_bytes = 0;
+    // ... and the chunk area, the scratch's one region: what follows the offset table in the file, chunk headers included.  An encode zeroes
+    // the words its chunks take and nothing else (used[0]: the longest of any encode so far).  The staging buffer takes the statistics, then
+    // the chunks; header and offset table are the host's, written into out_file in front of them.
+    size_t stream_capacity_words = 0;
+};
+
+int gr_exr_encoder_create(gr_program* p, int width, int height, gr_exr_encoder** out) {
+    const std::string who = "gr_exr_encoder_create: ";
+    if (!p || !out) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
+    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1 (width " + std::to_string(width) + ", height " + std::to_string(height) + ")");
+    const uint64_t bound = exr_stream::file_bound(width, height);
+    if (!bound) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a row of more than 2^31 - 1 raw bytes (width " + std::to_string(width) + ", 6 bytes a pixel)");
+    auto e = std::make_unique<gr_exr_encoder>();
+    GR_CHECK(e->borrow(p, width, height));
+    e->statistics_words = 256 + (size_t)height * (256 + 2);
+    e->placement_bytes = ((size_t)height + 1) * 8 + ((size_t)height * 2 + png_stream::SYMBOLS + png_stream::HEADER_WORDS) * 4;
+    e->stream_capacity_words = (size_t)((bound - exr_stream::chunks_at(height) + 3) / 4);
+    e->regions = guarded_scratch::lay_out(&e->stream_capacity_words, 1, 1);
+    GR_CHECK(e->allocate(&e->statistics, e->statistics_words * 4));
+    GR_CHECK(e->allocate(&e->placement, e->placement_bytes));
+    GR_CHECK(e->allocate(&e->scratch, e->regions.total * 4));
+    GR_CHECK(e->allocate(&e->placement_host, e->placement_bytes, true));
+    GR_CHECK(e->allocate(&e->staging, std::max(e->statistics_words * 4, e->stream_capacity_words * 4), true));
+    GR_CHECK(e->fill_scratch());
+    HIP_CHECK(hipDeviceSynchronize());
+    *out = e.release();
+    return GR_OK;
+}
+
+void gr_exr_encoder_destroy(gr_exr_encoder* e) { delete e; }
+int gr_exr_encoder_time_launches(gr_exr_encoder* e, int on) { return set_time_launches("gr_exr_encoder", e, on); }
+int gr_exr_encoder_launch_ms(gr_exr_encoder* e, float ms[2]) { return launch_ms("gr_exr_encoder", e, ms, 2, 2); }   // (events 0 - 1, 2 - 3)
+int gr_exr_encoder_scratch_intact(gr_exr_encoder* e, int* intact) { return scratch_intact("gr_exr_encoder", e, intact); }
+
+int gr_exr_encode_f32(gr_exr_encoder* e, void* stream, const void* device_rgba_f32, unsigned char* out_file, size_t capacity, size_t* out_bytes) {
+    const std::string who = "gr_exr_encode_f32: ";
+    if (!e) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required pointer is NULL");
+    bool too_small = false;
+    const std::string wrong = exr_stream::refusal(device_rgba_f32, e->width, e->height, out_file, capacity, out_bytes, true, &too_small);
+    if (!wrong.empty()) return refuse("gr_exr_encode_f32", wrong, too_small);
+    int width = e->width, height = e->height;
+    hipStream_t on = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(e->device));
+    // the first round trip: the frame's and the rows' histograms of predicted bytes, the rows' Adler sums
+    unsigned int* frame_histogram = e->statistics;
+    unsigned int* row_histogram = e->statistics + 256;
+    unsigned int* row_sums = row_histogram + (size_t)height * 256;
+    HIP_CHECK(hipMemsetAsync(frame_histogram, 0, 256 * 4, on));
+    GR_CHECK(e->mark(0, on));
+    void* histogram_args[] = {&device_rgba_f32, &width, &height, &frame_histogram, &row_histogram, &row_sums};
+    GR_CHECK(launch(e->program, K_EXR_HISTOGRAM, stream, (unsigned)height, 1, 64, 4, histogram_args));
+    GR_CHECK(e->mark(1, on));
+    HIP_CHECK(hipMemcpyAsync(e->staging, e->statistics, e->statistics_words * 4, hipMemcpyDeviceToHost, on));
+    HIP_CHECK(hipStreamSynchronize(on));
+    // the table from the frame's histogram and one end-of-block a row; from every row's own histogram the size of its zlib stream, and
+    // with it whether the row is stored raw and where its chunk lies; the Adler-32 from its sums
+    const unsigned int* got = (const unsigned int*)e->staging;
+    uint64_t histogram[png_stream::MAX_SYMBOLS] = {};
+    for (int v = 0; v < 256; v++) histogram[v] = got[v];
+    histogram[exr_stream::END_OF_BLOCK] = (uint64_t)height;
+    png_stream::table t;
+    exr_stream::build_table(histogram, t);
+    uint64_t* offset = (uint64_t*)e->placement_host;
+    unsigned int* row_words = (unsigned int*)(e->placement_host + ((size_t)height + 1) * 8);
+    unsigned int* table_words = row_words + 2 * (size_t)height;
+    unsigned int* header_words = table_words + png_stream::SYMBOLS;
+    const uint64_t raw_bytes = exr_stream::row_bytes(width);
+    offset[0] = 0;
+    for (int r = 0; r < height; r++) {
+        const uint64_t zipped = exr_stream::stream_bytes(exr_stream::row_block_bits(t, got + 256 + (size_t)r * 256));
+        const bool raw = exr_stream::stored_raw(zipped, width);
+        const unsigned int* sums = got + 256 + (size_t)height * 256 + 2 * (size_t)r;
+        offset[r + 1] = offset[r] + exr_stream::CHUNK_HEADER_BYTES + (raw ? raw_bytes : zipped);
+        row_words[2 * (size_t)r] = exr_stream::row_adler(width, sums[0], sums[1]);
+        row_words[2 * (size_t)r + 1] = raw ? 1u : 0u;
+    }
+    const uint64_t chunks_bytes = offset[height], stream_words = (chunks_bytes + 3) / 4;
+    if (stream_words > e->stream_capacity_words) return fail(GR_ERROR_DEVICE, who + "the chunks' sizes exceed the bound");   // (the raw fallback rules it out)
+    for (int s = 0; s < png_stream::SYMBOLS; s++) table_words[s] = (unsigned int)t.code[s] | ((unsigned int)t.length[s] << 16);
+    std::copy(t.header, t.header + png_stream::HEADER_WORDS, header_words);
+    // the second: placement up, the chunk area zeroed (the pack ORs the words chunks share), the pack, the chunks down
+    unsigned int* stream_at = e->region(0);
+    HIP_CHECK(hipMemcpyAsync(e->placement, e->placement_host, e->placement_bytes, hipMemcpyHostToDevice, on));
+    HIP_CHECK(hipMemsetAsync(stream_at, 0, (size_t)stream_words * 4, on));
+    e->used[0] = std::max(e->used[0], (size_t)stream_words);
+    GR_CHECK(e->mark(2, on));
+    int header_bits = t.header_bits;
+    const unsigned long long* offsets_on_device = (const unsigned long long*)e->placement;
+    const unsigned int* row_words_on_device = (const unsigned int*)(e->placement + ((size_t)height + 1) * 8);
+    const unsigned int* table_on_device = row_words_on_device + 2 * (size_t)height;
+    const unsigned int* header_on_device = table_on_device + png_stream::SYMBOLS;
+    unsigned long long word_count = stream_words;
+    void* pack_args[] = {&device_rgba_f32, &width, &height, &table_on_device, &header_on_device, &header_bits, &offsets_on_device, &row_words_on_device,
+                         &stream_at, &word_count};
+    GR_CHECK(launch(e->program, K_EXR_PACK, stream, (unsigned)height, 1, 64, 4, pack_args));
+    GR_CHECK(e->mark(3, on));
+    HIP_CHECK(hipMemcpyAsync(e->staging, stream_at, (size_t)stream_words * 4, hipMemcpyDeviceToHost, on));
+    // (the header and the offset table while the chunks travel: the offsets are final)
+    exr_stream::write_header(out_file, width, height);
+    exr_stream::write_offsets(out_file, height, offset);
+    HIP_CHECK(hipStreamSynchronize(on));
+    e->timed = e->time_launches;
+    memcpy(out_file + exr_stream::chunks_at(height), e->staging, (size_t)chunks_bytes);
+    *out_bytes = (size_t)(exr_stream::chunks_at(height) + chunks_bytes);
     return GR_OK;
 }
 

@@ -1,6 +1,6 @@
 // internal.hpp — what the library's translation units share and no caller sees: the gr_internal_* calls between them, one HIP_CHECK and
 // one GR_CHECK, and the little of a program (capi.cpp) that a file outside capi.cpp needs to launch its kernels.  No HIP header: the host-only
-// files (png_stream.cpp, jpeg_stream.cpp, imageio.cpp) include it and compile alone; the macros name HIP only where they are expanded.
+// files (png_stream.cpp, exr_stream.cpp, jpeg_stream.cpp, imageio.cpp) include it and compile alone; the macros name HIP only where they are expanded.
 #pragma once
 
 #include <string>
@@ -38,11 +38,11 @@ enum KernelId {
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
     K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_JPEG_BLOCKS, K_JPEG_PACK, K_JPEG_GATHER, K_PNG_HISTOGRAM_RUNS, K_PNG_PACK_RUNS, K_RENDER_ANALYTIC,
     K_RENDER_STARS, K_STARS_COUNT, K_STARS_SCAN, K_STARS_SCATTER, K_STARS_ORDER, K_STARS_GATHER, K_STARS_SUMS, K_STARS_PREFIX,
-    K_GLARE_ROWS, K_GLARE_COLUMNS, K_GLARE_SCALE, K_COUNT
+    K_GLARE_ROWS, K_GLARE_COLUMNS, K_GLARE_SCALE, K_EXR_HISTOGRAM, K_EXR_PACK, K_COUNT
 };
 
 namespace gr_internal __attribute__((visibility("hidden"))) {   // (not among the library's exported names)
-// what a refusal() of png_stream, jpeg_stream said - or any refusal in words - as a status, the caller's name in front
+// what a refusal() of png_stream, exr_stream, jpeg_stream said - or any refusal in words - as a status, the caller's name in front
 inline int refuse(const std::string& who, const std::string& wrong, bool too_small = false) {
     return gr_internal_fail(too_small ? GR_ERROR_BUFFER_TOO_SMALL : GR_ERROR_INVALID_ARGUMENT, (who + ": " + wrong).c_str());
 }

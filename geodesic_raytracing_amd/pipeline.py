@@ -419,7 +419,9 @@ def png_encode_host(pixels, stream_kind=None):
 
 class _DeviceEncoder:
     """what PngEncoder and JpegEncoder share: the handle of a gr_png_encoder or gr_jpeg_encoder (_prefix: "gr_png_" or "gr_jpeg_"), the
-    output array of the encoder's bound, and the calls both kinds answer alike (_launches: the times launch_ms returns)"""
+    output array of the encoder's bound, and the calls both kinds answer alike (_launches: the times launch_ms returns).  ExrEncoder is the
+    third (_prefix "gr_exr_"): its frames are float4 and its encode call (_encode) is gr_exr_encode_f32"""
+    _encode = "encode_rgba8"
 
     def _create(self, bound, create, *args):
         self.handle = c_void_p()
@@ -433,7 +435,7 @@ class _DeviceEncoder:
         """the file of the frame at device_ptr (width x height RGBA8 pixels) as bytes: the host encoder's (png_encode_host of the same kind,
         jpeg_encode_host of the same quality) of the same pixels"""
         size = ctypes.c_size_t()
-        self._call("encode_rgba8", stream, device_ptr, self._out.ctypes.data_as(c_void_p), self._out.nbytes, ctypes.byref(size))
+        self._call(self._encode, stream, device_ptr, self._out.ctypes.data_as(c_void_p), self._out.nbytes, ctypes.byref(size))
         return self._out[:size.value].tobytes()
 
     def write(self, path, device_ptr, stream=None):
@@ -482,6 +484,53 @@ class PngEncoder(_DeviceEncoder):
             self._create(png_encode_bound, lib.gr_png_encoder_create)
         else:
             self._create(png_encode_bound, lib.gr_png_encoder_create_as, self.stream_kind)
+
+
+def exr_encode_bound(width, height):
+    """the capacity both EXR encoders ask for (gr_exr_encode_bound): the size of the file whose every row is stored raw"""
+    need = ctypes.c_size_t()
+    check(lib.gr_exr_encode_bound(int(width), int(height), ctypes.byref(need)))
+    return need.value
+
+
+def exr_half_bits(values):
+    """the half-float bit patterns (uint16, the shape of `values`) the EXR encoders make of float32 values: NaN -> +0, clamped to +-65504,
+    round to nearest even with subnormals kept (gr_exr_half_bits)"""
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.empty(values.shape, np.uint16)
+    check(lib.gr_exr_half_bits(values.ctypes.data_as(c_void_p), values.size, out.ctypes.data_as(c_void_p)))
+    return out
+
+
+def exr_encode_host(frame):
+    """the OpenEXR file of a float32 frame [H, W, 4] (alpha ignored) as bytes, by the host encoder that defines ExrEncoder's file
+    (gr_exr_encode_f32_host: half-float B, G, R planes, ZIPS - one zlib stream a scan line, one Huffman table a frame, literals only, rows
+    that do not shrink stored raw)"""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.ndim != 3 or frame.shape[2] != 4:
+        raise ValueError(f"exr_encode_host: a frame of shape {frame.shape} is not [H, W, 4]")
+    h, w = frame.shape[:2]
+    if frame.ctypes.data % 16:   # (the encoder takes what a device frame is: 16-byte aligned pixels)
+        aligned = np.empty(frame.size + 4, np.float32)
+        start = (-aligned.ctypes.data % 16) // 4
+        aligned = aligned[start:start + frame.size].reshape(frame.shape)
+        aligned[...] = frame
+        frame = aligned
+    out = np.empty(exr_encode_bound(w, h), dtype=np.uint8)
+    size = ctypes.c_size_t()
+    check(lib.gr_exr_encode_f32_host(frame.ctypes.data_as(c_void_p), w, h, out.ctypes.data_as(c_void_p), out.nbytes, ctypes.byref(size)))
+    return out[:size.value].tobytes()
+
+
+class ExrEncoder(_DeviceEncoder):
+    """An OpenEXR encoder behind float4 frames of one size that are already on the program's device (gr_exr_encoder): half conversion,
+    predictor, histogram and bit-packing run there, the file's chunks come back.  encode() takes the float4 frame's device pointer, gives
+    exr_encode_host's bytes of the same pixels and synchronises the stream it is given.  The program must outlive it."""
+    _prefix, _launches, _encode = "gr_exr_", 2, "encode_f32"
+
+    def __init__(self, program, width, height):
+        self.program, self.width, self.height = program, int(width), int(height)   # (the program is borrowed: kept alive here)
+        self._create(exr_encode_bound, lib.gr_exr_encoder_create)
 
 
 def jpeg_encode_bound(width, height):

@@ -28,6 +28,8 @@
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --camera 0,0,-8,0 --camera-to 0,3,-6,0 --frames 48 --fps 30000/1001 --jpeg device --out pan.avi
     # lensed point stars with glare: a sharp core inside two Gaussian halos and one stop more exposure, so that a star of 400 outshines a star of 1 in 8 bits
     python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --sky stars:200000:7 --glare 0.06:1.5,0.03:10 --exposure 1 --out stars.png
+    # the same stars as the renderer computed them: scene-linear half floats in an OpenEXR file (ZIPS), nothing clamped at 1; --exr device deflates on the GPU
+    python -m geodesic_raytracing_amd.render --metric kerr_boyer --cfg a=0.45 --size 3840x2160 --sky stars:200000:7 --exr device --out stars.exr
 """
 import argparse
 import ctypes
@@ -68,6 +70,13 @@ def write_png_bytes(path, data):
     """a PNG file that is already encoded (render(png="device"), pipeline.PngEncoder.encode)"""
     with open(path, "wb") as f:
         f.write(data)
+
+
+def write_frame_exr(path, frame):
+    """a linear-light float frame [H, W, 4] as an OpenEXR file of half floats (gr_write_frame_exr: pipeline.exr_encode_host's bytes)"""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    h, w = frame.shape[:2]
+    gra.check(gra.lib.gr_write_frame_exr(path.encode(), frame.ctypes.data_as(ctypes.c_void_p), w, h))
 
 
 def write_jpeg_rgba8(path, pixels, quality=90):
@@ -190,8 +199,12 @@ def checked_png_stream(who, png, png_stream):
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
            parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box",
-           png="host", jpeg=None, quality=90, png_stream="literals", sky=None, glare=None, exposure=0.0):
-    """glare: a gra.GlareStruct (pipeline.glare_gaussians) or [(weight, sigma)], up to four Gaussians of sigma output pixels - every frame
+           png="host", jpeg=None, quality=90, png_stream="literals", sky=None, glare=None, exposure=0.0, exr=None):
+    """exr: "host" or "device" (float frames only: no rgba8, yuv420, png="device" or jpeg) - every frame returned is the bytes of a finished
+    OpenEXR file of scene-linear half floats instead of pixels: with "device" the float4 frame stays on the device and is converted,
+    predicted, histogrammed and bit-packed there (pipeline.ExrEncoder), with "host" it comes back and pipeline.exr_encode_host makes the
+    file - the same bytes.
+    glare: a gra.GlareStruct (pipeline.glare_gaussians) or [(weight, sigma)], up to four Gaussians of sigma output pixels - every frame
     goes through that point-spread function on the device, in linear light, after the resolve and before any encode (RenderState(glare=):
     pipeline.glare_frame of the frame rendered without it, bit for bit): a star far above 1 keeps a halo in an 8-bit file.  exposure:
     stops, -32 ... 32 - a gain of 2^exposure on the same stage (pipeline.glare_exposure); works alone.  Whole frames only.
@@ -232,6 +245,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
         raise ValueError(f"render: jpeg={jpeg!r} (None, or host or device with rgba8=True, no yuv420 and png='host')")
     if jpeg is not None and not 1 <= int(quality) <= 100:
         raise ValueError(f"render: quality={quality!r} (1 to 100)")
+    if exr not in (None, "host", "device") or (exr is not None and (rgba8 or yuv420 or png == "device" or jpeg is not None)):
+        raise ValueError(f"render: exr={exr!r} (None, or host or device with float frames: no rgba8, yuv420, png='device' or jpeg)")
     if png not in ("host", "device") or (png == "device" and (not rgba8 or yuv420)):
         raise ValueError(f"render: png={png!r} (host, or device with rgba8=True and no yuv420)")
     png_stream = checked_png_stream("render", png, png_stream)
@@ -267,7 +282,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     out_bytes = fmt.bytes(width, height)
     out = DeviceBuffer(device, out_bytes)
     encoder = (gra.PngEncoder(program, width, height, png_stream) if png == "device" else
-               gra.JpegEncoder(program, width, height, quality) if jpeg == "device" else None)
+               gra.JpegEncoder(program, width, height, quality) if jpeg == "device" else
+               gra.ExrEncoder(program, width, height) if exr == "device" else None)
     pinned = PinnedBuffer(out_bytes) if frame_format != gra.FRAME_F32 and encoder is None else None   # (a float frame is downloaded as it always was)
     cam = gra.default_camera(camera_pos, camera_quat)
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
@@ -278,6 +294,8 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
             return encoder.encode(out.ptr, None)   # the frame's stream: the encoder's launches queue behind the frame's
         if pinned is None:
             state.synchronize()
+            if exr == "host":
+                return gra.exr_encode_host(out.to_numpy(fmt.dtype, fmt.shape(width, height)))
             return out.to_numpy(fmt.dtype, fmt.shape(width, height))
         pinned.download_async(None, out.ptr, out_bytes)   # the frame's stream: copies queue behind its launches
         gra.check(gra.lib.gr_stream_synchronize(None))
@@ -475,7 +493,7 @@ def main(argv=None):
     ap.add_argument("--encode", choices=["host", "device"], default="host", help="where the frame becomes 8-bit sRGB: host = download float4 and "
                     "convert there; device = encode on the GPU and download 4 bytes a pixel (the same bytes).  Ignored for --out NAME.y4m, "
                     "whose frames are always encoded on the device")
-    ap.add_argument("--png", choices=["host", "device"], default="host", help="where a frame becomes a PNG file: host = the pixels come back and one host "
+    ap.add_argument("--png", choices=["host", "device"], default=None, help="where a frame becomes a PNG file: host = the pixels come back and one host "
                     "thread deflates them; device = the 8-bit frame is filtered, histogrammed and Huffman-coded on the GPU (Sub / Up filters, one "
                     "table a frame, no matches) and only the compressed bytes come back.  device implies --encode device; not with --out NAME.y4m")
     ap.add_argument("--png-stream", choices=sorted(gra.PNG_STREAM_NAMES, key=gra.PNG_STREAM_NAMES.get), default=None, help="the stream of a PNG made "
@@ -485,6 +503,10 @@ def main(argv=None):
                     "(JFIF, 4:2:0, the standard Huffman tables, one restart interval a row of 16 x 16 blocks): host (the default) = the 8-bit pixels "
                     "come back and one host thread encodes them; device = colour conversion, DCT, quantiser and Huffman coding run on the GPU and only "
                     "the file's bytes come back (the same bytes).  device implies --encode device; not with --out NAME.png or NAME.y4m")
+    ap.add_argument("--exr", choices=["host", "device"], default=None, help="where a frame of --out NAME.exr becomes an OpenEXR file (scene-linear half "
+                    "floats, B G R, ZIPS: one zlib stream a scan line, rows that do not shrink stored raw): host (the default) = the float4 frame comes "
+                    "back and one host thread converts and deflates it; device = half conversion, predictor, histogram and Huffman coding run on the "
+                    "GPU and only the file's bytes come back (the same bytes).  Only with --out NAME.exr; device not with --devices")
     ap.add_argument("--quality", type=int, default=None, help="of a .jpg or .avi: 1 ... 100, the usual scaling of the standard quantisation tables (90)")
     ap.add_argument("--sky", default=None, help="stars:N[:SEED[:MIN_FOOTPRINT]]: N point stars, generated, binned on the GPU and lensed there - a star's "
                     "brightness in a pixel goes as the inverse of the sky the pixel covers, down to MIN_FOOTPRINT (a power of two, 2^-16).  "
@@ -507,7 +529,7 @@ def main(argv=None):
     ap.add_argument("--devices", default=None, help="0,1,2,3: deal the rows of every frame to these GPUs (one process, peer copies; a device may "
                     "repeat); each traces, resolves and - with --encode device - encodes its share, the share rotating over --frames")
     ap.add_argument("--fps", default="24", help="frame rate of a .y4m or .avi file: N or N/D (24; 30000/1001)")
-    ap.add_argument("--bit-depth", type=int, choices=[8, 10], default=8, help="bits a sample of a .y4m file: 8 (C420jpeg, 1.5 bytes a pixel) or 10 "
+    ap.add_argument("--bit-depth", type=int, choices=[8, 10], default=None, help="bits a sample of a .y4m file: 8 (C420jpeg, 1.5 bytes a pixel) or 10 "
                     "(C420p10: 16-bit little-endian words, 3 bytes a pixel - the master for a 10-bit encode).  Only with --out NAME.y4m")
     ap.add_argument("--shutter", type=float, default=None, help="motion blur: the fraction of the frame interval the shutter is open, above 0 and at "
                     "most 1 (0.5: the 180-degree film shutter; default: no shutter, every frame one instantaneous pose).  Every frame is the "
@@ -516,11 +538,27 @@ def main(argv=None):
     ap.add_argument("--shutter-samples", type=int, default=None, help="sub-frames a frame of --shutter, 2 ... 64 (8)")
     ap.add_argument("--out", required=True, help="NAME.png: one PNG, or NAME_000.png ... for a sequence.  NAME.y4m: all frames in one uncompressed "
                     "YUV4MPEG2 file of 8-bit BT.709 Y'CbCr 4:2:0 frames, converted on the device.  NAME.jpg: one baseline JPEG, or NAME_000.jpg ... for a "
-                    "sequence.  NAME.avi: all frames in one Motion-JPEG file (AVI 1.0, at most 2 GiB)")
+                    "sequence.  NAME.avi: all frames in one Motion-JPEG file (AVI 1.0, at most 2 GiB).  NAME.exr: one OpenEXR file of the frame in linear "
+                    "light, half floats, or NAME_000.exr ... for a sequence")
     a = ap.parse_args(argv)
     video = a.out.lower().endswith(".y4m")
     avi = a.out.lower().endswith(".avi")
     jpeg_out = avi or a.out.lower().endswith((".jpg", ".jpeg"))
+    exr_out = a.out.lower().endswith(".exr")
+    if a.exr is not None and not exr_out:
+        ap.error(f"--exr {a.exr} with --out {a.out}: --exr says where an OpenEXR file is made; give --out NAME.exr")
+    if exr_out:
+        for given, flag in ((a.encode == "device", "--encode device"), (a.png is not None, "--png"), (a.jpeg is not None, "--jpeg"),
+                            (a.quality is not None, "--quality"), (a.bit_depth is not None, "--bit-depth")):
+            if given:
+                ap.error(f"{flag} with --out NAME.exr: an OpenEXR file holds the frame in linear light as half floats - there is no 8-bit encode, "
+                         "no PNG or JPEG stream and no video bit depth in it; leave the flag out (--exr host|device says where the file is made)")
+        a.exr = a.exr or "host"
+        if a.exr == "device" and a.devices is not None:
+            ap.error("--exr device with --devices: the assembled frame of a split render is not on one device for the encoder to read; "
+                     "--exr host works there")
+    a.png = a.png or "host"
+    a.bit_depth = a.bit_depth or 8
     try:
         fps = parse_fps(a.fps)
     except ValueError as e:
@@ -591,7 +629,7 @@ def main(argv=None):
     speed = [float(v) for v in a.geodesic_speed.split(",")] if a.geodesic_speed else None
     times = [a.geodesic_time + i * a.geodesic_dt for i in range(max(a.frames, 1))]
     moments = shutter_times(max(a.frames, 1), a.shutter, samples).ravel() if samples else None   # frame numbers, `samples` a frame
-    write = write_png_bytes if a.png == "device" or jpeg_out else write_rgba8_png if a.encode == "device" else write_frame_png
+    write = write_png_bytes if a.png == "device" or jpeg_out or (exr_out and a.devices is None) else write_frame_exr if exr_out else write_rgba8_png if a.encode == "device" else write_frame_png
     if a.devices is not None:
         try:
             devices = [int(v) for v in a.devices.split(",")]
@@ -632,7 +670,7 @@ def main(argv=None):
                     geodesic_times=[a.geodesic_time + float(t) * a.geodesic_dt for t in moments] if samples else times,
                     parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
                     rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples,
-                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream, sky=sky, glare=glare)
+                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream, sky=sky, glare=glare, exr=a.exr)
     if speed is None and cameras is None:
         result = [result]
     if video:

@@ -622,6 +622,69 @@ int gr_png_encoder_time_launches(gr_png_encoder* e, int on);
 int gr_png_encoder_launch_ms(gr_png_encoder* e, float ms[2]);
 int gr_png_encoder_scratch_intact(gr_png_encoder* e, int* intact);
 
+/* ---- EXR frames -----------------------------------------------------------------------------------------------------------------------
+ * An OpenEXR encoder behind a float4 frame that is already in device memory (gr_render_frame, gr_deliver_accumulated(GR_FRAME_F32)): the one
+ * sink that keeps what the renderer computed - scene-linear half floats, values far above 1 included - at 6 bytes a pixel or less.  Half
+ * conversion, plane separation, byte split, predictor, histogram and bit-packing run on the device (kernels/exr.hip, set-up module), only
+ * the file's chunks come back.  A sink like PNG, not a fifth GR_FRAME_* format.  (Declared here and not in geodesic_hip.h only because the
+ * contract header keeps to 80 names and 350 lines; all of this is public.)
+ *
+ * The file is fixed, so that host and device write the same bytes:
+ *   container   76 2F 31 01, version 02 00 00 00: one part, scan lines, short names.  The attributes, in this order: channels (chlist: B, G,
+ *               R, each HALF, pLinear 0, sampling 1 x 1), compression = 2 (ZIPS: zlib, one scan line a chunk), dataWindow and displayWindow
+ *               = (0, 0, width - 1, height - 1), lineOrder = 0, pixelAspectRatio = 1, screenWindowCenter = (0, 0), screenWindowWidth = 1 -
+ *               313 bytes with the closing 0.  No alpha (the frame's carries nothing), no chromaticities (the default, Rec. 709, is right).
+ *               Then the offset table, height x uint64 from the file's start, then the chunks in increasing y: int32 y, int32 size, data.
+ *   halfs       of a pixel's r, g, b: a NaN is +0; everything else is clamped to [-65504, 65504] - no infinity is written - and rounded to
+ *               nearest even with half subnormals kept (2^-25 is a tie and goes to 0).  Stated in integer arithmetic on the float's bits, the
+ *               same lines on host and device: no compiler's _Float16 and no build flag has a say.
+ *   raw row     three planes, B then G then R, each `width` little-endian halfs: 6 * width bytes.
+ *   zip order   of a raw row: its even-indexed bytes followed by its odd-indexed ones - the low bytes of B, G, R over all x, then the high
+ *               bytes - and then t[i] = t[i] - t[i - 1] + 128 mod 256 for i >= 1 over the reordered values.  The predictor does not stop at a
+ *               plane's end or between low and high bytes.
+ *   zlib        a row's stream: 78 01, ONE dynamic-Huffman block with BFINAL = 1 - the frame's block header, the codes of the row's 6 * width
+ *               predicted bytes, end-of-block; literals only -, 0 bits up to the byte boundary, the big-endian Adler-32 of the predicted bytes.
+ *   table       one per frame, "PNG frames"' construction as it stands (gr_png_build_table; only BFINAL differs in the header): from the
+ *               histogram of ALL rows' predicted bytes plus one end-of-block a row.  Rows that end up stored raw are counted too: the table is
+ *               a function of the pixels alone.
+ *   raw rows    the format's own fallback: a reader tells a raw chunk from a compressed one by its size.  With c the bytes of a row's zlib
+ *               stream, the chunk holds the stream when c < 6 * width and otherwise the 6 * width raw bytes, neither reordered nor
+ *               predicted.  c follows from the row's histogram before a bit is packed (width 1: always raw).
+ *   bound       gr_exr_encode_bound = 313 + 8 * height + height * (8 + 6 * width): every row raw.  Exact, not an estimate.
+ * The launches (one workgroup of 256 lanes a row in both): gr_exr_histogram - a pixel a lane: the six predicted bytes of its b, g, r counted
+ * in LDS, the row's histogram stored and added to the frame's, the Adler-32's sums reduced mod 65521 - and gr_exr_pack, which writes every
+ * chunk with its header at the byte offset the host gives it: a compressed row as bits in stream order, four consecutive bytes of the
+ * reordered row a lane, through the PNG encoder's bit-packer; a raw row as 32-bit words of halfs. */
+typedef struct gr_exr_encoder gr_exr_encoder;
+/* What no file of this size exceeds - the size of the file whose every row is stored raw: the capacity both encoders ask for. */
+int gr_exr_encode_bound(int width, int height, size_t* bytes);
+/* The half conversion on its own: out[i] = the bits of the half of values[i] as defined above. */
+int gr_exr_half_bits(const float* values, size_t count, unsigned short* out);
+/* The host encoder: the definition of the bytes above.  frame_rgba_f32: [height][width][4] floats, r, g, b, a; *out_bytes: the file's size.
+ * Both encoders refuse, before anything is written or any device call is made, with a message that names the entry point and the field: a
+ * NULL; a size below 1; a row of more than 2^31 - 1 raw bytes (6 a pixel); a capacity below gr_exr_encode_bound
+ * (GR_ERROR_BUFFER_TOO_SMALL; everything else GR_ERROR_INVALID_ARGUMENT); a frame pointer not aligned to 16 bytes.  out_file needs no
+ * alignment. */
+int gr_exr_encode_f32_host(const float* frame_rgba_f32, int width, int height, unsigned char* out_file, size_t capacity, size_t* out_bytes);
+/* gr_exr_encode_f32_host's file written to `path` (gr_write_frame_png's counterpart; the frame needs no alignment here). */
+int gr_write_frame_exr(const char* path, const float* frame_rgba_f32, int width, int height);
+/* A device encoder for frames of one size on the program's device: owns the device scratch (the rows' histograms and Adler sums, the table,
+ * the chunks' offsets, the chunk area) and a pinned staging buffer.  The program is borrowed and must outlive it. */
+int gr_exr_encoder_create(gr_program* p, int width, int height, gr_exr_encoder** out);
+void gr_exr_encoder_destroy(gr_exr_encoder* e);
+/* Encodes device_rgba_f32 (device memory, width x height float4 pixels, 16-byte aligned) into out_file (host memory): enqueues on `stream` -
+ * gr_exr_histogram, one download of the rows' histograms and Adler sums (1 KiB + 1 032 bytes a row), the table, the raw-or-compressed
+ * decisions and the chunks' offsets made on the host and uploaded, the chunk area zeroed, gr_exr_pack, the download of the chunks - and
+ * returns after the file's bytes are in out_file: it SYNCHRONISES that stream, twice.  Header and offset table are written by the host.
+ * The file is gr_exr_encode_f32_host's of the same pixels, byte for byte. */
+int gr_exr_encode_f32(gr_exr_encoder* e, void* stream, const void* device_rgba_f32, unsigned char* out_file, size_t capacity, size_t* out_bytes);
+/* Measurement and tests, as the PNG encoder's: _launch_ms gives the last timed encode's gr_exr_histogram and gr_exr_pack in milliseconds;
+ * _scratch_intact: *intact = 1 when every word of the chunk scratch outside the longest chunk area this encoder has made - the guard words in
+ * front of it and everything behind it - still holds what gr_exr_encoder_create wrote there. */
+int gr_exr_encoder_time_launches(gr_exr_encoder* e, int on);
+int gr_exr_encoder_launch_ms(gr_exr_encoder* e, float ms[2]);
+int gr_exr_encoder_scratch_intact(gr_exr_encoder* e, int* intact);
+
 /* ---- JPEG frames ----------------------------------------------------------------------------------------------------------------------
  * A baseline JPEG encoder behind an RGBA8 frame that is already in device memory - the three sources the PNG encoder takes - and a
  * Motion-JPEG AVI writer for a sequence of such files: colour conversion, DCT, quantiser, Huffman coding and byte stuffing run on the device
