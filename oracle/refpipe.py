@@ -43,7 +43,8 @@ def _p(a):
 
 class OraclePipeline:
     def __init__(self, so_path):
-        self.lib = ctypes.CDLL(so_path)
+        """so_path: the library's path, or a library that is loaded already"""
+        self.lib = so_path if isinstance(so_path, ctypes.CDLL) else ctypes.CDLL(so_path)
 
     def frame(self, width, height, cfg_values, features_bytes, camera_pos=(0, 0, -4, 0), camera_quat=None, use_prepass=False,
               background=None, max_probes=8, nthreads=8, flip=0.0, basis_speed=(0, 0, 0), stages="all"):
@@ -180,6 +181,46 @@ class OraclePipeline:
         self.lib.ref_get_geodesic_path_f64(_p(ray), _p(path), _p(vel), _p(ds), _p(rcount), max_len, _p(cfg), _p(dfg), _p(count))
         n = int(count[0])
         return path[:n].copy(), vel[:n].copy(), ds[:n].copy()
+
+    def geodesic_path(self, ray, cfg_values, features_bytes, max_len):
+        """ref_get_geodesic_path from an initial ray made by hand -> (positions [n, 4], velocities [n, 4], step lengths [n]) in fp32"""
+        cfg = np.array(list(cfg_values) if len(cfg_values) else [0.0], dtype="<f4")
+        dfg = np.frombuffer(features_bytes, dtype=np.uint8).copy()
+        ray = np.ascontiguousarray(ray, dtype=LIGHTRAY_DTYPE)
+        rcount = np.array([1], dtype="<i4")
+        path, vel, ds = np.zeros((max_len, 4), dtype="<f4"), np.zeros((max_len, 4), dtype="<f4"), np.zeros(max_len, dtype="<f4")
+        count = np.zeros(1, dtype="<i4")
+        self.lib.ref_get_geodesic_path(_p(ray), _p(path), _p(vel), _p(ds), _p(rcount), max_len, _p(cfg), _p(dfg), _p(count))
+        n = int(count[0])
+        return path[:n].copy(), vel[:n].copy(), ds[:n].copy()
+
+    def parallel_transport(self, path, velocity, ds, quantity, count, cfg_values, fill=0.0):
+        """ref_parallel_transport_quantity of one observer on arrays made by hand (tests/observer_path_model.py): the first `count` of
+        the samples are the path -> records [len(path), 4], `fill` where none was written"""
+        cfg = np.array(list(cfg_values) if len(cfg_values) else [0.0], dtype="<f4")
+        path, velocity = np.ascontiguousarray(path, dtype="<f4"), np.ascontiguousarray(velocity, dtype="<f4")
+        ds, quantity = np.ascontiguousarray(ds, dtype="<f4"), np.ascontiguousarray(quantity, dtype="<f4")
+        assert 0 <= count <= len(path) == len(velocity) == len(ds) and len(path) >= 1
+        out = np.full((len(path), 4), fill, dtype="<f4")
+        cnt = np.array([count], dtype="<i4")
+        self.lib.ref_parallel_transport_quantity(_p(path), _p(velocity), _p(ds), _p(quantity), _p(cnt), _p(out), _p(cfg))
+        return out
+
+    def interpolate(self, path, velocity, ds, legs, target_time, count, parallel_transport, basis_speed, cfg_values, fill=0.0):
+        """ref_handle_interpolating_geodesic on arrays made by hand: legs [4, n, 4] -> (camera [4], tetrad [4, 4], velocity [4]), `fill`
+        where nothing was written"""
+        cfg = np.array(list(cfg_values) if len(cfg_values) else [0.0], dtype="<f4")
+        path, velocity = np.ascontiguousarray(path, dtype="<f4"), np.ascontiguousarray(velocity, dtype="<f4")
+        ds, legs = np.ascontiguousarray(ds, dtype="<f4"), np.ascontiguousarray(legs, dtype="<f4")
+        assert 0 <= count <= len(path) == len(velocity) == len(ds) == legs.shape[1] and len(path) >= 1
+        speed = np.zeros(4, dtype="<f4")
+        speed[:3] = basis_speed
+        cam, vel, e = np.full(4, fill, dtype="<f4"), np.full(4, fill, dtype="<f4"), np.full((4, 4), fill, dtype="<f4")
+        cnt = np.array([count], dtype="<i4")
+        self.lib.ref_handle_interpolating_geodesic(_p(path), _p(velocity), _p(ds), _p(cam), _p(legs[0]), _p(legs[1]), _p(legs[2]), _p(legs[3]),
+                                                   _p(e[0]), _p(e[1]), _p(e[2]), _p(e[3]), ctypes.c_float(target_time), _p(cnt),
+                                                   int(bool(parallel_transport)), _p(speed), _p(vel), _p(cfg))
+        return cam, e, vel
 
     def geodesic_camera(self, cfg_values, features_bytes, camera_pos=(0, 0, -4, 0), basis_speed=(0, 0, 0), max_len=4096,
                         target_times=(), parallel_transport=True, flip=0.0):
