@@ -407,6 +407,18 @@ __device__ __forceinline__ float exact_ratio(int a, int b) {
     return (float)((double)a / (double)b);
 }
 
+// The prepass cell a pixel coordinate looks at: round(c / n * pn) (cl.cl:3217-3221), the quotient and the product each rounded to fp32
+// before the next step - the ONE statement of the rule, for every consumer of the grid.  The product passes through a register the
+// compiler knows nothing about: written as roundf(fx * pn) under -ffp-contract=fast the multiply was fused into roundf's own
+// "x - trunc(x)", the tie was decided by the unrounded product, and a pixel exactly half way between two cells (every 16th column
+// of a frame whose width is a multiple of 16) whose quotient had been rounded down went to the cell below the one the reference's
+// build sends it to: fl32(56 / 96) * 6 = 3.49999988 exactly, 3.5 in fp32.  tests/prepass_model.py: cell_of.
+__device__ __forceinline__ int prepass_cell_of(int c, int n, int pn) {
+    float product = exact_ratio(c, n) * (float)pn;
+    asm volatile("" : "+v"(product));
+    return (int)roundf(product);
+}
+
 __device__ __forceinline__ int early_terminate(int x, int y, int w, int h, const int* __restrict__ term) {
     if (x < 0 || y < 0 || x > w - 1 || y > h - 1) return 0;
     return term[y * w + x] == 1;

@@ -149,10 +149,8 @@ extern "C" __global__ void __launch_bounds__(GR_INIT_BLOCK) gr_init_rays_generic
             ray = make_pixel_ray(cx, cy, width, height, *g_generic_camera_in, *g_camera_quat, *e0, *e1, *e2, *e3, flip_geodesic_direction, cfg, dfg);
             // prepass stencil (cl.cl:3213-3232)
             if (prepass_width != width && prepass_height != height) {
-                float fx = exact_ratio(cx, width);
-                float fy = exact_ratio(cy, height);
-                int lx = (int)roundf(fx * prepass_width);
-                int ly = (int)roundf(fy * prepass_height);
+                int lx = prepass_cell_of(cx, width, prepass_width);
+                int ly = prepass_cell_of(cy, height, prepass_height);
                 if (early_terminate(lx - 1, ly, prepass_width, prepass_height, termination_buffer) &&
                     early_terminate(lx, ly, prepass_width, prepass_height, termination_buffer) &&
                     early_terminate(lx + 1, ly, prepass_width, prepass_height, termination_buffer) &&
@@ -621,10 +619,8 @@ __device__ __forceinline__ void trace_tile(int wave, int lane, const float4* __r
     const bool looks_at_cells = cell_wave < 0 && !(LATTICE_RAYS && guess_wave >= 0) && !known_skipped && !pending_only && !(PARKING && from_lot) && termination_buffer && prepass_width != width &&
                                 prepass_height != height;
     if (looks_at_cells && !speculative) {
-        float fx = exact_ratio(cx, width);
-        float fy = exact_ratio(cy, height);
-        int lx = (int)roundf(fx * prepass_width);
-        int ly = (int)roundf(fy * prepass_height);
+        int lx = prepass_cell_of(cx, width, prepass_width);
+        int ly = prepass_cell_of(cy, height, prepass_height);
         const bool skip = cells_in_flight ? early_terminate_stencil_when_known(lx, ly, prepass_width, prepass_height, termination_buffer)
                                           : early_terminate_stencil(lx, ly, prepass_width, prepass_height, termination_buffer);
         if (skip) terminated = 2;
@@ -733,7 +729,7 @@ __device__ __forceinline__ void trace_tile(int wave, int lane, const float4* __r
         }
         if (looks_at_cells && speculative) {
             // the verdict, after the fact: by now the cells' rays have usually ended too (they are as long as this tile's, and began with it)
-            const int lx = (int)roundf(exact_ratio(cx, width) * prepass_width), ly = (int)roundf(exact_ratio(cy, height) * prepass_height);
+            const int lx = prepass_cell_of(cx, width, prepass_width), ly = prepass_cell_of(cy, height, prepass_height);
             if (early_terminate_stencil_when_known(lx, ly, prepass_width, prepass_height, termination_buffer)) {
                 dat.tex_coord = make_float2(0, 0);
                 dat.z_shift = 0;
@@ -985,10 +981,8 @@ __device__ __forceinline__ bool trace_slot_to_pixel(unsigned int slot, int width
 __device__ __forceinline__ bool prepass_skips_pixel(int cx, int cy, int width, int height, const int* __restrict__ termination_buffer,
                                                     int prepass_width, int prepass_height) {
     if (!termination_buffer || prepass_width == width || prepass_height == height) return false;
-    float fx = exact_ratio(cx, width);
-    float fy = exact_ratio(cy, height);
-    int lx = (int)roundf(fx * prepass_width);
-    int ly = (int)roundf(fy * prepass_height);
+    int lx = prepass_cell_of(cx, width, prepass_width);
+    int ly = prepass_cell_of(cy, height, prepass_height);
     return early_terminate_stencil(lx, ly, prepass_width, prepass_height, termination_buffer);
 }
 
@@ -1208,7 +1202,7 @@ __device__ __forceinline__ int tile_cost_class(int tile, int width, int height, 
     if (!trace_slot_to_pixel((unsigned)tile * 64u + 36u, width, height, block_rows, strip_rank, strip_count, cx, cy) &&
         !trace_slot_to_pixel((unsigned)tile * 64u, width, height, block_rows, strip_rank, strip_count, cx, cy))
         return GR_TILE_CLASSES - 1;   // padding: nothing to trace
-    const int lx = (int)roundf(exact_ratio(cx, width) * prepass_width), ly = (int)roundf(exact_ratio(cy, height) * prepass_height);
+    const int lx = prepass_cell_of(cx, width, prepass_width), ly = prepass_cell_of(cy, height, prepass_height);
     // the halo pieces of a split frame are 64 pixels of one row, not a tile: four cells wide, so the promise of the last class
     // (below) cannot be made for them
     const int tiles_in_block = ((width + GR_TILE - 1) / GR_TILE) * (block_rows / GR_TILE);
