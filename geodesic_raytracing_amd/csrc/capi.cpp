@@ -991,16 +991,6 @@ const void* gr_internal::no_count_of(const gr_program* p) { return p->huge_count
 }
 using gr_internal::blocks, gr_internal::launch;
 
-// A launcher refuses a NULL where its kernel dereferences unconditionally: the reference's clSetKernelArg returns CL_INVALID_MEM_OBJECT
-// for a null buffer, a HIP launch takes it and the device faults (and a device fault ends the process).  cfg / dfg are not checked:
-// a substituted program reads neither.
-static int need(const char* who, std::initializer_list<const void*> buffers) {
-    for (const void* b : buffers)
-        if (!b) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a required buffer is NULL");
-    return GR_OK;
-}
-#define GR_NEED(who, ...) do { int rc_ = need(who, {__VA_ARGS__}); if (rc_ != GR_OK) return rc_; } while (0)
-
 int gr_cart_to_generic(gr_program* p, void* stream, const void* in, void* out, int count, float flip, const void* cfg) {
     GR_NEED("gr_cart_to_generic", in, out);
     void* args[] = {&in, &out, &count, &flip, &cfg};
@@ -1071,162 +1061,7 @@ int gr_handle_adaptive_sampling(gr_program* p, void* stream, const void* rays, c
     return launch(p, K_ADAPTIVE, stream, blocks(width / 2, 8), blocks(height / 2, 8), 8, 8, args);
 }
 
-int gr_render(gr_program* p, void* stream, const void* rdata, const void* rdata_count, int num_pixels, void* out,
-              const void* bg1, const void* bg2, int bg_width, int bg_height, int bg_levels, int width, int height,
-              int max_probes, const void* cfg, const void* dfg) {
-    GR_NEED("gr_render", rdata, rdata_count, out, bg1, bg2);
-    if (bg_width <= 0 || bg_height <= 0 || bg_levels <= 0) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_render: the background's width, height and levels");
-    int block_pixels = num_pixels > 0 ? num_pixels : 1, rank = 0, count = 1, compact = 0, seams_only = 0;
-    void* args[] = {&rdata, &rdata_count, &out, &bg1, &bg2, &bg_width, &bg_height, &bg_levels, &width, &height,
-                    &max_probes, &cfg, &dfg, &num_pixels, &block_pixels, &rank, &count, &compact, &seams_only};
-    return launch(p, K_RENDER, stream, blocks(num_pixels, 256), 1, 256, 1, args);
-}
-
-int gr_strip_local_blocks(int height, int block_rows, int strip_rank, int strip_count) {
-    if (block_rows <= 0 || strip_count <= 0) return 0;
-    int total = (height + block_rows - 1) / block_rows;
-    return strip_rank < total ? (total - strip_rank + strip_count - 1) / strip_count : 0;
-}
-
-// strip mode: render_data is indexed by pixel; shade this device's row blocks (block-cyclic)
-int gr_render_strips(gr_program* p, void* stream, const void* rdata, void* out, const void* bg1, const void* bg2, int bg_width,
-                     int bg_height, int bg_levels, int width, int height, int block_rows, int strip_rank, int strip_count,
-                     int compact_out, int max_probes, const void* cfg, const void* dfg) {
-    if (block_rows <= 0 || strip_count <= 0 || strip_rank < 0 || strip_rank >= strip_count)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "bad strip parameters");
-    int local_blocks = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count);
-    int block_pixels = block_rows * width;
-    int num = local_blocks * block_pixels;
-    const void* rdata_count = p ? p->huge_count : nullptr;
-    int seams_only = 0;
-    void* args[] = {&rdata, &rdata_count, &out, &bg1, &bg2, &bg_width, &bg_height, &bg_levels, &width, &height,
-                    &max_probes, &cfg, &dfg, &num, &block_pixels, &strip_rank, &strip_count, &compact_out, &seams_only};
-    return launch(p, K_RENDER, stream, blocks(num, 256), 1, 256, 1, args);
-}
-
-// ---- the analytic sky (geodesic_hip_internal.h, "Analytic sky") ------------------------------------------------------------------------
-int gr_analytic_sky_default(gr_analytic_sky* out) {
-    if (!out) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_analytic_sky_default: null argument");
-    static const float quadrants[2][4][3] = {{{0.16f, 0.30f, 0.62f}, {0.66f, 0.26f, 0.20f}, {0.20f, 0.52f, 0.32f}, {0.72f, 0.60f, 0.22f}},
-                                             {{0.52f, 0.24f, 0.58f}, {0.22f, 0.56f, 0.60f}, {0.76f, 0.46f, 0.18f}, {0.40f, 0.62f, 0.24f}}};
-    out->meridians = 36;
-    out->parallels = 18;
-    out->line_width = 0.08f;
-    memcpy(out->quadrant, quadrants, sizeof(quadrants));
-    for (int side = 0; side < 2; side++)
-        for (int c = 0; c < 3; c++) out->line[side][c] = 0.02f;
-    return GR_OK;
-}
-
-// what every entry point that takes a sky refuses of it, under its own name
-extern "C" int gr_internal_check_analytic_sky(const char* who, const gr_analytic_sky* sky) {
-    const std::string w = who;
-    if (!sky) return fail(GR_ERROR_INVALID_ARGUMENT, w + ": null sky");
-    if (sky->meridians < 2 || sky->meridians > 360) return fail(GR_ERROR_INVALID_ARGUMENT, w + ": meridians " + std::to_string(sky->meridians) + " (2 to 360)");
-    if (sky->parallels < 1 || sky->parallels > 180) return fail(GR_ERROR_INVALID_ARGUMENT, w + ": parallels " + std::to_string(sky->parallels) + " (1 to 180)");
-    if (!(sky->line_width >= 0.f && sky->line_width <= 0.5f)) return fail(GR_ERROR_INVALID_ARGUMENT, w + ": line_width " + std::to_string(sky->line_width) + " (0 to 0.5)");
-    for (int side = 0; side < 2; side++) {
-        for (int q = 0; q < 4; q++)
-            for (int c = 0; c < 3; c++)
-                if (!(sky->quadrant[side][q][c] >= 0.f && sky->quadrant[side][q][c] <= 1.f))
-                    return fail(GR_ERROR_INVALID_ARGUMENT, w + ": quadrant[" + std::to_string(side) + "][" + std::to_string(q) + "][" + std::to_string(c) + "] is not in [0, 1]");
-        for (int c = 0; c < 3; c++)
-            if (!(sky->line[side][c] >= 0.f && sky->line[side][c] <= 1.f))
-                return fail(GR_ERROR_INVALID_ARGUMENT, w + ": line[" + std::to_string(side) + "][" + std::to_string(c) + "] is not in [0, 1]");
-    }
-    return GR_OK;
-}
-
-int gr_render_analytic(gr_program* p, void* stream, const void* rdata, const void* rdata_count, int num_pixels, void* out, const gr_analytic_sky* sky,
-                       int width, int height, const void* cfg, const void* dfg) {
-    GR_NEED("gr_render_analytic", rdata, rdata_count, out);
-    int rc = gr_internal_check_analytic_sky("gr_render_analytic", sky);
-    if (rc != GR_OK) return rc;
-    gr_analytic_sky by_value = *sky;
-    int block_pixels = num_pixels > 0 ? num_pixels : 1, rank = 0, count = 1, compact = 0;
-    void* args[] = {&rdata, &rdata_count, &out, &by_value, &width, &height, &cfg, &dfg, &num_pixels, &block_pixels, &rank, &count, &compact};
-    return launch(p, K_RENDER_ANALYTIC, stream, blocks(num_pixels, 256), 1, 256, 1, args);
-}
-
-int gr_render_analytic_strips(gr_program* p, void* stream, const void* rdata, void* out, const gr_analytic_sky* sky, int width, int height,
-                              int block_rows, int strip_rank, int strip_count, int compact_out, const void* cfg, const void* dfg) {
-    GR_NEED("gr_render_analytic_strips", rdata, out);
-    int rc = gr_internal_check_analytic_sky("gr_render_analytic_strips", sky);
-    if (rc != GR_OK) return rc;
-    if (block_rows <= 0 || strip_count <= 0 || strip_rank < 0 || strip_rank >= strip_count)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_analytic_strips: bad strip parameters");
-    gr_analytic_sky by_value = *sky;
-    int local_blocks = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count);
-    int block_pixels = block_rows * width;
-    int num = local_blocks * block_pixels;
-    const void* rdata_count = p ? p->huge_count : nullptr;
-    void* args[] = {&rdata, &rdata_count, &out, &by_value, &width, &height, &cfg, &dfg, &num, &block_pixels, &strip_rank, &strip_count, &compact_out};
-    return launch(p, K_RENDER_ANALYTIC, stream, blocks(num, 256), 1, 256, 1, args);
-}
-
-namespace {
-// steps 2 and 3 of the definition, in double
-double sky_line_coverage(double x, double h, int n, double w) {
-    const double t = x * n, a = h * n;
-    auto covered_below = [&](double at) { const double s = at + w / 2, k = std::floor(s); return k * w + std::min(s - k, w); };
-    return (covered_below(t + a) - covered_below(t - a)) / (2 * a);
-}
-double sky_upper_half_share(double x, double h, bool periodic) {
-    auto below = [&](double at) { const double k = periodic ? std::floor(at) : 0.0; return k / 2 + std::max(at - k - 0.5, 0.0); };
-    return (below(x + h) - below(x - h)) / (2 * h);
-}
-}   // namespace
-
-int gr_analytic_sky_image(const gr_analytic_sky* sky, int side, int width, int height, unsigned char* out_rgba8) {
-    int rc = gr_internal_check_analytic_sky("gr_analytic_sky_image", sky);
-    if (rc != GR_OK) return rc;
-    if (!out_rgba8) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_analytic_sky_image: null out_rgba8");
-    if (side != 0 && side != 1) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_analytic_sky_image: side " + std::to_string(side) + " (0 or 1)");
-    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_analytic_sky_image: width and height");
-    const double floor_h = std::ldexp(1.0, -14);
-    const double hu = std::max(0.5 / width, floor_h), hv = std::max(0.5 / height, floor_h);
-    std::vector<double> cu(width), fu(width);
-    for (int x = 0; x < width; x++) {
-        const double u = (x + 0.5) / width;
-        cu[x] = sky_line_coverage(u, hu, sky->meridians, sky->line_width);
-        fu[x] = sky_upper_half_share(u, hu, true);
-    }
-    for (int y = 0; y < height; y++) {
-        const double v = (y + 0.5) / height;
-        const double cv = sky_line_coverage(v, hv, sky->parallels, sky->line_width), fv = sky_upper_half_share(v, hv, false);
-        for (int x = 0; x < width; x++) {
-            const double g = 1 - (1 - cu[x]) * (1 - cv);
-            const double weight[4] = {(1 - fu[x]) * (1 - fv), fu[x] * (1 - fv), (1 - fu[x]) * fv, fu[x] * fv};
-            unsigned char* px = out_rgba8 + ((size_t)y * width + x) * 4;
-            for (int c = 0; c < 3; c++) {
-                double base = 0;
-                for (int q = 0; q < 4; q++) base += weight[q] * sky->quadrant[side][q][c];
-                const double value = base + (sky->line[side][c] - base) * g;
-                px[c] = (unsigned char)std::lround(std::min(std::max(value, 0.0), 1.0) * 255.0);
-            }
-            px[3] = 255;
-        }
-    }
-    return GR_OK;
-}
-
-// the pixels gr_trace_fused_launch's in-tile shading leaves: last column and last row of every 8x8 tile of this device's blocks
-int gr_render_seams(gr_program* p, void* stream, const void* rdata, void* out, const void* bg1, const void* bg2, int bg_width,
-                    int bg_height, int bg_levels, int width, int height, int block_rows, int strip_rank, int strip_count,
-                    int compact_out, int max_probes, const void* cfg, const void* dfg) {
-    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = ((height + 7) / 8) * 8; }
-    if (block_rows <= 0 || block_rows % 8 != 0 || strip_rank < 0 || strip_rank >= strip_count || width <= 0 || width % 8 != 0)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_seams: width and block_rows must be multiples of 8");
-    int local_blocks = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count);
-    int block_pixels = block_rows * width;
-    long long items = (long long)local_blocks * (width / 8) * (block_rows / 8) * 15;
-    if (items > 0x7fffffff) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_seams: image too large");
-    int num = (int)items, seams_only = 1;
-    const void* rdata_count = p ? p->huge_count : nullptr;
-    void* args[] = {&rdata, &rdata_count, &out, &bg1, &bg2, &bg_width, &bg_height, &bg_levels, &width, &height,
-                    &max_probes, &cfg, &dfg, &num, &block_pixels, &strip_rank, &strip_count, &compact_out, &seams_only};
-    return launch(p, K_RENDER, stream, blocks(num, 256), 1, 256, 1, args);
-}
+// (the shading pass's launchers - gr_render and its kin, gr_strip_local_blocks, the analytic sky - are in shading.cpp)
 
 // What the resolve, present and accumulate launchers below refuse alike, before any device call: a NULL buffer; a NULL program where the
 // launcher answers for it under its own name (launch() refuses it for the others); a factor outside 1 ... 4; a size below 1 or with more

@@ -1501,24 +1501,36 @@ static int fused_trace(frame_context& f) {
     return f.end(GR_STAGE_TRACE);
 }
 
-static int fused_shade(frame_context& f) {
+// f.out shaded from the state's records by the sky the state carries - stars, the analytic sky, else the texture (the setters refuse
+// two at once): the whole frame off the counted records (the reference-shaped sequence), or this device's strips of a fused frame
+static int shade_frame(frame_context& f, bool whole_frame) {
     gr_render_state* s = f.s;
     const auto& q = f.plan;
+    const int count = f.width * f.height, block_rows = q.strip_count > 1 ? q.block_rows : f.height;
     const int compact_out = q.strip_count > 1 ? f.opt.compact_out : 0;
+    if (s->stars_set)
+        return whole_frame ? gr_render_stars(f.p, f.stream, s->render_data, s->render_data_count, count, f.out, &s->star_sky, s->near_stars, s->far_stars,
+                                             f.width, f.height, s->cfg, s->dfg)
+                           : gr_render_stars_strips(f.p, f.stream, s->render_data, f.out, &s->star_sky, s->near_stars, s->far_stars, f.width, f.height,
+                                                    block_rows, q.strip_rank, q.strip_count, compact_out, s->cfg, s->dfg);
+    if (s->sky_set)
+        return whole_frame ? gr_render_analytic(f.p, f.stream, s->render_data, s->render_data_count, count, f.out, &s->sky, f.width, f.height, s->cfg, s->dfg)
+                           : gr_render_analytic_strips(f.p, f.stream, s->render_data, f.out, &s->sky, f.width, f.height, block_rows, q.strip_rank,
+                                                       q.strip_count, compact_out, s->cfg, s->dfg);
+    if (whole_frame)
+        return gr_render(f.p, f.stream, s->render_data, s->render_data_count, count, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height, f.bg_levels, f.width,
+                         f.height, f.opt.max_probes, s->cfg, s->dfg);
+    if (q.shade_in_trace)
+        return gr_render_seams(f.p, f.stream, s->render_data, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height, f.bg_levels, f.width, f.height, q.block_rows,
+                               q.strip_rank, q.strip_count, compact_out, f.opt.max_probes, s->cfg, s->dfg);
+    return gr_render_strips(f.p, f.stream, s->render_data, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height, f.bg_levels, f.width, f.height, block_rows,
+                            q.strip_rank, q.strip_count, compact_out, f.opt.max_probes, s->cfg, s->dfg);
+}
+
+static int fused_shade(frame_context& f) {
     if (!f.out) return GR_OK;
     GR_CHECK(f.begin(GR_STAGE_RENDER));
-    if (s->stars_set)
-        GR_CHECK(gr_render_stars_strips(f.p, f.stream, s->render_data, f.out, &s->star_sky, s->near_stars, s->far_stars, f.width, f.height,
-                                        q.strip_count > 1 ? q.block_rows : f.height, q.strip_rank, q.strip_count, compact_out, s->cfg, s->dfg));
-    else if (s->sky_set)
-        GR_CHECK(gr_render_analytic_strips(f.p, f.stream, s->render_data, f.out, &s->sky, f.width, f.height, q.strip_count > 1 ? q.block_rows : f.height,
-                                           q.strip_rank, q.strip_count, compact_out, s->cfg, s->dfg));
-    else if (q.shade_in_trace)
-        GR_CHECK(gr_render_seams(f.p, f.stream, s->render_data, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height, f.bg_levels, f.width, f.height, q.block_rows,
-                                 q.strip_rank, q.strip_count, compact_out, f.opt.max_probes, s->cfg, s->dfg));
-    else
-        GR_CHECK(gr_render_strips(f.p, f.stream, s->render_data, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height, f.bg_levels, f.width, f.height,
-                                  q.strip_count > 1 ? q.block_rows : f.height, q.strip_rank, q.strip_count, compact_out, f.opt.max_probes, s->cfg, s->dfg));
+    GR_CHECK(shade_frame(f, false));
     return f.end(GR_STAGE_RENDER);
 }
 
@@ -1632,14 +1644,7 @@ static int render_reference_shaped(frame_context& f) {
 
     if (f.out) {
         GR_CHECK(f.begin(GR_STAGE_RENDER));
-        if (s->stars_set)
-            GR_CHECK(gr_render_stars(p, stream, s->render_data, s->render_data_count, width * height, f.out, &s->star_sky, s->near_stars, s->far_stars, width, height,
-                                     s->cfg, s->dfg));
-        else if (s->sky_set)
-            GR_CHECK(gr_render_analytic(p, stream, s->render_data, s->render_data_count, width * height, f.out, &s->sky, width, height, s->cfg, s->dfg));
-        else
-            GR_CHECK(gr_render(p, stream, s->render_data, s->render_data_count, width * height, f.out, f.bg1, f.bg2, f.bg_width, f.bg_height,
-                               f.bg_levels, width, height, f.opt.max_probes, s->cfg, s->dfg));
+        GR_CHECK(shade_frame(f, true));
         GR_CHECK(f.end(GR_STAGE_RENDER));
     }
     return GR_OK;

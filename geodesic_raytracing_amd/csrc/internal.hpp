@@ -3,13 +3,14 @@
 // files (png_stream.cpp, exr_stream.cpp, jpeg_stream.cpp, imageio.cpp) include it and compile alone; the macros name HIP only where they are expanded.
 #pragma once
 
+#include <initializer_list>
 #include <string>
 
 #include "../../include/geodesic_hip_internal.h"
 
 extern "C" {
 int gr_internal_fail(int code, const char* msg);   // capi.cpp: the text behind gr_last_error; returns code
-int gr_internal_check_analytic_sky(const char* who, const gr_analytic_sky* sky);   // capi.cpp: what every taker of a sky refuses
+int gr_internal_check_analytic_sky(const char* who, const gr_analytic_sky* sky);   // shading.cpp: what every taker of a sky refuses
 int gr_internal_check_star_sky(const char* who, const gr_star_sky* sky, const gr_star_catalogue* near, const gr_star_catalogue* far, const gr_program* p);   // star_catalogue.cpp
 int gr_internal_render_state_size(const gr_render_state* s, int* width, int* height);   // frame.cpp
 const char* gr_internal_filter_table_error(int factor, const float* taps, int count);   // imageio.cpp: NULL for nothing wrong
@@ -31,6 +32,7 @@ int gr_internal_render_frame_as(int format, int layout, gr_render_state* s, gr_p
         int _rc = (expr);             \
         if (_rc != GR_OK) return _rc; \
     } while (0)
+#define GR_NEED(who, ...) GR_CHECK(gr_internal::need(who, {__VA_ARGS__}))
 
 // a program's kernels, in the order of capi.cpp's KERNEL_NAMES
 enum KernelId {
@@ -51,4 +53,20 @@ int launch(gr_program* p, int k, void* stream, unsigned gx, unsigned gy, unsigne
 int device_of(const gr_program* p);
 const void* no_count_of(const gr_program* p);   // the device int INT_MAX that a range launch hands its kernel as the records' count
 inline unsigned blocks(long long n, int b) { return n <= 0 ? 0u : (unsigned)((n + b - 1) / b); }
+// A launcher refuses a NULL where its kernel dereferences unconditionally: the reference's clSetKernelArg returns CL_INVALID_MEM_OBJECT
+// for a null buffer, a HIP launch takes it and the device faults (and a device fault ends the process).  cfg / dfg are not checked:
+// a substituted program reads neither.
+inline int need(const char* who, std::initializer_list<const void*> buffers) {
+    for (const void* b : buffers)
+        if (!b) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(who) + ": a required buffer is NULL").c_str());
+    return GR_OK;
+}
+// what gr_render_stars takes of a catalogue, by value (star_catalogue_view of kernels/shading.hip, field for field)
+struct catalogue_view {
+    const int* cell_start;
+    const void* stars;
+    const double* table;
+    int n, cells_u, cells_v;
+};
+catalogue_view view_of(const gr_star_catalogue* c);   // star_catalogue.cpp; a NULL catalogue: n = 0 and no pointers
 }  // namespace gr_internal

@@ -169,6 +169,34 @@ __device__ __forceinline__ float wrapped_difference(float a, float b) {
     return (float)((double)(1.f * wrapped) / (2 * GR_PI));
 }
 
+// The colour tail every sky ends in, for a colour in linear light: the redshift where the feature is on, then the frame's coding
+// (sRGB unless LINEAR_FRAMEBUFFER)
+__device__ __forceinline__ float3 finish_linear_colour(float3 linear, float z_shift, dfg_t dfg) {
+    if (GET_FEATURE(redshift, dfg)) linear = apply_redshift(linear, z_shift, dfg);
+#ifndef LINEAR_FRAMEBUFFER
+    linear = linear_to_srgb(linear);
+#endif
+    return linear;
+}
+// ... and for an sRGB-coded colour (a texel, a colour of the C ABI): decoded for the tail, or passed through untouched where neither
+// the redshift nor the frame wants linear light
+__device__ __forceinline__ float3 finish_srgb_colour(float3 srgb, float z_shift, dfg_t dfg) {
+    if (GET_FEATURE(redshift, dfg)) return finish_linear_colour(srgb_to_linear(srgb), z_shift, dfg);
+#ifdef LINEAR_FRAMEBUFFER
+    return srgb_to_linear(srgb);
+#else
+    return srgb;
+#endif
+}
+
+// Half the footprint's size along u and v (x, y of the result) for the skies that integrate over a box: the mean size of the
+// differences to the two neighbours, no smaller than `floor`.  Only sizes enter, so a previous neighbour (last column / row) needs no sign.
+__device__ __forceinline__ float2 footprint_half_sizes(const render_data& self, float2 beside, float2 below, float floor) {
+    const float u = self.tex_coord.x, v = self.tex_coord.y;
+    return make_float2(__builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(u, beside.x)) + __builtin_fabsf(wrapped_difference(u, below.x))), floor),
+                       __builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(v, beside.y)) + __builtin_fabsf(wrapped_difference(v, below.y))), floor));
+}
+
 // One pixel: `self` is its record, `beside` / `below` the texture coordinates of its horizontal / vertical neighbour - the next
 // pixel, or the previous one at the last column / row (`beside_is_previous`, `below_is_previous`), cl.cl:5509-5546.
 __device__ float4 shade_pixel(const render_data& self, float2 beside, bool beside_is_previous, float2 below, bool below_is_previous,
@@ -183,17 +211,7 @@ __device__ float4 shade_pixel(const render_data& self, float2 beside, bool besid
     along_x.x *= sky.width; along_y.x *= sky.width;
     along_x.y *= sky.height; along_y.y *= sky.height;
     float4 colour = integrate_footprint(sky, self.tex_coord, pixel_footprint(along_x, along_y), most_probes);
-    float3 rgb = f3(colour.x, colour.y, colour.z);
-    if (GET_FEATURE(redshift, dfg)) {
-        rgb = apply_redshift(srgb_to_linear(rgb), self.z_shift, dfg);
-#ifndef LINEAR_FRAMEBUFFER
-        rgb = linear_to_srgb(rgb);
-#endif
-    } else {
-#ifdef LINEAR_FRAMEBUFFER
-        rgb = srgb_to_linear(rgb);
-#endif
-    }
+    const float3 rgb = finish_srgb_colour(f3(colour.x, colour.y, colour.z), self.z_shift, dfg);
     return f4(rgb.x, rgb.y, rgb.z, colour.w);
 }
 
@@ -203,15 +221,18 @@ __device__ __attribute__((noinline)) float4 shade_pixel_in_tile(const render_dat
     return shade_pixel(self, beside, false, below, false, near_sky, far_sky, shading.most_probes, dfg);
 }
 
+#if GR_FRAME_KERNELS
+// What a work item of a shading launch shades: the launch contract of gr_render, gr_render_analytic and gr_render_stars alike.
 // The launch of the reference (num_pixels = block_pixels = width * height, strip_rank 0, strip_count 1, compact_out 0) shades the
 // whole image; the extension shades one device's row blocks of a split image: work item gid is pixel `off` of local block `lb`,
 // the global block being lb * strip_count + strip_rank, and with compact_out the device's blocks are written back to back.
-#if GR_FRAME_KERNELS
-extern "C" __global__ void gr_render(const render_data* __restrict__ rdata, const int* __restrict__ rdata_count, float4* __restrict__ out,
-                                     const uchar4* __restrict__ bg1_texels, const uchar4* __restrict__ bg2_texels,
-                                     int bg_width, int bg_height, int bg_levels,
-                                     int width, int height, int most_probes, cfg_t cfg, dfg_t dfg,
-                                     int num_pixels, int block_pixels, int strip_rank, int strip_count, int compact_out, int seams_only) {
+// An item with work ends in shade(self, out_index, beside, below, last_column, last_row), the neighbours as shade_pixel takes them.
+// (The shader is handed in, not a flag handed back: a flag tested after the call stays a lane mask in the compiled kernels, which grow.)
+// A kernel without seams passes a literal 0 for seams_only and that branch folds away.
+template <class Shade>
+__device__ __forceinline__ void shading_work_item(int num_pixels, int block_pixels, int strip_rank, int strip_count, int compact_out, int seams_only,
+                                                  const render_data* __restrict__ rdata, const int* __restrict__ rdata_count, int width, int height,
+                                                  Shade shade) {
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= num_pixels) return;
     int lb, off;
@@ -242,8 +263,19 @@ extern "C" __global__ void gr_render(const render_data* __restrict__ rdata, cons
         beside = rdata[py * width + px + (last_column ? (width > 1 ? -1 : 0) : 1)].tex_coord;
         below = rdata[(py + (last_row ? (height > 1 ? -1 : 0) : 1)) * width + px].tex_coord;
     }
-    const sky_sampler near_sky{bg1_texels, bg_width, bg_height, bg_levels}, far_sky{bg2_texels, bg_width, bg_height, bg_levels};
-    out[out_index] = shade_pixel(self, beside, last_column, below, last_row, near_sky, far_sky, most_probes, dfg);
+    shade(self, out_index, beside, below, last_column, last_row);
+}
+
+extern "C" __global__ void gr_render(const render_data* __restrict__ rdata, const int* __restrict__ rdata_count, float4* __restrict__ out,
+                                     const uchar4* __restrict__ bg1_texels, const uchar4* __restrict__ bg2_texels,
+                                     int bg_width, int bg_height, int bg_levels,
+                                     int width, int height, int most_probes, cfg_t cfg, dfg_t dfg,
+                                     int num_pixels, int block_pixels, int strip_rank, int strip_count, int compact_out, int seams_only) {
+    shading_work_item(num_pixels, block_pixels, strip_rank, strip_count, compact_out, seams_only, rdata, rdata_count, width, height,
+                      [&](const render_data& self, int out_index, float2 beside, float2 below, bool last_column, bool last_row) __attribute__((always_inline)) {
+        const sky_sampler near_sky{bg1_texels, bg_width, bg_height, bg_levels}, far_sky{bg2_texels, bg_width, bg_height, bg_levels};
+        out[out_index] = shade_pixel(self, beside, last_column, below, last_row, near_sky, far_sky, most_probes, dfg);
+    });
     (void)cfg;
 }
 
@@ -283,13 +315,12 @@ __device__ __forceinline__ float upper_half_share(float x, float h, bool periodi
     return inside / (2.f * h);
 }
 
-// One pixel: `self`, `beside` and `below` as shade_pixel takes them.  Only the sizes of the differences enter, so a previous
-// neighbour (last column / row) needs no sign.
+// One pixel: `self`, `beside` and `below` as shade_pixel takes them
 __device__ __forceinline__ float4 shade_pixel_analytic(const render_data& self, float2 beside, float2 below, const analytic_sky& sky, dfg_t dfg) {
     if (self.terminated != 1) return f4(0, 0, 0, 1);
     const float floor_h = 6.103515625e-05f;   // 2^-14: keeps the result a continuous function of the record
-    const float hu = __builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(self.tex_coord.x, beside.x)) + __builtin_fabsf(wrapped_difference(self.tex_coord.x, below.x))), floor_h);
-    const float hv = __builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(self.tex_coord.y, beside.y)) + __builtin_fabsf(wrapped_difference(self.tex_coord.y, below.y))), floor_h);
+    const float2 half = footprint_half_sizes(self, beside, below, floor_h);
+    const float hu = half.x, hv = half.y;
     const float u = self.tex_coord.x, v = self.tex_coord.y;
     const float cu = line_coverage(u, hu, sky.meridians, sky.line_width), cv = line_coverage(v, hv, sky.parallels, sky.line_width);
     const float grid = 1.f - (1.f - cu) * (1.f - cv);
@@ -305,40 +336,19 @@ __device__ __forceinline__ float4 shade_pixel_analytic(const render_data& self, 
         const float base = w0 * q0 + w1 * q1 + w2 * q2 + w3 * q3;
         c[k] = base + (line - base) * grid;
     }
-    float3 rgb = f3(c[0], c[1], c[2]);
-    if (GET_FEATURE(redshift, dfg)) {
-        rgb = apply_redshift(srgb_to_linear(rgb), self.z_shift, dfg);
-#ifndef LINEAR_FRAMEBUFFER
-        rgb = linear_to_srgb(rgb);
-#endif
-    } else {
-#ifdef LINEAR_FRAMEBUFFER
-        rgb = srgb_to_linear(rgb);
-#endif
-    }
+    const float3 rgb = finish_srgb_colour(f3(c[0], c[1], c[2]), self.z_shift, dfg);
     return f4(rgb.x, rgb.y, rgb.z, 1.f);
 }
 
-// gr_render's launch, argument for argument, with the sky's description in place of its textures (and no seams_only: a frame with
-// an analytic sky is never shaded inside the trace)
+// shading_work_item's launch with the sky's description in place of the textures (and no seams_only: a frame with an analytic sky
+// is never shaded inside the trace)
 extern "C" __global__ void gr_render_analytic(const render_data* __restrict__ rdata, const int* __restrict__ rdata_count, float4* __restrict__ out,
                                               analytic_sky sky, int width, int height, cfg_t cfg, dfg_t dfg,
                                               int num_pixels, int block_pixels, int strip_rank, int strip_count, int compact_out) {
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= num_pixels) return;
-    const int lb = gid / block_pixels, off = gid - lb * block_pixels;
-    const int id = (lb * strip_count + strip_rank) * block_pixels + off;
-    if (id >= *rdata_count || id >= width * height) return;
-    const render_data self = rdata[id];
-    const int px = self.sx, py = self.sy;
-    const int out_index = compact_out ? lb * block_pixels + off : py * width + px;
-    const bool last_column = px == width - 1, last_row = py == height - 1;
-    float2 beside = make_float2(0, 0), below = make_float2(0, 0);
-    if (self.terminated == 1) {
-        beside = rdata[py * width + px + (last_column ? (width > 1 ? -1 : 0) : 1)].tex_coord;
-        below = rdata[(py + (last_row ? (height > 1 ? -1 : 0) : 1)) * width + px].tex_coord;
-    }
-    out[out_index] = shade_pixel_analytic(self, beside, below, sky, dfg);
+    shading_work_item(num_pixels, block_pixels, strip_rank, strip_count, compact_out, 0, rdata, rdata_count, width, height,
+                      [&](const render_data& self, int out_index, float2 beside, float2 below, bool last_column, bool last_row) __attribute__((always_inline)) {
+        out[out_index] = shade_pixel_analytic(self, beside, below, sky, dfg);
+    });
     (void)cfg;
 }
 
@@ -438,8 +448,8 @@ __device__ __forceinline__ float4 shade_pixel_stars(const render_data& self, flo
                                                     const star_catalogue_view& far_stars, dfg_t dfg) {
     if (self.terminated != 1) return f4(0, 0, 0, 1);
     const float u = self.tex_coord.x, v = self.tex_coord.y;
-    const float hu = __builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(u, beside.x)) + __builtin_fabsf(wrapped_difference(u, below.x))), sky.min_footprint);
-    const float hv = __builtin_fmaxf(0.5f * (__builtin_fabsf(wrapped_difference(v, beside.y)) + __builtin_fabsf(wrapped_difference(v, below.y))), sky.min_footprint);
+    const float2 half = footprint_half_sizes(self, beside, below, sky.min_footprint);
+    const float hu = half.x, hv = half.y;
     const bool near_side = self.side >= 1;   // which side of a wormhole the ray ended on, as shade_pixel picks bg1 / bg2
     const star_catalogue_view cat = near_side ? near_stars : far_stars;
     float3 stars = f3(0.f, 0.f, 0.f);
@@ -464,33 +474,18 @@ __device__ __forceinline__ float4 shade_pixel_stars(const render_data& self, flo
     float c[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) c[k] = srgb_to_linear(near_side ? sky.background[1][k] : sky.background[0][k]);
-    float3 rgb = f3(c[0] + stars.x, c[1] + stars.y, c[2] + stars.z);
-    if (GET_FEATURE(redshift, dfg)) rgb = apply_redshift(rgb, self.z_shift, dfg);   // (gr_render's colour tail, entered in linear light)
-#ifndef LINEAR_FRAMEBUFFER
-    rgb = linear_to_srgb(rgb);
-#endif
+    const float3 rgb = finish_linear_colour(f3(c[0] + stars.x, c[1] + stars.y, c[2] + stars.z), self.z_shift, dfg);   // (the sum is in linear light already)
     return f4(rgb.x, rgb.y, rgb.z, 1.f);
 }
 
-// gr_render_analytic's launch, argument for argument, with the star sky and the two catalogues in place of the analytic sky
+// gr_render_analytic's launch with the star sky and the two catalogues in place of the analytic sky
 extern "C" __global__ void gr_render_stars(const render_data* __restrict__ rdata, const int* __restrict__ rdata_count, float4* __restrict__ out,
                                            star_sky sky, star_catalogue_view near_stars, star_catalogue_view far_stars, int width, int height,
                                            cfg_t cfg, dfg_t dfg, int num_pixels, int block_pixels, int strip_rank, int strip_count, int compact_out) {
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= num_pixels) return;
-    const int lb = gid / block_pixels, off = gid - lb * block_pixels;
-    const int id = (lb * strip_count + strip_rank) * block_pixels + off;
-    if (id >= *rdata_count || id >= width * height) return;
-    const render_data self = rdata[id];
-    const int px = self.sx, py = self.sy;
-    const int out_index = compact_out ? lb * block_pixels + off : py * width + px;
-    const bool last_column = px == width - 1, last_row = py == height - 1;
-    float2 beside = make_float2(0, 0), below = make_float2(0, 0);
-    if (self.terminated == 1) {
-        beside = rdata[py * width + px + (last_column ? (width > 1 ? -1 : 0) : 1)].tex_coord;
-        below = rdata[(py + (last_row ? (height > 1 ? -1 : 0) : 1)) * width + px].tex_coord;
-    }
-    out[out_index] = shade_pixel_stars(self, beside, below, sky, near_stars, far_stars, dfg);
+    shading_work_item(num_pixels, block_pixels, strip_rank, strip_count, compact_out, 0, rdata, rdata_count, width, height,
+                      [&](const render_data& self, int out_index, float2 beside, float2 below, bool last_column, bool last_row) __attribute__((always_inline)) {
+        out[out_index] = shade_pixel_stars(self, beside, below, sky, near_stars, far_stars, dfg);
+    });
     (void)cfg;
 }
 #endif  // GR_FRAME_KERNELS

@@ -1,6 +1,6 @@
 // star_catalogue.cpp — the star sky's host half (geodesic_hip_internal.h, "Star sky"): gr_star_catalogue, built on the device by the
-// kernels of kernels/stars.hip through a borrowed program, as the file encoders of device_encoders.cpp are; the random field; and the two
-// launchers of gr_render_stars (kernels/shading.hip), which hand the kernel a view of each catalogue by value.
+// kernels of kernels/stars.hip through a borrowed program, as the file encoders of device_encoders.cpp are; the random field; and the view of
+// a catalogue that the launchers of gr_render_stars (shading.cpp) hand the kernel by value.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -23,14 +23,6 @@ const int MOST_STARS = 1 << 24;
 
 bool cell_count_allowed(int cells) { return cells >= 16 && cells <= 4096 && (cells & (cells - 1)) == 0; }
 
-// what gr_render_stars takes of a catalogue, by value (star_catalogue_view of kernels/shading.hip, field for field)
-struct catalogue_view {
-    const int* cell_start;
-    const void* stars;
-    const double* table;
-    int n, cells_u, cells_v;
-};
-
 }   // namespace
 
 struct gr_star_catalogue {
@@ -52,7 +44,6 @@ struct gr_star_catalogue {
     }
     size_t cells() const { return (size_t)cells_u * (size_t)cells_v; }
     size_t table_entries() const { return 3 * (size_t)(cells_v + 1) * (size_t)(cells_u + 1); }
-    catalogue_view view() const { return {cell_start, stars, table, n, cells_u, cells_v}; }
 };
 
 int gr_star_sky_default(gr_star_sky* out) {
@@ -150,6 +141,10 @@ int gr_star_catalogue_create(gr_program* p, int n, const float* uv, const float*
 
 void gr_star_catalogue_destroy(gr_star_catalogue* c) { delete c; }
 
+gr_internal::catalogue_view gr_internal::view_of(const gr_star_catalogue* c) {
+    return c ? catalogue_view{c->cell_start, c->stars, c->table, c->n, c->cells_u, c->cells_v} : catalogue_view{};
+}
+
 int gr_star_catalogue_info(const gr_star_catalogue* c, int* n, int* cells_u, int* cells_v) {
     if (!c) return fail("gr_star_catalogue_info: null catalogue");
     if (n) *n = c->n;
@@ -195,36 +190,4 @@ int gr_star_field_random(unsigned long long seed, int n, float* out_uv, float* o
         for (int c = 0; c < 3; c++) out_flux[3 * (size_t)s + c] = (float)(brightness * colour[k][c] / area);
     }
     return GR_OK;
-}
-
-// ---- the launchers of gr_render_stars: gr_render_analytic's, with the sky by value and a view of each catalogue by value ------------------
-static int launch_render_stars(const char* who, gr_program* p, void* stream, const void* rdata, const void* rdata_count, void* out, const gr_star_sky* sky,
-                               const gr_star_catalogue* near, const gr_star_catalogue* far, int width, int height, const void* cfg, const void* dfg,
-                               int num, int block_pixels, int rank, int count, int compact) {
-    if (!rdata || !rdata_count || !out) return fail(std::string(who) + ": a required buffer is NULL");
-    GR_CHECK(gr_internal_check_star_sky(who, sky, near, far, p));
-    gr_star_sky by_value = *sky;
-    catalogue_view near_view = near ? near->view() : catalogue_view{}, far_view = far ? far->view() : catalogue_view{};
-    void* args[] = {&rdata, &rdata_count, &out, &by_value, &near_view, &far_view, &width, &height, &cfg, &dfg, &num, &block_pixels, &rank, &count, &compact};
-    return launch(p, K_RENDER_STARS, stream, blocks(num, 256), 1, 256, 1, args);
-}
-
-int gr_render_stars(gr_program* p, void* stream, const void* rdata, const void* rdata_count, int num_pixels, void* out, const gr_star_sky* sky,
-                    const gr_star_catalogue* near, const gr_star_catalogue* far, int width, int height, const void* cfg, const void* dfg) {
-    return launch_render_stars("gr_render_stars", p, stream, rdata, rdata_count, out, sky, near, far, width, height, cfg, dfg, num_pixels,
-                               num_pixels > 0 ? num_pixels : 1, 0, 1, 0);
-}
-
-int gr_render_stars_strips(gr_program* p, void* stream, const void* rdata, void* out, const gr_star_sky* sky, const gr_star_catalogue* near,
-                           const gr_star_catalogue* far, int width, int height, int block_rows, int strip_rank, int strip_count, int compact_out,
-                           const void* cfg, const void* dfg) {
-    // (the refusals first, in gr_render_analytic_strips' order: the program is not looked into before them)
-    if (!rdata || !out) return fail("gr_render_stars_strips: a required buffer is NULL");
-    GR_CHECK(gr_internal_check_star_sky("gr_render_stars_strips", sky, nullptr, nullptr, nullptr));
-    if (block_rows <= 0 || strip_count <= 0 || strip_rank < 0 || strip_rank >= strip_count) return fail("gr_render_stars_strips: bad strip parameters");
-    if (!p) return fail("gr_render_stars_strips: null program");
-    const int block_pixels = block_rows * width;
-    const int num = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_pixels;
-    return launch_render_stars("gr_render_stars_strips", p, stream, rdata, gr_internal::no_count_of(p), out, sky, near, far, width, height, cfg, dfg, num,
-                               block_pixels, strip_rank, strip_count, compact_out);
 }

@@ -246,3 +246,21 @@ def test_every_refusal_names_the_function_and_the_field():
     # ... and the Python layer hands the library's message on
     with pytest.raises(gra.GeodesicError, match="parallels"):
         gra.AnalyticSky(parallels=500).image(4, 4)
+
+
+@pytest.mark.parametrize("name", ["gr_render_strips", "gr_render_seams"])
+def test_the_texture_strip_launchers_refuse_a_null_buffer_first(name):
+    """as gr_render_analytic_strips does: a NULL rdata, out, bg1 or bg2 under the function's name, then the geometry, then the program -
+    none of it needs a device"""
+    call = getattr(lib, name)
+    somewhere = ctypes.c_void_p(4096)   # never dereferenced: no call gets as far as a launch
+    for missing in range(4):
+        buffers = [None if k == missing else somewhere for k in range(4)]
+        refused(call(None, None, *buffers, 16, 8, 1, 8, 8, 8, 0, 1, 0, 4, None, None), name, "NULL")
+        refused(call(None, None, *buffers, 16, 8, 1, 8, 8, 0, 3, 2, 0, 4, None, None), name, "NULL")   # (before the geometry's refusals)
+    good = [somewhere] * 4
+    for block_rows, rank, ranks in ((0, 0, 1), (8, 0, 0), (8, -1, 2), (8, 2, 2)):
+        refused(lib.gr_render_strips(None, None, *good, 16, 8, 1, 8, 8, block_rows, rank, ranks, 0, 4, None, None), "strip")
+    refused(lib.gr_render_seams(None, None, *good, 16, 8, 1, 8, 8, 4, 0, 2, 0, 4, None, None), "gr_render_seams", "multiples of 8")
+    refused(lib.gr_render_seams(None, None, *good, 16, 8, 1, 12, 8, 8, 0, 1, 0, 4, None, None), "gr_render_seams", "multiples of 8")
+    refused(call(None, None, *good, 16, 8, 1, 8, 8, 8, 0, 1, 0, 4, None, None), "null program")
