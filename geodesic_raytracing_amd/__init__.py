@@ -135,12 +135,27 @@ class GlareStruct(ctypes.Structure):
     _fields_ = [("core", c_float), ("components", c_int), ("weight", c_float * 4), ("taps", c_int * 4), ("tap", (c_float * 129) * 4)]
 
 
+class ToneStruct(ctypes.Structure):
+    """struct gr_tone (include/geodesic_hip_internal.h, "Metering and tone curve"): a manual or metered exposure and a tone curve"""
+    _fields_ = [("mode", c_int), ("stops", c_float), ("key_stops", c_float), ("low", c_float), ("high", c_float), ("min_stops", c_float),
+                ("max_stops", c_float), ("rate", c_float), ("curve", c_int), ("white", c_float)]
+
+
+class ToneStateStruct(ctypes.Structure):
+    """struct gr_tone_state: what the device's solve keeps and writes - 24 bytes, aligned to 8"""
+    _fields_ = [("adapted", ctypes.c_double), ("primed", c_int), ("q", c_int), ("gain", c_float), ("reserved", c_int)]
+
+
 MODE_REFERENCE, MODE_FUSED = 0, 1
 FRAME_F32, FRAME_RGBA8 = 0, 1
 FRAME_YUV420, FRAME_YUV420P10 = 2, 3   # GR_FRAME_YUV420 / _YUV420P10: the video formats of gr_deliver_accumulated (include/geodesic_hip_internal.h)
 FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN, FILTER_MITCHELL = 0, 1, 2, 3   # GR_FILTER_*: the reconstruction filter of a state's frames (include/geodesic_hip_internal.h, "Filtered frames")
 FILTER_NAMES = {"box": FILTER_BOX, "tent": FILTER_TENT, "gaussian": FILTER_GAUSSIAN, "mitchell": FILTER_MITCHELL}
 FILTER_MAX_TAPS = 16
+TONE_MANUAL, TONE_AUTO = 0, 1   # GR_TONE_*: the mode and the curve of a tone (include/geodesic_hip_internal.h, "Metering and tone curve")
+TONE_LINEAR, TONE_REINHARD, TONE_FILMIC = 0, 1, 2
+TONE_CURVE_NAMES = {"linear": TONE_LINEAR, "reinhard": TONE_REINHARD, "filmic": TONE_FILMIC}
+METER_BINS, METER_COUNTERS = 384, 385
 GLARE_MAX_COMPONENTS, GLARE_MAX_TAPS = 4, 129   # GR_GLARE_*: the PSF of a state's frames (include/geodesic_hip_internal.h, "Glare")
 PNG_STREAM_LITERALS, PNG_STREAM_RUNS = 0, 1   # GR_PNG_STREAM_*: the stream kind of a device-made PNG (include/geodesic_hip_internal.h, "PNG frames")
 PNG_STREAM_NAMES = {"literals": PNG_STREAM_LITERALS, "runs": PNG_STREAM_RUNS}
@@ -363,6 +378,16 @@ _SIGNATURES = {
     "gr_apply_glare": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, ctypes.POINTER(GlareStruct)]),
     "gr_render_state_set_glare": (c_int, [c_void_p, ctypes.POINTER(GlareStruct)]),
     "gr_render_state_glare": (c_int, [c_void_p, ctypes.POINTER(GlareStruct), ctypes.POINTER(c_int)]),
+    "gr_tone_default": (c_int, [ctypes.POINTER(ToneStruct)]),
+    "gr_meter_histogram_frame": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "gr_meter_solve_host": (c_int, [c_void_p, ctypes.POINTER(ToneStruct), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int), ctypes.POINTER(c_float), ctypes.POINTER(c_int)]),
+    "gr_tone_frame": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(ToneStruct), c_float, c_void_p]),
+    "gr_meter_frame": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gr_meter_solve_device": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(ToneStruct), c_void_p]),
+    "gr_apply_tone": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(ToneStruct), c_void_p, c_float]),
+    "gr_render_state_set_tone": (c_int, [c_void_p, ctypes.POINTER(ToneStruct)]),
+    "gr_render_state_tone": (c_int, [c_void_p, ctypes.POINTER(ToneStruct), ctypes.POINTER(c_int)]),
+    "gr_render_state_exposure": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
     "gr_analytic_sky_default": (c_int, [ctypes.POINTER(AnalyticSkyStruct)]),
     "gr_render_analytic": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(AnalyticSkyStruct), c_int, c_int, c_void_p, c_void_p]),
     "gr_render_analytic_strips": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(AnalyticSkyStruct), c_int, c_int, c_int, c_int, c_int, c_int,
@@ -441,5 +466,5 @@ def check(rc):
 from .pipeline import (GeodesicCamera, Metric, PinnedBuffer, Program, RenderState, TiledFrame, box_resolve, build_background,  # noqa: E402,F401
                        default_camera, default_features, encode_srgb8, frame_options, synthetic_background, pack_background, rgba8_to_yuv420,
                        yuv420_bytes, Y4MWriter, srgb10_thresholds, frame_to_rgb10, rgb10_to_yuv420p10, yuv420p10_bytes, accumulate_frame, filter_taps,
-                       filter_frame, glare_gaussians, glare_exposure, glare_frame, glare_scratch_bytes, apply_glare, PngEncoder, png_encode_bound, png_encode_host, ExrEncoder, exr_encode_bound, exr_encode_host, exr_half_bits, JpegEncoder, jpeg_encode_bound, jpeg_encode_host, jpeg_quant_tables,
+                       filter_frame, glare_gaussians, glare_exposure, glare_frame, glare_scratch_bytes, apply_glare, tone, meter_histogram, meter_solve, tone_frame, meter_frame, meter_solve_device, apply_tone, PngEncoder, png_encode_bound, png_encode_host, ExrEncoder, exr_encode_bound, exr_encode_host, exr_half_bits, JpegEncoder, jpeg_encode_bound, jpeg_encode_host, jpeg_quant_tables,
                        AviWriter, AnalyticSky, StarCatalogue, StarSky, star_field_random)

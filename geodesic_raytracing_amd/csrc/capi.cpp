@@ -73,7 +73,8 @@ const char* const KERNEL_NAMES[] = {
     "gr_background_reduce", "gr_background_slices", "gr_present_yuv420", "gr_present_yuv420p10", "gr_shutter_accumulate", "gr_resolve_filtered", "gr_png_histogram", "gr_png_pack",
     "gr_jpeg_blocks", "gr_jpeg_pack", "gr_jpeg_gather", "gr_png_histogram_runs", "gr_png_pack_runs", "gr_render_analytic",
     "gr_render_stars", "gr_stars_count", "gr_stars_scan", "gr_stars_scatter", "gr_stars_order", "gr_stars_gather", "gr_stars_sums", "gr_stars_prefix",
-    "gr_glare_rows", "gr_glare_columns", "gr_glare_scale", "gr_exr_histogram", "gr_exr_pack"};
+    "gr_glare_rows", "gr_glare_columns", "gr_glare_scale", "gr_exr_histogram", "gr_exr_pack",
+    "gr_meter_histogram", "gr_meter_solve", "gr_tone_apply"};
 
 // the kernels of the set-up module (kernels/camera.hip, geodesic_camera.hip): once per frame, one lane, IEEE arithmetic - and the box
 // filter of a supersampled frame (kernels/resolve.hip), its 8-bit sRGB and 8- and 10-bit Y'CbCr 4:2:0 encodes (kernels/present.hip) and the sky's mip slices
@@ -81,14 +82,15 @@ const char* const KERNEL_NAMES[] = {
 // PNG encoder (kernels/png.hip; each in two instances, one a stream kind) and the three of the JPEG encoder (kernels/jpeg.hip), which want
 // no part in it either - and the seven that build a star catalogue (kernels/stars.hip), whose sums are taken in the order they are written -
 // and the three of the glare (kernels/glare.hip), which are held to a host definition bit for bit - and the two integer kernels of the
-// EXR encoder (kernels/exr.hip), which use the PNG encoder's bit-packer
+// EXR encoder (kernels/exr.hip), which use the PNG encoder's bit-packer - and the three of the meter and the tone curve (kernels/tone.hip),
+// held to host statements exactly
 bool is_setup_kernel(int k) {
     return k == K_CART_TO_GENERIC || k == K_INIT_BASIS || k == K_CAMERA_SETUP || k == K_BOOST_TETRAD || k == K_INIT_INERTIAL ||
            k == K_GEODESIC_PATH || k == K_PARALLEL_TRANSPORT || k == K_INTERPOLATE_GEODESIC || k == K_RESOLVE_SUPERSAMPLED || k == K_PRESENT_RGBA8 ||
            k == K_BACKGROUND_REDUCE || k == K_BACKGROUND_SLICES || k == K_PRESENT_YUV420 || k == K_PRESENT_YUV420P10 || k == K_SHUTTER_ACCUMULATE || k == K_RESOLVE_FILTERED ||
            k == K_PNG_HISTOGRAM || k == K_PNG_PACK || k == K_JPEG_BLOCKS || k == K_JPEG_PACK || k == K_JPEG_GATHER || k == K_PNG_HISTOGRAM_RUNS ||
            k == K_PNG_PACK_RUNS || (k >= K_STARS_COUNT && k <= K_STARS_PREFIX) || k == K_GLARE_ROWS || k == K_GLARE_COLUMNS || k == K_GLARE_SCALE || k == K_EXR_HISTOGRAM ||
-           k == K_EXR_PACK;
+           k == K_EXR_PACK || k == K_METER_HISTOGRAM || k == K_METER_SOLVE || k == K_TONE_APPLY;
 }
 
 namespace pb = program_build;   // what a build decides: switches, options, source lists, keys, the occupancy rule, the cache files
@@ -1207,6 +1209,63 @@ int gr_apply_glare(gr_program* p, void* stream, const void* src, void* dst, void
         if (int rc = launch(p, K_GLARE_COLUMNS, stream, grid(column_tiles), 1, 256, 1, column_args)) return rc;
     }
     return GR_OK;
+}
+
+// ---- metering and tone curve (kernels/tone.hip; geodesic_hip_internal.h, "Metering and tone curve") ----------------------------------
+
+// The 385 counters are zeroed on the stream, then one launch: a one-dimensional grid of at most METER_MAX_WORKGROUPS workgroups of
+// METER_LANES lanes, each walking tiles of METER_TILE pixels with the grid's stride.  METER_TILE and METER_LANES are tone.hip's
+// GR_METER_TILE and GR_METER_LANES (tests/test_tone_abi.py holds the two files to one value).
+static const unsigned long long METER_TILE = 1024, METER_MAX_WORKGROUPS = 1024;
+static const unsigned METER_LANES = 256;
+int gr_meter_frame(gr_program* p, void* stream, const void* src, int width, int height, void* device_hist) {
+    const std::string who = "gr_meter_frame: ";
+    if (!src || !device_hist) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null argument");
+    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
+    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
+    if ((long long)width * height > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, who + "more than 2^31 - 1 pixels");
+    if ((uintptr_t)src % 16) return fail(GR_ERROR_INVALID_ARGUMENT, who + "src is not aligned to 16 bytes");
+    if ((uintptr_t)device_hist % 4) return fail(GR_ERROR_INVALID_ARGUMENT, who + "device_hist is not aligned to 4 bytes");
+    HIP_CHECK(hipMemsetAsync(device_hist, 0, GR_METER_COUNTERS * sizeof(unsigned), (hipStream_t)stream));
+    unsigned long long pixels = (unsigned long long)width * (unsigned long long)height;
+    const unsigned grid = (unsigned)std::min<unsigned long long>((pixels + METER_TILE - 1) / METER_TILE, METER_MAX_WORKGROUPS);
+    void* args[] = {&src, &pixels, &device_hist};
+    return launch(p, K_METER_HISTOGRAM, stream, grid, 1, METER_LANES, 1, args);
+}
+
+int gr_meter_solve_device(gr_program* p, void* stream, const void* device_hist, const gr_tone* tone, void* device_state) {
+    const std::string who = "gr_meter_solve_device: ";
+    if (!device_hist || !tone || !device_state) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null argument");
+    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
+    if (int rc = gr_internal_check_tone("gr_meter_solve_device", tone)) return rc;
+    if (tone->mode != GR_TONE_AUTO) return fail(GR_ERROR_INVALID_ARGUMENT, who + "mode is not GR_TONE_AUTO (a manual gain is gr_meter_solve_host's)");
+    if ((uintptr_t)device_hist % 4) return fail(GR_ERROR_INVALID_ARGUMENT, who + "device_hist is not aligned to 4 bytes");
+    if ((uintptr_t)device_state % 8) return fail(GR_ERROR_INVALID_ARGUMENT, who + "device_state is not aligned to 8 bytes");
+    float key = tone->key_stops, low = tone->low, high = tone->high, lowest = tone->min_stops, highest = tone->max_stops, rate = tone->rate;
+    void* args[] = {&device_hist, &device_state, &key, &low, &high, &lowest, &highest, &rate};
+    return launch(p, K_METER_SOLVE, stream, 1, 1, 64, 1, args);
+}
+
+int gr_apply_tone(gr_program* p, void* stream, const void* src, void* dst, int width, int height, const gr_tone* tone, const void* device_gain,
+                  float host_gain) {
+    const std::string who = "gr_apply_tone: ";
+    if (!src || !dst || !tone) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null argument");
+    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
+    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
+    if ((long long)width * height > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, who + "more than 2^31 - 1 pixels");
+    if (int rc = gr_internal_check_tone("gr_apply_tone", tone)) return rc;
+    if (!device_gain && (!std::isfinite(host_gain) || host_gain < 0.f)) return fail(GR_ERROR_INVALID_ARGUMENT, who + "host_gain is not finite or is negative");
+    if ((uintptr_t)src % 16 || (uintptr_t)dst % 16) return fail(GR_ERROR_INVALID_ARGUMENT, who + "src or dst is not aligned to 16 bytes");
+    if ((uintptr_t)device_gain % 4) return fail(GR_ERROR_INVALID_ARGUMENT, who + "device_gain is not aligned to 4 bytes");
+    const size_t frame_bytes = (size_t)width * (size_t)height * 4 * sizeof(float);
+    if (src != dst && (uintptr_t)src < (uintptr_t)dst + frame_bytes && (uintptr_t)dst < (uintptr_t)src + frame_bytes)
+        return fail(GR_ERROR_INVALID_ARGUMENT, who + "src and dst overlap and are not one buffer");
+    unsigned long long pixels = (unsigned long long)width * (unsigned long long)height;
+    int curve = tone->curve;
+    float iw2 = gr_internal_tone_inverse_white_squared(tone);
+    const unsigned grid = (unsigned)std::min<unsigned long long>((pixels + 255) / 256, 1ull << 20);
+    void* args[] = {&src, &dst, &pixels, &curve, &iw2, &device_gain, &host_gain};
+    return launch(p, K_TONE_APPLY, stream, grid, 1, 256, 1, args);
 }
 
 // ---- the sky's mip slices on the device (kernels/background.hip) ------------------------------------

@@ -85,6 +85,15 @@ struct gr_render_state {
     gr_glare glare{};
     void* glare_frame = nullptr;
     void* glare_scratch = nullptr;
+    // gr_render_state_set_tone (geodesic_hip_internal.h, "Metering and tone curve"): with a tone the finished frame - resolved, and glared
+    // into glare_frame if a glare is set - is metered and solved (auto mode) into tone_words (a gr_tone_state, then the 385 counters) and
+    // gr_apply_tone writes tone_frame (or the caller's float4 memory), which the sink reads at factor 1.  tone_frame is allocated with
+    // the first delivery in an encoded format, tone_words with the first in auto mode.  tone_reset: the adaptation state is zeroed on the stream of the next delivery.
+    bool tone_set = false;
+    gr_tone tone{};
+    void* tone_frame = nullptr;
+    void* tone_words = nullptr;
+    bool tone_reset = false;
     // gr_render_state_set_sky: with a sky every frame of the state is shaded by gr_render_analytic and reads no background; without
     // one (the default) by gr_render / gr_render_strips, launch for launch as before.  Shading only: the records do not depend on it.
     bool sky_set = false;
@@ -625,6 +634,43 @@ int gr_render_state_glare(const gr_render_state* s, gr_glare* out, int* is_set) 
     return GR_OK;
 }
 
+int gr_render_state_set_tone(gr_render_state* s, const gr_tone* tone) {
+    if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_tone: null render state");
+    if (tone) {
+        GR_CHECK(gr_internal_check_tone("gr_render_state_set_tone", tone));
+        s->tone = *tone;
+    }
+    s->tone_set = tone != nullptr;
+    s->tone_reset = true;   // (the adaptation starts again; zeroed on the stream of the next delivery: nothing here touches the device)
+    return GR_OK;
+}
+
+int gr_render_state_tone(const gr_render_state* s, gr_tone* out, int* is_set) {
+    if (!s || !out || !is_set) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_tone: null argument");
+    *is_set = s->tone_set ? 1 : 0;
+    if (s->tone_set) *out = s->tone;
+    return GR_OK;
+}
+
+// the last delivered frame's exposure: the only call here that waits for the device (tests, the CLI's printout)
+int gr_render_state_exposure(gr_render_state* s, void* stream, float* stops, float* gain) {
+    if (!s || !stops || !gain) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_exposure: null argument");
+    if (!s->tone_set) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_exposure: the state has no tone (gr_render_state_set_tone)");
+    gr_tone_state words{};
+    words.gain = 1.f;
+    if (s->tone.mode == GR_TONE_MANUAL) {
+        gr_internal_tone_gain((double)s->tone.stops, &words.gain, &words.q);
+    } else if (s->tone_words && !s->tone_reset) {
+        HIP_CHECK(hipSetDevice(s->device));
+        HIP_CHECK(hipMemcpyAsync(&words, s->tone_words, sizeof words, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+        if (!words.primed && words.gain == 0.f) words.gain = 1.f;   // (no frame delivered yet: the words are still zero)
+    }
+    *stops = (float)words.q / 16.f;
+    *gain = words.gain;
+    return GR_OK;
+}
+
 int gr_render_state_set_sky(gr_render_state* s, const gr_analytic_sky* sky) {
     if (!s) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_state_set_sky: null render state");
     if (sky) {
@@ -681,7 +727,7 @@ void gr_render_state_destroy(gr_render_state* s) {
                                s->tetrad[3], s->rays_count_in, s->rays_adaptive_count, s->render_data_count, s->cfg, s->dfg,
                                s->attempts, s->rays_in, s->rays_adaptive, s->render_data, s->termination_buffer, s->tile_order,
                                s->tile_cost, s->lattice_rays, s->guessed[0], s->guessed[1], s->pending_list, s->block_cost, s->block_cost_before, s->ref_cost[0], s->ref_cost[1], s->ref_order, s->ref_sort_work, s->parking_records, s->parking_words,
-                               s->traced_frame, s->accumulation, s->filtered_frame, s->glare_frame, s->glare_scratch};
+                               s->traced_frame, s->accumulation, s->filtered_frame, s->glare_frame, s->glare_scratch, s->tone_frame, s->tone_words};
     for (auto& slot : s->pre) {
         if (slot.stream) { (void)hipStreamSynchronize(slot.stream); (void)hipStreamDestroy(slot.stream); }
         if (slot.ready) (void)hipEventDestroy(slot.ready);
@@ -1705,6 +1751,55 @@ static int allocate_glare_frames(gr_render_state* s) {
     return GR_OK;
 }
 
+// what a tone works in (gr_render_state: tone_frame; tone_words: a gr_tone_state at 0, the 385 counters at 32), on the state's device
+static const size_t TONE_WORDS_BYTES = 32 + GR_METER_COUNTERS * sizeof(unsigned);
+static bool tone_memory_missing(const gr_render_state* s, int format) {
+    return (format != GR_FRAME_F32 && !s->tone_frame) || (s->tone.mode == GR_TONE_AUTO && !s->tone_words);
+}
+// (a float4 delivery is toned straight into the caller's memory and needs no frame; a manual tone needs no words)
+static int allocate_tone_memory(gr_render_state* s, int format) {
+    if (format != GR_FRAME_F32 && !s->tone_frame) HIP_CHECK(hipMalloc(&s->tone_frame, (size_t)s->out_width * s->out_height * 4 * sizeof(float)));
+    if (s->tone.mode == GR_TONE_AUTO && !s->tone_words) {
+        HIP_CHECK(hipMalloc(&s->tone_words, TONE_WORDS_BYTES));
+        s->tone_reset = true;
+    }
+    return GR_OK;
+}
+
+// The stages between the resolve and the sink of a state with a glare, a tone or both (their memory is allocated): the glare of
+// `resolved` if one is set, the meter and the solve in auto mode, the tone; the last of them writes the caller's memory where that is
+// float4, else a frame of the state, which the format's own kernel encodes at factor 1.  No call here waits for the device.
+static int finish_frame(gr_render_state* s, gr_program* p, void* stream, const void* resolved, int format, int layout, void* out) {
+    const int w = s->out_width, h = s->out_height;
+    const bool into_out = format == GR_FRAME_F32;
+    const void* finished = resolved;
+    if (s->glare_set) {
+        void* glared = into_out && !s->tone_set ? out : s->glare_frame;
+        GR_CHECK(gr_apply_glare(p, stream, resolved, glared, s->glare_scratch, (size_t)w * h * 4 * sizeof(float), w, h, &s->glare));
+        finished = glared;
+    }
+    if (s->tone_set) {
+        const void* device_gain = nullptr;   // auto: the word the solve writes; manual: the host's gain in the argument block
+        float host_gain = 1.f;
+        int q = 0;
+        if (s->tone.mode == GR_TONE_AUTO) {
+            gr_tone_state* words = (gr_tone_state*)s->tone_words;
+            void* counters = (char*)s->tone_words + 32;
+            device_gain = &words->gain;
+            if (s->tone_reset) HIP_CHECK(hipMemsetAsync(s->tone_words, 0, 32, (hipStream_t)stream));
+            s->tone_reset = false;
+            GR_CHECK(gr_meter_frame(p, stream, finished, w, h, counters));
+            GR_CHECK(gr_meter_solve_device(p, stream, counters, &s->tone, words));
+        } else {
+            gr_internal_tone_gain((double)s->tone.stops, &host_gain, &q);
+        }
+        void* toned = into_out ? out : s->tone_frame;
+        GR_CHECK(gr_apply_tone(p, stream, finished, toned, w, h, &s->tone, device_gain, host_gain));
+        finished = toned;
+    }
+    return into_out ? GR_OK : encode_frame(p, stream, format, layout, finished, w, h, 1, nullptr, out);
+}
+
 // The delivery core (`name`: the entry point's, for its refusals).  What needs no device is refused first; nothing is allocated for a call that is refused.
 static int deliver_frame(const char* name, const sink& to, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream,
                          const gr_camera* camera, const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1,
@@ -1725,9 +1820,16 @@ static int deliver_frame(const char* name, const sink& to, gr_render_state* s, g
     if (s->glare_set && opt.strip_count > 1)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": a state with a glare renders whole frames only (strip_count > 1): the PSF "
                                                                                 "reads across strip borders").c_str());
+    // ... and so is a tone: the delivery meters and tones the frame, or the accumulation, once
+    const bool toned = s->tone_set && !to.accumulate;
+    if (s->tone_set && opt.strip_count > 1)
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": a state with a tone renders whole frames only (strip_count > 1): a histogram "
+                                                                                "of a strip is not the frame's").c_str());
     GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, to.accumulate ? s : to.out));   // (s: any non-NULL out)
-    const bool resolves = filtered || (glared && factor > 1);   // into filtered_frame: by the filter, or by the box in front of a glare
-    const bool allocates = !s->traced_frame || (to.accumulate && !s->accumulation) || (resolves && !s->filtered_frame) || (glared && (!s->glare_frame || !s->glare_scratch));
+    const bool finished = glared || toned;   // stages between the resolve and the sink: finish_frame
+    const bool resolves = filtered || (finished && factor > 1);   // into filtered_frame: by the filter, or by the box in front of a glare or a tone
+    const bool allocates = !s->traced_frame || (to.accumulate && !s->accumulation) || (resolves && !s->filtered_frame) || (glared && (!s->glare_frame || !s->glare_scratch)) ||
+                           (toned && tone_memory_missing(s, to.format));
     if (allocates) HIP_CHECK(hipSetDevice(s->device));   // (render_traced_frame sets it for everything else)
     if (!s->traced_frame) {   // a factor-1 state's first frame that does not go straight to the caller
         HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
@@ -1742,6 +1844,7 @@ static int deliver_frame(const char* name, const sink& to, gr_render_state* s, g
     }
     if (resolves && !s->filtered_frame) HIP_CHECK(hipMalloc(&s->filtered_frame, (size_t)w * h * 4 * sizeof(float)));
     if (glared) GR_CHECK(allocate_glare_frames(s));
+    if (toned) GR_CHECK(allocate_tone_memory(s, to.format));
     if (to.accumulate && to.first) s->accumulated = 0;   // (a sub-frame that fails below leaves nothing to deliver)
     GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
                                  s->traced_frame, &traced));
@@ -1749,15 +1852,13 @@ static int deliver_frame(const char* name, const sink& to, gr_render_state* s, g
     const bool timed = opt.time_kernels == 1;
     if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
     // a state with a filter: the filtered frame - straight into the caller's memory where that is float4 - and the sink from it at factor 1
-    if (glared) {
-        // a state with a glare: the resolved frame at the output size, the glare of it - straight into the caller's memory where that is
-        // float4 - and the sink from the glare's frame at factor 1
+    if (finished) {
+        // a state with a glare or a tone: the resolved frame at the output size, then finish_frame - the last stage straight into the
+        // caller's memory where that is float4 - and the sink from the state's frame at factor 1
         if (filtered) GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, s->filtered_frame, w, h, factor, taps, tap_count));
         else if (factor > 1) GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, s->filtered_frame, w, h, factor, 0, 0, 1, 0));
         const void* resolved = resolves ? s->filtered_frame : s->traced_frame;
-        const bool into_out = to.format == GR_FRAME_F32;
-        GR_CHECK(gr_apply_glare(p, stream, resolved, into_out ? to.out : s->glare_frame, s->glare_scratch, (size_t)w * h * 4 * sizeof(float), w, h, &s->glare));
-        if (!into_out) GR_CHECK(encode_frame(p, stream, to.format, to.layout, s->glare_frame, w, h, 1, nullptr, to.out));
+        GR_CHECK(finish_frame(s, p, stream, resolved, to.format, to.layout, to.out));
     } else {
     const bool direct = filtered && !to.accumulate && to.format == GR_FRAME_F32;
     if (filtered) GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, direct ? to.out : s->filtered_frame, w, h, factor, taps, tap_count));
@@ -1784,8 +1885,8 @@ int gr_internal_render_frame_as(int format, int layout, gr_render_state* s, gr_p
         GR_CHECK(refuse_output(f.entry, format, layout, out, s, options ? options->strip_count : 1));
     }
     if (s) s->resolve_timed = false;
-    // (a factor-1 box state's float4 frame goes straight to the caller unless a glare is set; out == NULL stops after the records: nothing was shaded, nothing to resolve)
-    if (format == GR_FRAME_F32 && (!s || (s->supersample == 1 && s->filter == GR_FILTER_BOX && !s->glare_set) || !out))
+    // (a factor-1 box state's float4 frame goes straight to the caller unless a glare or a tone is set; out == NULL stops after the records: nothing was shaded, nothing to resolve)
+    if (format == GR_FRAME_F32 && (!s || (s->supersample == 1 && s->filter == GR_FILTER_BOX && !s->glare_set && !s->tone_set) || !out))
         return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out, options);
     return deliver_frame(f.entry, sink{format, layout, out, false, 0.f, 0}, s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2,
                          bg_width, bg_height, bg_levels, options);
@@ -1848,12 +1949,10 @@ int gr_deliver_accumulated(gr_render_state* s, gr_program* p, void* stream, int 
     if (!s->accumulated || !s->accumulation)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: the state holds no accumulation (gr_render_subframe first)");
     HIP_CHECK(hipSetDevice(s->device));
-    if (s->glare_set) {   // the glare of the accumulation - into the state's own frame, or the caller's float4 memory -, then the encode of that
-        const int w = s->out_width, h = s->out_height;
-        GR_CHECK(allocate_glare_frames(s));
-        const bool into_out = format == GR_FRAME_F32;
-        GR_CHECK(gr_apply_glare(p, stream, s->accumulation, into_out ? out : s->glare_frame, s->glare_scratch, (size_t)w * h * 4 * sizeof(float), w, h, &s->glare));
-        return into_out ? GR_OK : encode_frame(p, stream, format, layout, s->glare_frame, w, h, 1, nullptr, out);
+    if (s->glare_set || s->tone_set) {   // the glare of the accumulation, then its meter and tone - into the state's own frames, or the caller's float4 memory -, then the encode of that
+        if (s->glare_set) GR_CHECK(allocate_glare_frames(s));
+        if (s->tone_set) GR_CHECK(allocate_tone_memory(s, format));
+        return finish_frame(s, p, stream, s->accumulation, format, layout, out);
     }
     return encode_frame(p, stream, format, layout, s->accumulation, s->out_width, s->out_height, 1, nullptr, out);
 }

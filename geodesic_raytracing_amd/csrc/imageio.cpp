@@ -747,4 +747,185 @@ GR_NO_CONTRACTION int gr_glare_frame(const float* src, int width, int height, co
     return GR_OK;
 }
 
+// ---- metering and tone curve - the host statements (geodesic_hip_internal.h, "Metering and tone curve"; kernels/tone.hip's launches behind
+// gr_meter_frame, gr_meter_solve_device and gr_apply_tone are held to these exactly).
+// what every taker of a tone refuses about its fields, under the caller's name and by the field's; all fields in both modes
+int gr_internal_check_tone(const char* who, const gr_tone* t) {
+    std::string wrong;
+    const auto stops = [](float v) { return std::isfinite(v) && v >= -32.f && v <= 32.f; };
+    if (t->mode != GR_TONE_MANUAL && t->mode != GR_TONE_AUTO) wrong = "mode " + std::to_string(t->mode) + " (GR_TONE_MANUAL, GR_TONE_AUTO)";
+    else if (!stops(t->stops)) wrong = "stops is not in -32 to 32";
+    else if (!stops(t->key_stops)) wrong = "key_stops is not in -32 to 32";
+    else if (!std::isfinite(t->low) || t->low < 0.f || t->low > 1.f) wrong = "low is not in [0, 1]";
+    else if (!std::isfinite(t->high) || t->high < 0.f || t->high > 1.f) wrong = "high is not in [0, 1]";
+    else if (!(t->low < t->high)) wrong = "low >= high";
+    else if (!stops(t->min_stops)) wrong = "min_stops is not in -32 to 32";
+    else if (!stops(t->max_stops)) wrong = "max_stops is not in -32 to 32";
+    else if (t->min_stops > t->max_stops) wrong = "min_stops > max_stops";
+    else if (!std::isfinite(t->rate) || !(t->rate > 0.f) || t->rate > 1.f) wrong = "rate is not in (0, 1]";
+    else if (t->curve != GR_TONE_LINEAR && t->curve != GR_TONE_REINHARD && t->curve != GR_TONE_FILMIC) wrong = "curve " + std::to_string(t->curve) + " (GR_TONE_LINEAR, _REINHARD, _FILMIC)";
+    else if (!std::isfinite(t->white) || !(t->white > 0.f) || t->white > 4096.f) wrong = "white is not in (0, 4096]";
+    return wrong.empty() ? GR_OK : gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(who) + ": " + wrong).c_str());
+}
+
+int gr_tone_default(gr_tone* out) {
+    if (!out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_tone_default: null argument");
+    gr_tone made;
+    std::memset(&made, 0, sizeof made);
+    made.mode = GR_TONE_MANUAL;
+    made.stops = 0.f;
+    made.key_stops = -0x1.3ca9c6p+1f;   // (float)log2(0.18)
+    made.low = 0.5f;
+    made.high = 0.98f;
+    made.min_stops = -32.f;
+    made.max_stops = 32.f;
+    made.rate = 1.f;
+    made.curve = GR_TONE_LINEAR;
+    made.white = 4.f;
+    *out = made;
+    return GR_OK;
+}
+
+GR_NO_CONTRACTION int gr_meter_histogram_frame(const float* src, int width, int height, unsigned* hist) {
+    const std::string who = "gr_meter_histogram_frame: ";
+    if (!src || !hist) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "null argument").c_str());
+    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "a size below 1").c_str());
+    if ((long long)width * height > 0x7fffffffll) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "more than 2^31 - 1 pixels").c_str());
+    std::memset(hist, 0, GR_METER_COUNTERS * sizeof(unsigned));
+    const size_t pixels = (size_t)width * (size_t)height;
+    for (size_t i = 0; i < pixels; i++) {
+        const float yr = 0.2126f * src[4 * i], yg = 0.7152f * src[4 * i + 1], yb = 0.0722f * src[4 * i + 2];
+        const float yrg = yr + yg;
+        const float y = yrg + yb;
+        if (!(y > 0.f)) {
+            hist[GR_METER_BINS]++;
+            continue;
+        }
+        uint32_t bits;
+        std::memcpy(&bits, &y, sizeof bits);
+        const int e = (int)(bits >> 20) - 824;
+        hist[std::min(std::max(e, 0), GR_METER_BINS - 1)]++;
+    }
+    return GR_OK;
+}
+
+namespace {
+const float TONE_SIXTEENTHS[16] = GR_TONE_SIXTEENTHS;
+inline double tone_lesser(double a, double b) { return a < b ? a : b; }
+inline double tone_greater(double a, double b) { return a > b ? a : b; }
+}   // namespace
+
+// the gain of `adapted` stops (-32 ... 32), in sixteenths of a stop from the table
+GR_NO_CONTRACTION void gr_internal_tone_gain(double adapted, float* gain, int* q_out) {
+    const double sixteenths = adapted * 16.0;
+    const int q = (int)std::nearbyint(sixteenths);   // (the rounding mode is the default: to nearest, ties to even)
+    const int index = ((q % 16) + 16) % 16;
+    const int whole = (q - index) / 16;
+    *q_out = q;
+    *gain = std::ldexp(TONE_SIXTEENTHS[index], whole);
+}
+
+// kernels/tone.hip's gr_meter_solve repeats this operation for operation
+GR_NO_CONTRACTION int gr_meter_solve_host(const unsigned* hist, const gr_tone* tone, double* adapted_io, int* primed_io, float* gain, int* q_out) {
+    const std::string who = "gr_meter_solve_host: ";
+    if (!hist || !tone || !adapted_io || !primed_io || !gain || !q_out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "null argument").c_str());
+    GR_CHECK(gr_internal_check_tone("gr_meter_solve_host", tone));
+    double adapted;
+    if (tone->mode == GR_TONE_MANUAL) {
+        adapted = (double)tone->stops;
+    } else {
+        if (!std::isfinite(*adapted_io) || *adapted_io < -32.0 || *adapted_io > 32.0)
+            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "adapted is not in -32 to 32").c_str());
+        adapted = *adapted_io;
+        int primed = *primed_io != 0;
+        unsigned long long total = 0;
+        for (int b = 0; b < GR_METER_BINS; b++) total += hist[b];
+        if (total != 0) {
+            const double n = (double)total;
+            const double lo = (double)tone->low * n, hi = (double)tone->high * n;
+            double sum_w = 0.0, sum_m = 0.0;
+            unsigned long long below = 0;
+            for (int b = 0; b < GR_METER_BINS; b++) {
+                const double c = (double)below;
+                below += hist[b];
+                const double upper = tone_lesser((double)below, hi), lower = tone_greater(c, lo);
+                const double w = tone_greater(0.0, upper - lower);
+                const double centre = (double)b + 0.5;
+                const double m = w * centre;
+                sum_w = sum_w + w;
+                sum_m = sum_m + m;
+            }
+            const double mean = sum_m / sum_w;
+            const double octaves = mean / 8.0;
+            const double level = octaves - 24.0;
+            const double wanted = (double)tone->key_stops - level;
+            const double target = tone_lesser(tone_greater(wanted, (double)tone->min_stops), (double)tone->max_stops);
+            if (!primed) {
+                adapted = target;
+                primed = 1;
+            } else {
+                const double step = target - adapted;
+                const double move = (double)tone->rate * step;
+                adapted = adapted + move;
+            }
+        } else if (!primed) {
+            adapted = 0.0;
+        }
+        *adapted_io = adapted;
+        *primed_io = primed;
+    }
+    gr_internal_tone_gain(adapted, gain, q_out);
+    return GR_OK;
+}
+
+namespace {
+GR_NO_CONTRACTION inline float tone_curve(float c, float gain, int curve, float iw2) {
+    const float v = gain * c;
+    const float x = v > 0.f ? (v < 16777216.f ? v : 16777216.f) : 0.f;
+    if (curve == GR_TONE_REINHARD) {
+        const float a = x * iw2;
+        const float one_a = 1.f + a;
+        const float n = x * one_a;
+        const float d = 1.f + x;
+        return n / d;
+    }
+    if (curve == GR_TONE_FILMIC) {
+        const float n1 = 2.51f * x;
+        const float n2 = n1 + 0.03f;
+        const float n = x * n2;
+        const float d1 = 2.43f * x;
+        const float d2 = d1 + 0.59f;
+        const float d3 = x * d2;
+        const float d = d3 + 0.14f;
+        const float y = n / d;
+        return y < 1.f ? y : 1.f;
+    }
+    return x;
+}
+}   // namespace
+
+float gr_internal_tone_inverse_white_squared(const gr_tone* t) { return (float)(1.0 / ((double)t->white * (double)t->white)); }
+
+GR_NO_CONTRACTION int gr_tone_frame(const float* src, int width, int height, const gr_tone* tone, float gain, float* dst) {
+    const std::string who = "gr_tone_frame: ";
+    if (!src || !tone || !dst) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "null argument").c_str());
+    if (width < 1 || height < 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "a size below 1").c_str());
+    if ((long long)width * height > 0x7fffffffll) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "more than 2^31 - 1 pixels").c_str());
+    GR_CHECK(gr_internal_check_tone("gr_tone_frame", tone));
+    if (!std::isfinite(gain) || gain < 0.f) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (who + "gain is not finite or is negative").c_str());
+    const float iw2 = gr_internal_tone_inverse_white_squared(tone);
+    const size_t pixels = (size_t)width * (size_t)height;
+    for (size_t i = 0; i < pixels; i++) {
+        const float r = tone_curve(src[4 * i], gain, tone->curve, iw2), g = tone_curve(src[4 * i + 1], gain, tone->curve, iw2),
+                    b = tone_curve(src[4 * i + 2], gain, tone->curve, iw2);
+        uint32_t alpha;
+        std::memcpy(&alpha, &src[4 * i + 3], sizeof alpha);   // (as an integer: a NaN's payload passes whatever the machine does to float moves)
+        dst[4 * i] = r;
+        dst[4 * i + 1] = g;
+        dst[4 * i + 2] = b;
+        std::memcpy(&dst[4 * i + 3], &alpha, sizeof alpha);
+    }
+    return GR_OK;
+}
+
 }  // extern "C"

@@ -14,6 +14,9 @@ int gr_internal_check_analytic_sky(const char* who, const gr_analytic_sky* sky);
 int gr_internal_check_star_sky(const char* who, const gr_star_sky* sky, const gr_star_catalogue* near, const gr_star_catalogue* far, const gr_program* p);   // star_catalogue.cpp
 int gr_internal_render_state_size(const gr_render_state* s, int* width, int* height);   // frame.cpp
 const char* gr_internal_filter_table_error(int factor, const float* taps, int count);   // imageio.cpp: NULL for nothing wrong
+int gr_internal_check_tone(const char* who, const gr_tone* t);   // imageio.cpp: what every taker of a tone refuses about its fields
+void gr_internal_tone_gain(double adapted_stops, float* gain, int* q);   // imageio.cpp: section 2's gain, for a manual tone too
+float gr_internal_tone_inverse_white_squared(const gr_tone* t);   // imageio.cpp: iw2 of the Reinhard curve, as gr_tone_frame takes it
 int gr_internal_check_glare(const char* who, const gr_glare* g);   // imageio.cpp: what every taker of a glare refuses about its fields
 // frame.cpp: gr_render_frame and its three encoded kin by the format's value (tiled.cpp renders a share through it)
 int gr_internal_render_frame_as(int format, int layout, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
@@ -40,7 +43,8 @@ enum KernelId {
     K_ADAPTIVE, K_RENDER, K_TRACE_FUSED, K_TRACE_FUSED_LATTICE, K_TRACE_PAIR, K_TRACE_COMPACT, K_PREPASS_FUSED, K_CAMERA_SETUP, K_ORDER_TILES, K_ADAPTIVE_REFINE, K_TRACE_PENDING, K_APPLY_GUESSED, K_DO_RAYS_SCHEDULED, K_SORT_TILES_COUNT, K_SORT_TILES_PLACE, K_TRACE_FUSED_PARKING, K_BOOST_TETRAD, K_INIT_INERTIAL, K_GEODESIC_PATH, K_PARALLEL_TRANSPORT,
     K_INTERPOLATE_GEODESIC, K_RESOLVE_SUPERSAMPLED, K_PRESENT_RGBA8, K_BACKGROUND_REDUCE, K_BACKGROUND_SLICES, K_PRESENT_YUV420, K_PRESENT_YUV420P10, K_SHUTTER_ACCUMULATE, K_RESOLVE_FILTERED, K_PNG_HISTOGRAM, K_PNG_PACK, K_JPEG_BLOCKS, K_JPEG_PACK, K_JPEG_GATHER, K_PNG_HISTOGRAM_RUNS, K_PNG_PACK_RUNS, K_RENDER_ANALYTIC,
     K_RENDER_STARS, K_STARS_COUNT, K_STARS_SCAN, K_STARS_SCATTER, K_STARS_ORDER, K_STARS_GATHER, K_STARS_SUMS, K_STARS_PREFIX,
-    K_GLARE_ROWS, K_GLARE_COLUMNS, K_GLARE_SCALE, K_EXR_HISTOGRAM, K_EXR_PACK, K_COUNT
+    K_GLARE_ROWS, K_GLARE_COLUMNS, K_GLARE_SCALE, K_EXR_HISTOGRAM, K_EXR_PACK,
+    K_METER_HISTOGRAM, K_METER_SOLVE, K_TONE_APPLY, K_COUNT
 };
 
 namespace gr_internal __attribute__((visibility("hidden"))) {   // (not among the library's exported names)

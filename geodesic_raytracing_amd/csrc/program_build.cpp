@@ -216,9 +216,9 @@ const char* const KERNEL_PARTS[] = {"program.hip",       // structs of the bound
                                     "shading.hip"};      // texture sampling, gr_render
 // ... and the set-up module's: what runs once per frame on one lane (camera.hip, geodesic_camera.hip), the box filter of a supersampled
 // frame, the separable filters that replace it (filter.hip), the shutter's accumulation (which uses the box), the encodes, the sky's
-// mip slices, the PNG encoder's two kernels, the EXR encoder's two (behind png.hip: they use its bit-packer), the JPEG encoder's three, the seven that build a star catalogue and the three of the glare
+// mip slices, the PNG encoder's two kernels, the EXR encoder's two (behind png.hip: they use its bit-packer), the JPEG encoder's three, the seven that build a star catalogue, the three of the meter and the tone curve (tone.hip) and the three of the glare
 const char* const PARTS[] = {"program.hip", "probes.inc", "metric.hip", "setup.hip", "camera.hip", "geodesic_camera.hip", "resolve.hip",
-                             "filter.hip", "shutter.hip", "present.hip", "background.hip", "png.hip", "exr.hip", "jpeg.hip", "stars.hip", "glare.hip"};
+                             "filter.hip", "shutter.hip", "present.hip", "background.hip", "png.hip", "exr.hip", "jpeg.hip", "stars.hip", "tone.hip", "glare.hip"};
 }   // namespace
 
 bool read_file(const std::string& path, std::string& out) {

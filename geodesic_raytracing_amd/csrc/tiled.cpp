@@ -296,6 +296,13 @@ bool state_has_glare(const gr_render_state* s) {
     return gr_render_state_glare(s, glare.get(), &is_set) == GR_OK && is_set;
 }
 
+// ... or are metered and toned (gr_render_state_set_tone): whole frames only too
+bool state_has_tone(const gr_render_state* s) {
+    gr_tone tone;
+    int is_set = 0;
+    return gr_render_state_tone(s, &tone, &is_set) == GR_OK && is_set;
+}
+
 }  // namespace
 
 extern "C" {
@@ -577,6 +584,8 @@ int gr_render_frame_tiled_as(gr_tiled* t, gr_render_state* s, gr_program* p, con
             return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled_as: a render state with a filter (gr_render_state_set_filter) renders whole frames only; a split frame takes GR_FILTER_BOX");
         if (state_has_glare(s))
             return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled_as: a render state with a glare (gr_render_state_set_glare) renders whole frames only: the PSF reads across strip borders");
+        if (state_has_tone(s))
+            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled_as: a render state with a tone (gr_render_state_set_tone) renders whole frames only: a histogram of a strip is not the frame's");
     }
     {   // (the staging buffers and the blocks' places in the root's frame are those of the participant's frame size: the size of the
         // state's frames, which a supersampled state traces at factor x that)
@@ -643,6 +652,8 @@ int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const 
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a render state with a filter (gr_render_state_set_filter) renders whole frames only; a split frame takes GR_FILTER_BOX");
     if (state_has_glare(s))
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a render state with a glare (gr_render_state_set_glare) renders whole frames only: the PSF reads across strip borders");
+    if (state_has_tone(s))
+        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a render state with a tone (gr_render_state_set_tone) renders whole frames only: a histogram of a strip is not the frame's");
     if (factor != 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a supersampled render state (gr_render_state_create_supersampled) renders its split frames through gr_render_frame_tiled_as; this entry point takes a state of factor 1");
     return gr_render_frame_tiled_as(t, s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
                                     frame_on_root, options, rotation, GR_FRAME_F32);

@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from . import (AnalyticSkyStruct, GlareStruct, GLARE_MAX_COMPONENTS, StarSkyStruct, Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, FRAME_YUV420, FRAME_YUV420P10, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
+from . import (AnalyticSkyStruct, GlareStruct, ToneStruct, TONE_AUTO, TONE_MANUAL, TONE_CURVE_NAMES, METER_COUNTERS, GLARE_MAX_COMPONENTS, StarSkyStruct, Camera, Features, FrameOptions, FILTER_BOX, FILTER_MAX_TAPS, FILTER_NAMES, FRAME_F32, FRAME_RGBA8, FRAME_YUV420, FRAME_YUV420P10, YUV420_I420, GeodesicError, MetricInfo, MODE_FUSED, STAGE_NAMES, c_float, c_int,
                c_size_t, c_void_p, check, lib)
 
 LIGHTRAY_DTYPE = np.dtype([("position", "<f4", 4), ("velocity", "<f4", 4), ("initial_quat", "<f4", 4),
@@ -687,7 +687,7 @@ class StarSky:
 class RenderState:
     """Per-frame device buffers + the frame sequence (render_state.hpp:97-197, main.cpp:2244-2526)."""
 
-    def __init__(self, width, height, device=0, supersample=1, filter=FILTER_BOX, sky=None, stars=None, glare=None):
+    def __init__(self, width, height, device=0, supersample=1, filter=FILTER_BOX, sky=None, stars=None, glare=None, tone=None):
         """supersample = f > 1 (gr_render_state_create_supersampled; 2, 3 or 4): frames are still width x height, traced at f x that per
         axis and box-averaged on the device (box_resolve says what that means).  Everything else about the state - buffer(), the
         prepass grid, tile history - is of traced_size.  filter (gr_render_state_set_filter): FILTER_BOX, or FILTER_TENT / _GAUSSIAN /
@@ -696,7 +696,9 @@ class RenderState:
         it by gr_render_analytic, and render() needs no background.  stars (gr_render_state_set_stars): (StarSky, near StarCatalogue or None, far
         StarCatalogue or None) - every frame is shaded by gr_render_stars from the catalogues; not together with sky.  glare
         (gr_render_state_set_glare): a GlareStruct (glare_gaussians, glare_exposure) - every frame delivered is then glare_frame of the
-        frame the state would have delivered as float4, applied on the device before the encode; whole frames only."""
+        frame the state would have delivered as float4, applied on the device before the encode; whole frames only.  tone
+        (gr_render_state_set_tone): a ToneStruct (pipeline.tone) - every frame delivered is then metered (auto mode), exposed and put through
+        the tone curve on the device, after the glare and before the encode: tone_frame of the frame delivered without it; whole frames only."""
         self.width, self.height, self.device = width, height, device
         self.handle = c_void_p()
         if supersample == 1:
@@ -714,6 +716,25 @@ class RenderState:
             self.set_stars(*stars)
         if glare is not None:
             self.set_glare(glare)
+        if tone is not None:
+            self.set_tone(tone)
+
+    def set_tone(self, tone):
+        """the exposure and tone curve of the frames from here on (a ToneStruct), or None: frames as they were; the adaptation starts again"""
+        check(lib.gr_render_state_set_tone(self.handle, ctypes.byref(tone) if tone is not None else None))
+
+    @property
+    def tone(self):
+        """the state's ToneStruct, or None"""
+        out, is_set = ToneStruct(), c_int()
+        check(lib.gr_render_state_tone(self.handle, ctypes.byref(out), ctypes.byref(is_set)))
+        return out if is_set.value else None
+
+    def exposure(self, stream=None):
+        """(stops, gain) of the last delivered frame of a state with a tone (gr_render_state_exposure): waits for `stream`"""
+        stops, gain = c_float(), c_float()
+        check(lib.gr_render_state_exposure(self.handle, stream, ctypes.byref(stops), ctypes.byref(gain)))
+        return stops.value, gain.value
 
     def set_glare(self, glare):
         """the PSF and exposure of the frames from here on (a GlareStruct), or None: frames as they were"""
@@ -1059,6 +1080,78 @@ def apply_glare(program, src_ptr, dst_ptr, scratch_ptr, scratch_bytes, width, he
     """glare_frame on the program's device (gr_apply_glare), bit for bit, asynchronous on `stream`: src, dst and scratch are device
     pointers to float4[width * height] frames (scratch: glare_scratch_bytes, aligned to 16) that do not overlap"""
     check(lib.gr_apply_glare(program.handle, stream, src_ptr, dst_ptr, scratch_ptr, int(scratch_bytes), int(width), int(height), ctypes.byref(glare)))
+
+
+def tone(auto=False, stops=0.0, key_stops=None, low=None, high=None, min_stops=None, max_stops=None, rate=None, curve=None, white=None):
+    """A ToneStruct (gr_tone_default, then what is given): auto - the exposure is metered on the device from every frame's luminance
+    histogram (the mean level of the pixels between the fractions low and high of the non-black ones goes to 2^key_stops, within
+    min_stops ... max_stops, approached at `rate` a frame) - or manual `stops`; curve: "linear", "reinhard" (with `white`) or "filmic", or
+    TONE_*.  The fields are checked where the struct is used."""
+    t = ToneStruct()
+    check(lib.gr_tone_default(ctypes.byref(t)))
+    t.mode, t.stops = (TONE_AUTO if auto else TONE_MANUAL), float(stops)
+    for name, value in (("key_stops", key_stops), ("low", low), ("high", high), ("min_stops", min_stops), ("max_stops", max_stops), ("rate", rate), ("white", white)):
+        if value is not None:
+            setattr(t, name, float(value))
+    if curve is not None:
+        if isinstance(curve, str) and curve not in TONE_CURVE_NAMES:
+            raise ValueError(f"tone: curve {curve!r} is none of {sorted(TONE_CURVE_NAMES)}")
+        t.curve = TONE_CURVE_NAMES[curve] if isinstance(curve, str) else int(curve)
+    return t
+
+
+def _float4_frame(who, frame):
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.ndim != 3 or frame.shape[2] != 4 or not frame.size:
+        raise ValueError(f"{who}: a frame of shape {frame.shape} is not [H, W, 4]")
+    return frame
+
+
+def meter_histogram(frame):
+    """The host statement of the meter (gr_meter_histogram_frame): float32 [H, W, 4] -> uint32 [385]: pixels by the exponent and the top
+    three mantissa bits of their Rec. 709 luminance, 8 bins an octave from 2^-24; [384] counts the pixels whose luminance is not above 0"""
+    frame = _float4_frame("meter_histogram", frame)
+    hist = np.zeros(METER_COUNTERS, dtype=np.uint32)
+    check(lib.gr_meter_histogram_frame(frame.ctypes.data_as(c_void_p), frame.shape[1], frame.shape[0], hist.ctypes.data_as(c_void_p)))
+    return hist
+
+
+def meter_solve(hist, tone, adapted=0.0, primed=False):
+    """The host statement of the solve (gr_meter_solve_host): -> (adapted, primed, gain, q); manual mode leaves the state as given"""
+    hist = np.ascontiguousarray(hist, dtype=np.uint32)
+    if hist.shape != (METER_COUNTERS,):
+        raise ValueError(f"meter_solve: a histogram of shape {hist.shape} is not [{METER_COUNTERS}]")
+    a, p, gain, q = ctypes.c_double(adapted), c_int(1 if primed else 0), c_float(), c_int()
+    check(lib.gr_meter_solve_host(hist.ctypes.data_as(c_void_p), ctypes.byref(tone), ctypes.byref(a), ctypes.byref(p), ctypes.byref(gain), ctypes.byref(q)))
+    return a.value, bool(p.value), np.float32(gain.value), q.value
+
+
+def tone_frame(frame, tone, gain, out=None):
+    """The host statement of the curve (gr_tone_frame): float32 [H, W, 4] -> [H, W, 4], r, g and b times `gain` through tone.curve, alpha
+    bit for bit; out: where to (it may be `frame` itself)"""
+    frame = _float4_frame("tone_frame", frame)
+    if out is None:
+        out = np.empty_like(frame)
+    if out.shape != frame.shape or out.dtype != np.float32 or not out.flags.c_contiguous:
+        raise ValueError("tone_frame: out is not a contiguous float32 frame of the source's shape")
+    check(lib.gr_tone_frame(frame.ctypes.data_as(c_void_p), frame.shape[1], frame.shape[0], ctypes.byref(tone), float(gain), out.ctypes.data_as(c_void_p)))
+    return out
+
+
+def meter_frame(program, src_ptr, width, height, hist_ptr, stream=None):
+    """meter_histogram on the program's device (gr_meter_frame), exactly, asynchronous on `stream`: 385 uint32 at hist_ptr, zeroed first"""
+    check(lib.gr_meter_frame(program.handle, stream, src_ptr, int(width), int(height), hist_ptr))
+
+
+def meter_solve_device(program, hist_ptr, tone, state_ptr, stream=None):
+    """meter_solve on the program's device (gr_meter_solve_device), bit for bit: state_ptr is a ToneStateStruct in device memory"""
+    check(lib.gr_meter_solve_device(program.handle, stream, hist_ptr, ctypes.byref(tone), state_ptr))
+
+
+def apply_tone(program, src_ptr, dst_ptr, width, height, tone, gain_ptr=None, gain=1.0, stream=None):
+    """tone_frame on the program's device (gr_apply_tone), bit for bit: the gain is the float at the device pointer gain_ptr, else `gain`;
+    src_ptr == dst_ptr is allowed"""
+    check(lib.gr_apply_tone(program.handle, stream, src_ptr, dst_ptr, int(width), int(height), ctypes.byref(tone), gain_ptr, float(gain)))
 
 
 def yuv420p10_bytes(width, height):

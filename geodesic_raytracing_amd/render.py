@@ -186,6 +186,34 @@ def parse_glare(text):
     return pairs
 
 
+def parse_tone_curve(text):
+    """'linear' | 'reinhard[:WHITE]' | 'filmic' -> (gra.TONE_*, white or None); ValueError otherwise"""
+    name, _, white = text.partition(":")
+    if name not in gra.TONE_CURVE_NAMES or (white and name != "reinhard") or (text.endswith(":")):
+        raise ValueError("linear, reinhard[:WHITE] or filmic, e.g. reinhard:4")
+    return gra.TONE_CURVE_NAMES[name], float(white) if white else None
+
+
+def parse_meter(text):
+    """'LOW:HIGH' -> (low, high), the metered window as fractions of the non-black pixels; ValueError otherwise"""
+    fields = text.split(":")
+    if len(fields) != 2:
+        raise ValueError("LOW:HIGH, e.g. 0.5:0.98")
+    return float(fields[0]), float(fields[1])
+
+
+def tone_of(auto_exposure=None, meter=None, adapt=None, curve=None):
+    """the CLI's four switches as one gra.ToneStruct with checked fields, or None where they ask for nothing.  auto_exposure: None, True
+    (the default key) or the key in stops; meter: (low, high); adapt: the rate; curve: (gra.TONE_*, white or None)"""
+    if auto_exposure is None and curve is None:
+        return None
+    low, high = meter if meter is not None else (None, None)
+    made = gra.tone(auto=auto_exposure is not None, key_stops=None if auto_exposure in (None, True) else auto_exposure, low=low, high=high, rate=adapt,
+                    curve=curve[0] if curve else None, white=curve[1] if curve else None)
+    gra.meter_solve(np.zeros(gra.METER_COUNTERS, dtype=np.uint32), made)   # (the library's own check of every field)
+    return made
+
+
 def checked_png_stream(who, png, png_stream):
     """the PNG stream kind as gra.PNG_STREAM_*; a kind other than literals is a property of device-made files"""
     if png_stream not in gra.PNG_STREAM_NAMES and png_stream not in gra.PNG_STREAM_NAMES.values():
@@ -199,11 +227,15 @@ def checked_png_stream(who, png, png_stream):
 def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, camera_quat=None, redshift=False, adaptive=False,
            background=None, device=0, fov=90.0, universe=20.0, wait_for_static=True, geodesic_speed=None, geodesic_times=None,
            parallel_transport=True, supersample=1, rgba8=False, mips="host", yuv420=False, cameras=None, bit_depth=8, shutter_samples=0, filter="box",
-           png="host", jpeg=None, quality=90, png_stream="literals", sky=None, glare=None, exposure=0.0, exr=None):
+           png="host", jpeg=None, quality=90, png_stream="literals", sky=None, glare=None, exposure=0.0, exr=None, tone=None, exposures=None):
     """exr: "host" or "device" (float frames only: no rgba8, yuv420, png="device" or jpeg) - every frame returned is the bytes of a finished
     OpenEXR file of scene-linear half floats instead of pixels: with "device" the float4 frame stays on the device and is converted,
     predicted, histogrammed and bit-packed there (pipeline.ExrEncoder), with "host" it comes back and pipeline.exr_encode_host makes the
     file - the same bytes.
+    tone: a gra.ToneStruct (pipeline.tone) - every frame delivered is metered (auto mode), exposed and put through the tone curve on the
+    device, after the glare and before any encode (RenderState(tone=)); along a sequence the exposure adapts at tone.rate.  exposures: a
+    list that receives (stops, gain) of every frame delivered - in auto mode by RenderState.exposure() after the frame's own download, a
+    24-byte copy and a wait more a frame (leave it None where frames must stay in flight); a manual tone's pair is computed once on the host.  Whole frames only.
     glare: a gra.GlareStruct (pipeline.glare_gaussians) or [(weight, sigma)], up to four Gaussians of sigma output pixels - every frame
     goes through that point-spread function on the device, in linear light, after the resolve and before any encode (RenderState(glare=):
     pipeline.glare_frame of the frame rendered without it, bit for bit): a star far above 1 keeps a halo in an 8-bit file.  exposure:
@@ -271,7 +303,7 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     program = manager.current(wait=wait_for_static)
     stars = sky.on(program) if isinstance(sky, StarField) else None   # (point stars: a catalogue built on this device, the same on both sides)
     state = gra.RenderState(width, height, device, supersample=supersample, filter=filter, sky=sky if stars is None else None, stars=stars,
-                            glare=glare_of(glare, exposure))
+                            glare=glare_of(glare, exposure), tone=tone)
     if sky is None:
         rgba = background if background is not None else gra.synthetic_background(2048, 1024)
         if mips == "device":
@@ -289,7 +321,15 @@ def render(metric_name, width, height, scripts=None, cfg=None, camera_pos=None, 
     mode = gra.MODE_REFERENCE if adaptive else gra.MODE_FUSED
     bg = (dbg.ptr, rgba.shape[1], rgba.shape[0], levels) if sky is None else None   # (an analytic sky: no image, no mips, no upload)
 
+    manual_exposure = state.exposure() if tone is not None and tone.mode != gra.TONE_AUTO else None   # (host arithmetic: no device call)
+
     def fetch():
+        frame = fetched()
+        if tone is not None and exposures is not None:   # auto: one more small download behind the frame's, which fetched() has waited for
+            exposures.append(state.exposure() if tone.mode == gra.TONE_AUTO else manual_exposure)
+        return frame
+
+    def fetched():
         if encoder is not None:
             return encoder.encode(out.ptr, None)   # the frame's stream: the encoder's launches queue behind the frame's
         if pinned is None:
@@ -526,6 +566,16 @@ def main(argv=None):
                     "core keeps the rest), e.g. 0.06:1.5,0.03:10 - a star far above 1 keeps a halo in an 8-bit file.  Not with --devices")
     ap.add_argument("--exposure", type=float, default=None, metavar="STOPS", help="a gain of 2^STOPS on the same stage, -32 ... 32; works alone.  Not "
                     "with --devices")
+    ap.add_argument("--auto-exposure", nargs="?", const="key", default=None, metavar="KEY_STOPS", help="meter every frame on the device - a luminance "
+                    "histogram of the finished frame, solved there to the gain that puts the metered level at 2^KEY_STOPS (log2 0.18 = -2.47) - in "
+                    "sixteenths of a stop, no host round trip; along --frames the exposure adapts (--adapt) and every frame's stops are printed.  "
+                    "Not with --exposure or --devices")
+    ap.add_argument("--meter", default=None, metavar="LOW:HIGH", help="with --auto-exposure: the metered window, as fractions of the pixels that are "
+                    "not black, ordered by luminance (0.5:0.98)")
+    ap.add_argument("--adapt", type=float, default=None, metavar="RATE", help="with --auto-exposure: the share of the way to a frame's own exposure that "
+                    "the sequence moves a frame, (0, 1] (1: every frame on its own)")
+    ap.add_argument("--tone", default=None, metavar="CURVE", help="linear, reinhard[:WHITE] or filmic: the curve after the gain, on the device before any "
+                    "encode - reinhard (white point WHITE, 4) and filmic roll highlights off instead of clipping them at 1.  Not with --devices")
     ap.add_argument("--devices", default=None, help="0,1,2,3: deal the rows of every frame to these GPUs (one process, peer copies; a device may "
                     "repeat); each traces, resolves and - with --encode device - encodes its share, the share rotating over --frames")
     ap.add_argument("--fps", default="24", help="frame rate of a .y4m or .avi file: N or N/D (24; 30000/1001)")
@@ -617,6 +667,20 @@ def main(argv=None):
             glare = glare_of(parse_glare(a.glare) if a.glare is not None else [], a.exposure or 0.0) or gra.glare_gaussians()
         except (ValueError, gra.GeodesicError) as e:
             ap.error(f"--glare {a.glare} --exposure {a.exposure}: {e}")
+    tone = None
+    given = [name for name, value in (("--auto-exposure", a.auto_exposure), ("--meter", a.meter), ("--adapt", a.adapt), ("--tone", a.tone)) if value is not None]
+    if given:
+        if a.devices is not None:
+            ap.error(f"{given[0]} with --devices: a histogram of a strip is not the frame's, and the curve follows the meter; render such frames on one device")
+        if a.auto_exposure is not None and a.exposure is not None:
+            ap.error("--auto-exposure with --exposure: the exposure is either metered or given")
+        if a.auto_exposure is None and (a.meter is not None or a.adapt is not None):
+            ap.error(f"{'--meter' if a.meter is not None else '--adapt'} without --auto-exposure: there is no meter to set")
+        try:
+            key = None if a.auto_exposure is None else True if a.auto_exposure == "key" else float(a.auto_exposure)
+            tone = tone_of(key, parse_meter(a.meter) if a.meter is not None else None, a.adapt, parse_tone_curve(a.tone) if a.tone is not None else None)
+        except (ValueError, gra.GeodesicError) as e:
+            ap.error(f"{' '.join(given)}: {e}")
     if video and a.devices is not None:
         ap.error("--out NAME.y4m with --devices: a split frame travels as float4 or RGBA8, not as 4:2:0 planes; render the video on one device")
     if (a.camera_to or a.quat_to) and a.geodesic_speed:
@@ -665,14 +729,18 @@ def main(argv=None):
             cameras = camera_path_at(position, quat, *ends, max(a.frames, 1), moments) if samples else camera_path(position, quat, *ends, max(a.frames, 1))
         except ValueError as e:
             ap.error(f"--camera-to / --quat-to: {e}")
+    exposures = []
     result = render(a.metric, w, h, a.scripts, cfg, position, quat, a.redshift, a.adaptive,
                     read_png(a.background) if a.background else None, a.device, a.fov, a.universe, geodesic_speed=speed,
                     geodesic_times=[a.geodesic_time + float(t) * a.geodesic_dt for t in moments] if samples else times,
                     parallel_transport=not a.recompute_tetrads, supersample=a.supersample,
                     rgba8=a.encode == "device" and not video, mips=a.mips, yuv420=video, cameras=cameras, bit_depth=a.bit_depth, shutter_samples=samples,
-                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream, sky=sky, glare=glare, exr=a.exr)
+                    filter=a.filter, png=a.png, jpeg=a.jpeg, quality=a.quality or 90, png_stream=a.png_stream, sky=sky, glare=glare, exr=a.exr, tone=tone, exposures=exposures)
     if speed is None and cameras is None:
         result = [result]
+    if tone is not None and tone.mode == gra.TONE_AUTO:
+        for i, (stops, gain) in enumerate(exposures):
+            print(f"frame {i}: exposure {stops:+.4f} stops (gain {gain:.6g})")
     if video:
         with Y4MWriter(a.out, w, h, fps, bit_depth=a.bit_depth) as stream:
             for frame in result:

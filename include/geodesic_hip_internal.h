@@ -532,6 +532,102 @@ int gr_apply_glare(gr_program* p, void* stream, const void* src, void* dst, void
 int gr_render_state_set_glare(gr_render_state* s, const struct gr_glare* glare_or_null);
 int gr_render_state_glare(const gr_render_state* s, struct gr_glare* out, int* is_set);
 
+/* ---- Metering and tone curve ----------------------------------------------------------------------------------------------------------
+ * The gain that puts a frame into the range the sinks keep, chosen on the device from the frame itself, and a curve that rolls highlights
+ * off instead of clipping them.  Both sit after the glare and before the encode, and nothing on the frame path waits for the host: the
+ * meter reduces the finished frame to a luminance histogram, one wave solves it to an exposure and adapts it from frame to frame, and the
+ * curve reads the gain from the device word the solve wrote.  (Declared here for the reason "Glare" gives: the contract header gains
+ * nothing.)
+ *
+ * 1. The histogram - exact integers.  s is the source, float4, W x H.  Per pixel
+ *      Y = ((0.2126f * r) + (0.7152f * g)) + (0.0722f * b)          five fp32 operations, each rounded once, NEVER fused
+ *    black: Y > 0 is false (a zero of either sign, a negative value, NaN): counted in hist[384].  Otherwise e = bits(Y) >> 20 (the exponent
+ *    and the top three bits of the mantissa: 8 bins an octave) and bin = clamp((int)e - 824, 0, 383); 824 = (127 - 24) * 8, so bin 0 starts
+ *    at 2^-24 and bin 383 ends below 2^24; everything smaller, subnormals included, lands in bin 0, everything larger, +infinity included,
+ *    in bin 383.  The pixel is counted in hist[bin].  hist is 385 uint32 counters; a frame has at most 2^31 - 1 pixels, so none overflows.
+ *    No logarithm is taken, the counts are a function of the frame alone, and host and device agree exactly.
+ * 2. The solve - double, a handful of operations, every one a single IEEE double operation, none contracted, host and device the same bits.
+ *      N = hist[0] + ... + hist[383] (an integer)      lo = (double)low * N      hi = (double)high * N      c_b = the count below bin b
+ *      w_b = max(0, min(c_b + hist[b], hi) - max(c_b, lo))        min(a, b) = a < b ? a : b, max(a, b) = a > b ? a : b
+ *      W = the sum of w_b, M = the sum of (w_b * (b + 0.5)), both in ascending b        level = M / W / 8 - 24
+ *      auto = min(max(key_stops - level, min_stops), max_stops)
+ *    The adaptation state is a double `adapted` and a flag `primed`.  Not primed: adapted = auto, and the state becomes primed.  Primed:
+ *    adapted = adapted + rate * (auto - adapted).  A frame with N == 0 changes nothing: it uses adapted if primed, else 0 stops.  Manual
+ *    mode: adapted = stops, and the state is neither read nor written.  The gain:
+ *      q = nearbyint(adapted * 16), ties to even        gain = ldexpf(T[q mod 16], floor(q / 16))        T[i] = (float)exp2(i / 16.0)
+ *    with q mod 16 in 0 ... 15.  T is GR_TONE_SIXTEENTHS below, 16 hex float literals that host and kernel share; neither evaluates exp2.
+ *    So the exposure moves in sixteenths of a stop and is reproducible to the bit.
+ * 3. The curve.  Per r, g and b, every step a single fp32 IEEE operation in the order written, NEVER fused, the division IEEE's:
+ *      v = gain * c        x = v > 0 ? (v < 16777216.f ? v : 16777216.f) : 0.f        (NaN, negatives and -0 become +0; infinity 2^24)
+ *      GR_TONE_LINEAR     y = x
+ *      GR_TONE_REINHARD   a = x * iw2;  n = x * (1 + a);  y = n / (1 + x)        iw2 = (float)(1.0 / ((double)white * white)), on the host
+ *      GR_TONE_FILMIC     n = x * ((2.51f * x) + 0.03f);  d = (x * ((2.43f * x) + 0.59f)) + 0.14f;  y = n / d;  y = y < 1 ? y : 1
+ *    Alpha passes bit for bit.  The output is still linear-light float4: the sinks' own transfer curves stay as they are. */
+#define GR_TONE_MANUAL 0
+#define GR_TONE_AUTO 1
+#define GR_TONE_LINEAR 0
+#define GR_TONE_REINHARD 1
+#define GR_TONE_FILMIC 2
+#define GR_METER_BINS 384
+#define GR_METER_COUNTERS 385   /* [384]: black */
+#define GR_TONE_SIXTEENTHS {0x1.000000p+0f, 0x1.0b5586p+0f, 0x1.172b84p+0f, 0x1.2387a6p+0f, 0x1.306fe0p+0f, 0x1.3dea64p+0f, 0x1.4bfdaep+0f, 0x1.5ab07ep+0f, \
+                            0x1.6a09e6p+0f, 0x1.7a1148p+0f, 0x1.8ace54p+0f, 0x1.9c4918p+0f, 0x1.ae89fap+0f, 0x1.c199bep+0f, 0x1.d5818ep+0f, 0x1.ea4afap+0f}
+struct gr_tone {
+    int mode;               /* GR_TONE_MANUAL, GR_TONE_AUTO */
+    float stops;            /* manual: -32 ... 32 */
+    float key_stops;        /* auto: where the metered level goes, -32 ... 32; default (float)log2(0.18) = -0x1.3ca9c6p+1f */
+    float low, high;        /* the metered window, fractions of the non-black pixels: 0 <= low < high <= 1; default 0.5, 0.98 */
+    float min_stops, max_stops;   /* -32 <= min_stops <= max_stops <= 32; default -32, 32 */
+    float rate;             /* (0, 1]; default 1: no memory */
+    int curve;              /* GR_TONE_LINEAR, _REINHARD, _FILMIC; default linear */
+    float white;            /* Reinhard's white point: finite, (0, 4096]; default 4 */
+};
+/* what the solve keeps in DEVICE memory from frame to frame (adapted, primed: the 16 bytes of adaptation state) and what it writes for
+ * the curve and for gr_render_state_exposure (q, gain); 24 bytes, aligned to 8.  All zero: not primed. */
+struct gr_tone_state {
+    double adapted;
+    int primed;
+    int q;
+    float gain;
+    int reserved;
+};
+/* Every function below refuses, before any device call and before it writes anything, with GR_ERROR_INVALID_ARGUMENT and a message that
+ * names the function and the field: a NULL; a size below 1; more than 2^31 - 1 pixels; a field of *tone out of its range or not finite -
+ * all fields are checked in both modes -, low >= high, min_stops > max_stops, an unknown mode or curve; a gain that is not finite or is
+ * negative; the launchers also a NULL program and a device pointer that is not aligned (frames to 16 bytes, the state to 8, counters to 4). */
+int gr_tone_default(struct gr_tone* out);   /* manual, 0 stops, and the defaults above */
+/* The host statements of 1, 2 and 3, compiled so that nothing is contracted.  src, dst: float[4 * width * height]; hist: 385 counters,
+ * written (not added to).  gr_meter_solve_host reads and writes *adapted and *primed as 2 says (manual mode: neither), and writes *gain
+ * and *q.  gr_tone_frame takes the gain as a value; src == dst is allowed. */
+int gr_meter_histogram_frame(const float* src, int width, int height, unsigned* hist);
+int gr_meter_solve_host(const unsigned* hist, const struct gr_tone* tone, double* adapted, int* primed, float* gain, int* q);
+int gr_tone_frame(const float* src, int width, int height, const struct gr_tone* tone, float gain, float* dst);
+/* The same on the device (kernels/tone.hip, set-up module: IEEE arithmetic, no contraction), asynchronous on `stream`; *tone is HOST
+ * memory and travels in the argument block.  gr_meter_frame zeroes device_hist (385 words) on the stream and launches gr_meter_histogram
+ * - a one-dimensional grid of at most 1024 workgroups that walk tiles of 1024 pixels.  gr_meter_solve_device (auto mode only: a manual
+ * gain is the host's) launches gr_meter_solve, one wave, which reads device_hist and *device_state and writes *device_state.
+ * gr_apply_tone launches gr_tone_apply: the gain is the float at device_gain (&state->gain), or host_gain where that is NULL; the mode
+ * of *tone is not looked at; src == dst is allowed, any other overlap is not. */
+int gr_meter_frame(gr_program* p, void* stream, const void* src, int width, int height, void* device_hist);
+int gr_meter_solve_device(gr_program* p, void* stream, const void* device_hist, const struct gr_tone* tone, void* device_state);
+int gr_apply_tone(gr_program* p, void* stream, const void* src, void* dst, int width, int height, const struct gr_tone* tone,
+                  const void* device_gain_or_null, float host_gain);
+/* The tone of a state's frames.  NULL (the default): every entry point is as it was, launch for launch.  With a tone set the order of a
+ * delivery (gr_render_frame and its three encoded kin, gr_deliver_accumulated) is: resolve, glare if one is set, meter and solve in auto
+ * mode, tone, sink at factor 1 - all four formats; a float4 delivery is toned straight into `out`, and a factor-1 box state no longer
+ * renders straight into `out`, as with a glare.  What is delivered is gr_tone_frame of the frame the state delivers without a tone,
+ * with the gain of gr_meter_solve_host of gr_meter_histogram_frame of that frame.  The traced frame and the accumulation stay as they
+ * are: gr_render_subframe accumulates untoned and the delivery meters and tones the accumulation once, after its glare.  All launches
+ * lie between the events of gr_render_state_resolve_ms, and no call on the frame path synchronises.  The adaptation state lives in the
+ * state's device memory, advances once per delivered frame, is reset by gr_render_state_set_tone (on the stream of the next delivery)
+ * and is freed with the state.  gr_render_state_exposure synchronises `stream` and downloads the last delivered frame's values: *stops =
+ * q / 16 and *gain (before any delivery: 0 and 1); it serves tests and the CLI's printout.  Whole frames only: strip_count > 1 and
+ * gr_render_frame_tiled / _tiled_as are refused before anything is rendered, because a histogram of a strip is not the frame's.
+ * gr_render_state_tone: *is_set = 1 and the tone in *out, or 0 and *out untouched. */
+int gr_render_state_set_tone(gr_render_state* s, const struct gr_tone* tone_or_null);
+int gr_render_state_tone(const gr_render_state* s, struct gr_tone* out, int* is_set);
+int gr_render_state_exposure(gr_render_state* s, void* stream, float* stops, float* gain);
+
 /* ---- PNG frames -----------------------------------------------------------------------------------------------------------------------
  * A PNG encoder behind an RGBA8 frame that is already in device memory (gr_render_frame_rgba8, gr_deliver_accumulated(GR_FRAME_RGBA8),
  * participant 0's frame of gr_render_frame_tiled_as): filtering, histogram and bit-packing run on the device (kernels/png.hip, set-up
