@@ -35,6 +35,7 @@
 #include "jsfront.hpp"
 #include "metric_codegen.hpp"
 #include "program_build.hpp"
+#include "trace_plan.hpp"
 
 namespace {
 
@@ -44,10 +45,6 @@ int fail(gr_status code, const std::string& msg) {
     g_error = msg;
     return (int)code;
 }
-
-#ifndef GR_DEFAULT_SPECULATIVE_CLASSES
-#define GR_DEFAULT_SPECULATIVE_CLASSES 5   // gr_trace_fused: the list's first classes do not wait for the prepass cells of their own launch
-#endif
 
 #define GR_TRY_BEGIN try {
 #define GR_TRY_END                                                                 \
@@ -990,6 +987,33 @@ int gr_internal::launch(gr_program* p, int k, void* stream, unsigned gx, unsigne
 }
 int gr_internal::device_of(const gr_program* p) { return p->device; }
 const void* gr_internal::no_count_of(const gr_program* p) { return p->huge_count; }
+gr_internal::program_facts gr_internal::facts_of(const gr_program* p) {
+    program_facts f;
+    if (!p) return f;
+    f.compute_units = p->compute_units; f.cell_rows = p->cell_rows; f.tile_shading = p->tile_shading;
+    f.has_pair = p->fn[K_TRACE_PAIR] != nullptr; f.has_parking = p->fn[K_TRACE_FUSED_PARKING] != nullptr;
+    return f;
+}
+int gr_internal::resident_groups_per_cu(gr_program* p, int k, int wg, int* per_cu) {
+    if (!p->resident_groups_per_cu[k]) {
+        int n = 0;
+        if (hipSetDevice(p->device) != hipSuccess) return fail(GR_ERROR_DEVICE, "hipSetDevice");
+        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&n, function_of(p, k), wg, 0) != hipSuccess || n < 1) {
+            (void)hipGetLastError();
+            n = 4 * 8 * 64 / wg;
+        }
+        p->resident_groups_per_cu[k] = n;
+    }
+    *per_cu = p->resident_groups_per_cu[k];
+    return GR_OK;
+}
+int gr_internal::draw_ticket(gr_program* p, void* stream, unsigned int** ticket) {
+    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, "null program");
+    *ticket = p->tickets + (p->next_ticket.fetch_add(1) % gr_program::TICKET_RING);
+    HIP_CHECK(hipSetDevice(p->device));
+    HIP_CHECK(hipMemsetAsync(*ticket, 0, sizeof(unsigned int), (hipStream_t)stream));
+    return GR_OK;
+}
 }
 using gr_internal::blocks, gr_internal::launch;
 
@@ -1063,7 +1087,7 @@ int gr_handle_adaptive_sampling(gr_program* p, void* stream, const void* rays, c
     return launch(p, K_ADAPTIVE, stream, blocks(width / 2, 8), blocks(height / 2, 8), 8, 8, args);
 }
 
-// (the shading pass's launchers - gr_render and its kin, gr_strip_local_blocks, the analytic sky - are in shading.cpp)
+// (the shading pass's launchers - gr_render and its kin, the analytic sky - are in shading.cpp; gr_strip_local_blocks is in trace_plan.cpp)
 
 // What the resolve, present and accumulate launchers below refuse alike, before any device call: a NULL buffer; a NULL program where the
 // launcher answers for it under its own name (launch() refuses it for the others); a factor outside 1 ... 4; a size below 1 or with more
@@ -1085,8 +1109,9 @@ static int launch_dealt_rows(int k, gr_program* p, void* stream, const void* src
                              int strip_rank, int strip_count, int compact_out) {
     const char* who = KERNEL_NAMES[k];
     if (int rc = refuse_frame_launch(who, p, false, src, dst, width, height, factor, 0)) return rc;
-    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = height; }
-    if (block_rows <= 0 || strip_rank < 0 || strip_rank >= strip_count) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": bad strip parameters");
+    const trace_plan::strip_share share = trace_plan::strips(height, block_rows, strip_rank, strip_count, trace_plan::THE_HEIGHT);
+    if (share.bad) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": bad strip parameters");
+    block_rows = share.block_rows; strip_rank = share.strip_rank; strip_count = share.strip_count;
     int local_rows = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_rows;
     void* args[] = {&src, &dst, &width, &height, &factor, &block_rows, &strip_rank, &strip_count, &compact_out, &local_rows};
     return launch(p, k, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
@@ -1336,439 +1361,11 @@ int gr_build_mipped_background(gr_program* p, void* stream, const void* rgba8, i
 
 int gr_internal_fail(int code, const char* msg) { return fail((gr_status)code, msg ? msg : ""); }
 
-int gr_prepass_fused_strips(gr_program* p, void* stream, const void* camera_generic, const void* camera_quat, void* term,
-                            int prepass_width, int prepass_height, const void* e0, const void* e1, const void* e2, const void* e3,
-                            const void* cfg, const void* dfg, int image_height, int block_rows, int strip_rank, int strip_count,
-                            void* cell_attempts, int row_margin) {
-    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = 8; }
-    if (block_rows <= 0 || strip_rank < 0 || strip_rank >= strip_count || image_height <= 0)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "bad strip description");
-    void* args[] = {&camera_generic, &camera_quat, &term, &prepass_width, &prepass_height, &e0, &e1, &e2, &e3, &cfg, &dfg,
-                    &image_height, &block_rows, &strip_rank, &strip_count, &cell_attempts, &row_margin};
-    if (row_margin < 0) return fail(GR_ERROR_INVALID_ARGUMENT, "negative row margin");
-    return launch(p, K_PREPASS_FUSED, stream, blocks((long long)prepass_width * prepass_height, 64), 1, 64, 1, args);
-}
-
-int gr_camera_prepass(gr_program* p, void* stream, const void* position_cart, float flip, const float basis_speed[3], void* position_generic_out,
-                      void* e0_out, void* e1_out, void* e2_out, void* e3_out, const void* camera_quat, void* term, int prepass_width,
-                      int prepass_height, const void* cfg, const void* dfg, int image_height, int block_rows, int strip_rank, int strip_count,
-                      void* cell_attempts, int row_margin) {
-    if (!basis_speed) return fail(GR_ERROR_INVALID_ARGUMENT, "null basis speed");
-    if (prepass_width < 0 || prepass_height < 0) return fail(GR_ERROR_INVALID_ARGUMENT, "negative prepass size");
-    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = 8; }
-    if (block_rows <= 0 || strip_rank < 0 || strip_rank >= strip_count) return fail(GR_ERROR_INVALID_ARGUMENT, "bad strip description");
-    if (image_height <= 0) image_height = prepass_height > 0 ? prepass_height * 16 : 16;
-    float sx = basis_speed[0], sy = basis_speed[1], sz = basis_speed[2];
-    if (row_margin < 0) return fail(GR_ERROR_INVALID_ARGUMENT, "negative row margin");
-    // the camera's coordinates and tetrad: one lane of the set-up module (IEEE arithmetic, kernels/camera.hip) ...
-    void* setup_args[] = {&position_cart, &flip, &sx, &sy, &sz, &position_generic_out, &e0_out, &e1_out, &e2_out, &e3_out, &cfg};
-    int rc = launch(p, K_CAMERA_SETUP, stream, 1, 1, 64, 1, setup_args);
-    if (rc != GR_OK) return rc;
-    // ... then the prepass grid reads them back (same stream)
-    const long long cells = (long long)prepass_width * prepass_height;
-    if (cells <= 0) return GR_OK;
-    const void* camera_generic = position_generic_out;
-    const void *e0 = e0_out, *e1 = e1_out, *e2 = e2_out, *e3 = e3_out;
-    void* args[] = {&camera_generic, &camera_quat, &term, &prepass_width, &prepass_height, &e0, &e1, &e2, &e3, &cfg, &dfg,
-                    &image_height, &block_rows, &strip_rank, &strip_count, &cell_attempts, &row_margin};
-    return launch(p, K_PREPASS_FUSED, stream, blocks(cells, 64), 1, 64, 1, args);
-}
-
-int gr_prepass_fused(gr_program* p, void* stream, const void* camera_generic, const void* camera_quat, void* term,
-                     int prepass_width, int prepass_height, const void* e0, const void* e1, const void* e2, const void* e3,
-                     const void* cfg, const void* dfg) {
-    return gr_prepass_fused_strips(p, stream, camera_generic, camera_quat, term, prepass_width, prepass_height, e0, e1, e2, e3, cfg, dfg,
-                                   prepass_height * 16, 8, 0, 1, nullptr, 0);
-}
-
-// tiles (one wave each) a device traces: its row blocks cut into 8x8 tiles + per block the halo row in 64-pixel pieces; 0 when
-// the description is invalid (trace_launch says why)
-static long long device_tile_count(int width, int height, int block_rows, int strip_rank, int strip_count) {
-    const int T = 8;
-    if (width <= 0 || height <= 0) return 0;
-    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = ((height + T - 1) / T) * T; }
-    if (block_rows <= 0 || block_rows % T != 0 || strip_rank < 0 || strip_rank >= strip_count) return 0;
-    long long per_block = (long long)((width + T - 1) / T) * (block_rows / T) + (strip_count > 1 ? (width + 63) / 64 : 0);
-    return per_block * gr_strip_local_blocks(height, block_rows, strip_rank, strip_count);
-}
-
-long long gr_tile_order_bytes(int width, int height, int block_rows, int strip_rank, int strip_count) {
-    return (32 + 2 * device_tile_count(width, height, block_rows, strip_rank, strip_count)) * 4;   // header (2 x 16 classes), list, classes
-}
-
-static int order_tiles_launch(gr_program* p, void* stream, const void* term, const void* cell_attempts, int prepass_width, int prepass_height,
-                              int width, int height, int block_rows, int strip_rank, int strip_count, void* tile_order, const void* tile_history,
-                              int shift_x = 0, int shift_y = 0) {
-    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = ((height + 7) / 8) * 8; }
-    long long tiles = device_tile_count(width, height, block_rows, strip_rank, strip_count);
-    if (tiles <= 0 || tiles > 0x7fffffff) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_order_tiles: bad image or strip description");
-    int total = (int)tiles;
-    HIP_CHECK(hipSetDevice(p->device));
-    HIP_CHECK(hipMemsetAsync(tile_order, 0, 128, (hipStream_t)stream));
-    // how far (in tiles) a tile looks around itself in the history: the image may have moved by that much since
-    static const int reach_default = [] { const char* e = getenv("GR_TILE_HISTORY_REACH"); int v = e ? atoi(e) : 2; return (v >= 0 && v <= 8) ? v : 2; }();
-    int history_reach = reach_default;
-    for (int phase = 0; phase < 2; phase++) {
-        void* args[] = {&term, &cell_attempts, &prepass_width, &prepass_height, &width, &height, &block_rows, &strip_rank, &strip_count,
-                        &total, &tile_order, &phase, &tile_history, &history_reach, &shift_x, &shift_y};
-        int rc = launch(p, K_ORDER_TILES, stream, blocks(total, 1024), 1, 1024, 1, args);
-        if (rc != GR_OK) return rc;
-    }
-    return GR_OK;
-}
-
-int gr_order_tiles(gr_program* p, void* stream, const void* term, const void* cell_attempts, int prepass_width, int prepass_height,
-                   int width, int height, int block_rows, int strip_rank, int strip_count, void* tile_order) {
-    if (!p || !term || !cell_attempts || !tile_order || prepass_width <= 0 || prepass_height <= 0)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "gr_order_tiles: null argument or no prepass");
-    return order_tiles_launch(p, stream, term, cell_attempts, prepass_width, prepass_height, width, height, block_rows, strip_rank, strip_count,
-                              tile_order, nullptr);
-}
-
-int gr_order_tiles_by_history(gr_program* p, void* stream, const void* tile_history, int width, int height, int block_rows, int strip_rank,
-                              int strip_count, void* tile_order, int shift_x, int shift_y) {
-    if (!p || !tile_history || !tile_order) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_order_tiles_by_history: null argument");
-    return order_tiles_launch(p, stream, nullptr, nullptr, 0, 0, width, height, block_rows, strip_rank, strip_count, tile_order, tile_history,
-                              shift_x, shift_y);
-}
-
-// workgroups of `wg` lanes of a trace kernel the device holds at once (asked of the runtime once per kernel); < 0: -error code
-static long long resident_trace_groups(gr_program* p, int kernel_index, int wg) {
-    if (!p->resident_groups_per_cu[kernel_index]) {
-        int n = 0;
-        if (hipSetDevice(p->device) != hipSuccess) return -(long long)fail(GR_ERROR_DEVICE, "hipSetDevice");
-        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&n, function_of(p, kernel_index), wg, 0) != hipSuccess || n < 1) {
-            (void)hipGetLastError();
-            n = 4 * 8 * 64 / wg;
-        }
-        p->resident_groups_per_cu[kernel_index] = n;
-    }
-    return (long long)p->compute_units * p->resident_groups_per_cu[kernel_index];
-}
-
-size_t gr_parking_lot_bytes(int slots, int groups, size_t* words_bytes) {
-    if (words_bytes) *words_bytes = (16 + (size_t)(groups > 0 ? groups : 0)) * sizeof(unsigned int);
-    return (size_t)(slots > 0 ? slots : 0) * 6 * 16;
-}
-
-long long gr_trace_fused_wave_slots(gr_program* p) {
-    if (!p) return 0;
-    const long long groups = resident_trace_groups(p, K_TRACE_FUSED, 256);
-    return groups < 0 ? 0 : groups * 4;
-}
-
-// gr_trace_fused (rays_per_lane 1) and gr_trace_pair (2): same tiles, same arguments; a pair wave takes two tile-waves
-static int trace_launch(gr_program* p, int rays_per_lane, void* stream, const void* camera_generic, const void* camera_quat, void* rdata,
-                        int width, int height, int block_rows, int strip_rank, int strip_count, const void* term, int prepass_width,
-                        int prepass_height, const void* e0, const void* e1, const void* e2, const void* e3, const void* cfg,
-                        const void* dfg, void* attempt_counter, int lattice = 1, int pending_only = 0, const void* tile_order = nullptr,
-                        int waves_per_simd = 0, const gr_trace_shading* shading_in = nullptr, int inline_prepass = 0, void* tile_cost = nullptr,
-                        int tile_order_by_history = 0, void* lattice_rays = nullptr, const gr_parking_lot* parking = nullptr,
-                        int speculative_classes_in = 0, void* guessed = nullptr) {
-    const int T = 8;
-    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, "null program");
-    // the prepass inside the launch: its cell waves are the first tickets (gr_trace_fused's prepass_tickets)
-    int prepass_tickets = 0;
-    if (inline_prepass) {
-        if (rays_per_lane != 1 || pending_only || (tile_order && !tile_order_by_history) || !term || prepass_width <= 0 ||
-            prepass_height <= 0 || prepass_width == width || prepass_height == height)
-            return fail(GR_ERROR_INVALID_ARGUMENT, "inline_prepass: gr_trace_fused on every pixel of its rows (or the lattice launch of adaptive sampling), in image order or the order of "
-                                                   "gr_order_tiles_by_history (gr_order_tiles' needs the prepass first), with a prepass grid");
-        // a cell wave is 8 x 8 cells (trace.hip: GR_CELL_BLOCK; a program built with -DGR_CELL_BLOCK=0 takes 64 cells of a row)
-        prepass_tickets = p->cell_rows ? (int)(((long long)prepass_width * prepass_height + 63) / 64) : ((prepass_width + 7) / 8) * ((prepass_height + 7) / 8);
-    }
-    if ((lattice != 1 && lattice != 2) || ((lattice == 2 || pending_only) && rays_per_lane != 1))
-        return fail(GR_ERROR_INVALID_ARGUMENT, "lattice / pending_only: gr_trace_fused only");
-    const bool parks = parking && parking->lanes > 0;
-    if (parks) {
-        if (!p->fn[K_TRACE_FUSED_PARKING])
-            return fail(GR_ERROR_INVALID_ARGUMENT, "parking: the program was built without -DGR_PARKING in its argument string (gr_program_has_parking)");
-        if (rays_per_lane != 1 || lattice != 1 || pending_only || (shading_in && shading_in->out))
-            return fail(GR_ERROR_INVALID_ARGUMENT, "parking: gr_trace_fused on every pixel of its rows, one ray per lane, no in-tile shading");
-        if (!parking->records || !parking->words || parking->lanes > 64 || parking->trips < 1 || parking->slots < 64 || parking->slots > (1 << 24) ||
-            parking->groups < 1)
-            return fail(GR_ERROR_INVALID_ARGUMENT, "parking: records and words (gr_parking_lot_bytes), 1 <= lanes <= 64, trips >= 1, 64 <= slots <= 2^24, groups >= 1");
-    }
-    if (rays_per_lane == 2 && !p->fn[K_TRACE_PAIR])
-        return fail(GR_ERROR_INVALID_ARGUMENT, "this program has no gr_trace_pair kernel (its expressions do not instantiate on pairs)");
-    if (strip_count <= 1) {   // one block covering the image
-        strip_count = 1;
-        strip_rank = 0;
-        block_rows = ((height + T - 1) / T) * T;
-    }
-    if (block_rows <= 0 || block_rows % T != 0 || strip_rank < 0 || strip_rank >= strip_count)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "block_rows must be a positive multiple of 8 and 0 <= strip_rank < strip_count");
-    if (strip_count > 1 && height > 1 && (height - 1) % block_rows == 0)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "the last image row must not start a block (its filter reads the row above)");
-    int local_blocks = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count);
-    long long waves_per_block = (long long)((width + T - 1) / T) * (block_rows / T) + (strip_count > 1 ? (width + 63) / 64 : 0);
-    if (lattice == 2) {   // tiles of the whole half-resolution grid, whoever owns the rows (the kernel leaves the rows of others alone)
-        waves_per_block = (long long)((width / 2 + T - 1) / T) * ((height / 2 + T - 1) / T);
-        local_blocks = 1;
-    }
-    // four tile-waves per workgroup (measured on MI355X, 4K Kerr: 64 -> 7.59 ms, 128 -> 7.43, 256 -> 7.24; one wave per SIMD
-    // still leaves the full 512-VGPR budget to the heaviest metrics).  Experiment hooks: GR_TRACE_BLOCK=64|128|256 with the
-    // kernel built with the same -DGR_TRACE_BLOCK through GR_EXTRA_FLAGS; GR_TRACE_PERSISTENT=0 launches one wave per tile.
-    static const int wg = [] { const char* e = getenv("GR_TRACE_BLOCK"); int v = e ? atoi(e) : 256; return (v == 64 || v == 128) ? v : 256; }();
-    static const bool persistent = [] { const char* e = getenv("GR_TRACE_PERSISTENT"); return !(e && e[0] == '0'); }();
-    long long waves = waves_per_block * local_blocks;
-    if (waves <= 0) return GR_OK;
-    if (waves > 0x7fffffff) return fail(GR_ERROR_INVALID_ARGUMENT, "too many tiles");
-    int total_waves = (int)waves;
-    long long groups = (((waves + rays_per_lane - 1) / rays_per_lane + prepass_tickets) * 64 + wg - 1) / wg;
-    unsigned int* tickets = nullptr;
-    // persistent mode only pays when there are more tiles than wave slots.  The launch is exactly as many workgroups as the
-    // kernel's register and scratch footprint lets the device hold (asked of the runtime once per kernel): a larger one
-    // leaves workgroups queued behind the resident ones which start only when the tickets are gone, and which the
-    // dispatcher then has to retire before the next launch's workgroups get the freed slots
-    // experiment hook: GR_TRACE_WAVES_PER_SIMD=k launches k persistent waves per SIMD whatever fits (occupancy studies)
-    static const int forced_waves_per_simd = [] { const char* e = getenv("GR_TRACE_WAVES_PER_SIMD"); int v = e ? atoi(e) : 0; return (v >= 1 && v <= 8) ? v : 0; }();
-    // (the lattice launch of adaptive sampling that leaves its rays behind is a kernel of its own: gr_trace_fused is not touched by it)
-    const int kernel_index = parks ? K_TRACE_FUSED_PARKING : rays_per_lane == 2 ? K_TRACE_PAIR : (lattice == 2 && lattice_rays) ? K_TRACE_FUSED_LATTICE : K_TRACE_FUSED;
-    long long resident_groups = resident_trace_groups(p, kernel_index, wg);
-    if (resident_groups < 0) return (int)-resident_groups;
-    // a caller that keeps several frames in flight may take fewer slots per launch: two smaller launches then share the device
-    // and the one drains while the other is in full swing (gr_frame_options.trace_waves_per_simd)
-    if (forced_waves_per_simd)
-        resident_groups = (long long)p->compute_units * 4 * forced_waves_per_simd * 64 / wg;
-    else if (waves_per_simd >= 1 && waves_per_simd <= 8)
-        resident_groups = std::min(resident_groups, (long long)p->compute_units * 4 * waves_per_simd * 64 / wg);
-    if ((persistent && groups > resident_groups) || prepass_tickets || parks || guessed) {   // (... and so do the pixels traced ahead)   // prepass tickets need the ticket order whatever the size, and so does a lot
-        tickets = p->tickets + (p->next_ticket.fetch_add(1) % gr_program::TICKET_RING);
-        HIP_CHECK(hipSetDevice(p->device));
-        HIP_CHECK(hipMemsetAsync(tickets, 0, sizeof(unsigned int), (hipStream_t)stream));
-        groups = std::min(groups, resident_groups);
-    }
-    // tiles per ticket: one, unless a wave would draw more than 32 tickets (then as many as keep it at 32, at most 8)
-    int ticket_tiles = 1;
-    if (tickets) {
-        const long long launched_waves = groups * (wg / 64);
-        const long long per_wave = (waves + prepass_tickets + launched_waves - 1) / launched_waves;
-        ticket_tiles = (int)std::min<long long>(8, std::max<long long>(1, (per_wave + 31) / 32));
-        if (const char* e = getenv("GR_TICKET_TILES")) { const int v = atoi(e); if (v >= 1 && v <= 64) ticket_tiles = v; }
-    }
-    // the kernel's trace_shading, by value (same layout)
-    struct { void* out; const void* bg1; const void* bg2; int bg_width, bg_height, bg_levels, most_probes, compact_out; } shading = {};
-    if (shading_in && shading_in->out) {
-        if (!p->tile_shading)
-            return fail(GR_ERROR_INVALID_ARGUMENT, "in-tile shading: the program was built without -DGR_TILE_SHADING in its argument string");
-        if (rays_per_lane != 1 || lattice != 1 || pending_only || width % T != 0 || height % T != 0)
-            return fail(GR_ERROR_INVALID_ARGUMENT, "in-tile shading: gr_trace_fused on every pixel of an image whose sides are multiples of 8");
-        shading.out = shading_in->out; shading.bg1 = shading_in->background1; shading.bg2 = shading_in->background2;
-        shading.bg_width = shading_in->bg_width; shading.bg_height = shading_in->bg_height; shading.bg_levels = shading_in->bg_levels;
-        shading.most_probes = shading_in->max_probes; shading.compact_out = strip_count > 1 ? shading_in->compact_out : 0;
-    }
-    if (tile_cost && (rays_per_lane != 1 || pending_only || (lattice == 2 && strip_count > 1)))
-        return fail(GR_ERROR_INVALID_ARGUMENT, "tile_cost: gr_trace_fused on every pixel of its rows, or the lattice launch of a whole frame");
-    // (every argument has been checked by now: nothing below fails for a reason of the caller's, and nothing above has touched a buffer)
-    if (prepass_tickets)   // every cell unknown (GR_CELL_UNKNOWN = -1) until its ray has been traced
-        HIP_CHECK(hipMemsetAsync(const_cast<void*>(term), 0xff, (size_t)prepass_width * prepass_height * sizeof(int), (hipStream_t)stream));
-    if (tile_cost) {
-        HIP_CHECK(hipSetDevice(p->device));
-        HIP_CHECK(hipMemsetAsync(tile_cost, 0, (size_t)total_waves * sizeof(unsigned int), (hipStream_t)stream));
-    }
-    // Whether the list's last class is a promise (gr_order_tiles: nothing to trace, nothing to look up) or a guess
-    // (gr_order_tiles_by_history) is written into the list by the launch that made it, and the kernel reads it there; the caller's
-    // flag only says which he thinks it is, for the checks above.
-    int last_class_is_skipped = 0;   // (kept in the kernel's parameter list: 1 would force the promise, nothing passes it)
-    // ... its upper bits: how many of the list's classes, dearest first, do not wait for the prepass cells they look at when those are
-    // traced by this launch (trace_fused_body: speculative tiles).  Classes are octaves of a tile's longest ray in the frame before,
-    // 16 384 attempts = class 0: the default, 5, are the tiles that had a ray of 1 024 attempts or more.
-    static const int speculative_classes = [] { const char* e = getenv("GR_SPECULATIVE_CLASSES"); int v = e ? atoi(e) : GR_DEFAULT_SPECULATIVE_CLASSES; return (v >= 0 && v <= 14) ? v : 0; }();
-    const int speculative = speculative_classes_in < 0 ? 0 : speculative_classes_in == 0 ? speculative_classes : std::min(speculative_classes_in, 14);
-    if (prepass_tickets && tile_order && tile_order_by_history && !parks) last_class_is_skipped |= speculative << 8;
-    // the kernel's parking_lot, by value (same layout); an empty lot before every launch
-    struct { void* records; void* words; int lanes, trips, slots, groups; } lot = {};
-    if (parks) {
-        lot.records = parking->records; lot.words = parking->words; lot.lanes = parking->lanes; lot.trips = parking->trips;
-        lot.slots = parking->slots; lot.groups = parking->groups;
-        HIP_CHECK(hipSetDevice(p->device));
-        HIP_CHECK(hipMemsetAsync(parking->words, 0, (16 + (size_t)parking->groups) * sizeof(unsigned int), (hipStream_t)stream));
-    }
-    void* args[] = {&camera_generic, &camera_quat, &rdata, &width, &height, &block_rows, &strip_rank, &strip_count, &term,
-                    &prepass_width, &prepass_height, &e0, &e1, &e2, &e3, &cfg, &dfg, &attempt_counter, &tickets, &total_waves,
-                    &lattice, &pending_only, &tile_order, &shading, &prepass_tickets, &ticket_tiles, &tile_cost,
-                    &last_class_is_skipped, &lattice_rays, &lot, &guessed};   // the last eleven: gr_trace_fused only (gr_trace_pair's parameter list ends before them), the lot gr_trace_fused_parking and (unused) gr_trace_fused_lattice, the very last gr_trace_fused_lattice only
-    return launch(p, kernel_index, stream, (unsigned)groups, 1, wg, 1, args);
-}
-
-int gr_trace_fused_adaptive(gr_program* p, void* stream, const void* camera_generic, const void* camera_quat, void* rdata, int width,
-                            int height, const void* term, int prepass_width, int prepass_height, const void* e0, const void* e1,
-                            const void* e2, const void* e3, const void* cfg, const void* dfg, void* attempt_counter, int lattice,
-                            int pending_only, void* lattice_rays) {
-    return trace_launch(p, 1, stream, camera_generic, camera_quat, rdata, width, height, 0, 0, 1, term, prepass_width, prepass_height, e0, e1,
-                        e2, e3, cfg, dfg, attempt_counter, lattice, pending_only, nullptr, 0, nullptr, 0, nullptr, 0,
-                        lattice == 2 ? lattice_rays : nullptr);
-}
-
-int gr_adaptive_refine_strips(gr_program* p, void* stream, void* rdata, void* pending_count, int width, int height, const void* dfg,
-                              int block_rows, int strip_rank, int strip_count, const void* lattice_rays, const void* cfg) {
-    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = ((height + 7) / 8) * 8; }
-    if (block_rows <= 0 || block_rows % 8 != 0 || strip_rank < 0 || strip_rank >= strip_count)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "bad strip description");
-    if (lattice_rays && !cfg) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_adaptive_refine: lattice_rays needs the metric's cfg");
-    void* pending_list = nullptr;
-    int phase = 0;
-    const void* block_cost_before = nullptr;
-    void* args[] = {&rdata, &pending_count, &width, &height, &dfg, &block_rows, &strip_rank, &strip_count, &lattice_rays, &cfg, &pending_list, &phase,
-                    &block_cost_before};
-    return launch(p, K_ADAPTIVE_REFINE, stream, (unsigned)((width / 2 + 15) / 16), (unsigned)((height / 2 + 15) / 16), 16, 16, args);
-}
-
-size_t gr_pending_list_bytes(int width, int height) {
-    if (width < 2 || height < 2) return 0;
-    return (128 + 3 * (size_t)(width / 2) * (height / 2)) * sizeof(unsigned int);   // 64 class counts, 64 cursors, the pixels
-}
-
-size_t gr_lattice_rays_bytes(int width, int height) {
-    if (width < 2 || height < 2) return 0;
-    return (size_t)(width / 2) * (height / 2) * (3 * 16 + 4);   // three float4 of end state + the ray's attempts per lattice pixel
-}
-
-int gr_adaptive_refine_list(gr_program* p, void* stream, void* rdata, void* pending_count, int width, int height, const void* dfg, int block_rows,
-                            int strip_rank, int strip_count, const void* lattice_rays, const void* cfg, void* pending_list,
-                            const void* block_cost_before) {
-    if (!p || !rdata || !pending_list) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_adaptive_refine_list: null argument");
-    if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = ((height + 7) / 8) * 8; }
-    if (block_rows <= 0 || block_rows % 8 != 0 || strip_rank < 0 || strip_rank >= strip_count)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "bad strip description");
-    if (lattice_rays && !cfg) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_adaptive_refine_list: lattice_rays needs the metric's cfg");
-    HIP_CHECK(hipSetDevice(p->device));
-    HIP_CHECK(hipMemsetAsync(pending_list, 0, 128 * sizeof(unsigned int), (hipStream_t)stream));
-    for (int phase = 0; phase < 2; phase++) {   // decide, mark and count by cost class; then deal every marked pixel its place
-        void* args[] = {&rdata, &pending_count, &width, &height, &dfg, &block_rows, &strip_rank, &strip_count, &lattice_rays, &cfg, &pending_list, &phase,
-                        &block_cost_before};
-        int rc = launch(p, K_ADAPTIVE_REFINE, stream, (unsigned)((width / 2 + 15) / 16), (unsigned)((height / 2 + 15) / 16), 16, 16, args);
-        if (rc != GR_OK) return rc;
-    }
-    return GR_OK;
-}
-
-int gr_trace_pending(gr_program* p, void* stream, const void* camera_generic, const void* camera_quat, void* rdata, int width, int height,
-                     const void* e0, const void* e1, const void* e2, const void* e3, const void* cfg, const void* dfg, void* attempt_counter,
-                     const void* pending_list, int waves_per_simd, void* block_cost, void* guessed_next) {
-    if (!p || !rdata || !pending_list) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_trace_pending: null argument");
-    if (width < 2 || height < 2) return GR_OK;
-    const int wg = 256;
-    long long groups = resident_trace_groups(p, K_TRACE_PENDING, wg);
-    if (groups < 0) return (int)-groups;
-    if (waves_per_simd >= 1 && waves_per_simd <= 8) groups = std::min(groups, (long long)p->compute_units * 4 * waves_per_simd * 64 / wg);
-    // (how many entries the list holds is only known on the device: the launch fills the machine and its waves draw tickets until
-    // the list is used up - no more workgroups than the worst case needs, though)
-    const long long worst = (3LL * (width / 2) * (height / 2) + wg - 1) / wg;
-    groups = std::max(1LL, std::min(groups, worst));
-    unsigned int* tickets = p->tickets + (p->next_ticket.fetch_add(1) % gr_program::TICKET_RING);
-    HIP_CHECK(hipSetDevice(p->device));
-    HIP_CHECK(hipMemsetAsync(tickets, 0, sizeof(unsigned int), (hipStream_t)stream));
-    void* args[] = {&camera_generic, &camera_quat, &rdata, &width, &height, &e0, &e1, &e2, &e3, &cfg, &dfg, &attempt_counter, &tickets, &pending_list,
-                    &block_cost, &guessed_next};
-    return launch(p, K_TRACE_PENDING, stream, (unsigned)groups, 1, wg, 1, args);
-}
-
-size_t gr_guessed_bytes(void) { return (8 + (size_t)65536 * (1 + 1 + 8)) * sizeof(unsigned int); }   // program.hip: GR_GUESSED_HEADER, GR_GUESSED_CAPACITY pixels, attempts, records
-
-int gr_apply_guessed(gr_program* p, void* stream, void* rdata, int width, const void* guessed, void* guessed_next, void* block_cost, void* attempt_counter) {
-    if (!p || !rdata || !guessed || width < 2) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_apply_guessed: null argument");
-    void* args[] = {&rdata, &width, &guessed, &guessed_next, &block_cost, &attempt_counter};
-    return launch(p, K_APPLY_GUESSED, stream, 65536 / 256, 1, 256, 1, args);
-}
-
-// gr_do_generic_rays over ray records in 8x8-tile slot order with the fused trace's scheduling (kernels/trace.hip): the device filled
-// once, tiles drawn from a ticket counter in `tile_order`'s order (NULL: slot order), each tile's cost left in `tile_cost` (NULL: not).
-int gr_do_generic_rays_scheduled(gr_program* p, void* stream, void* rays, const void* ray_count, int tile_count, const void* cfg, const void* dfg,
-                                 void* attempt_counter, const void* tile_order, void* tile_cost) {
-    if (!p || !rays || !ray_count) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_do_generic_rays_scheduled: null argument");
-    if (tile_count < 1) return GR_OK;
-    long long groups = resident_trace_groups(p, K_DO_RAYS_SCHEDULED, 64);
-    if (groups < 0) return (int)-groups;
-    // experiment hook: GR_SCHEDULED_WAVES_PER_SIMD=k launches k persistent waves per SIMD whatever fits (occupancy studies)
-    static const int forced = [] { const char* e = getenv("GR_SCHEDULED_WAVES_PER_SIMD"); int v = e ? atoi(e) : 0; return (v >= 1 && v <= 8) ? v : 0; }();
-    if (forced) groups = (long long)p->compute_units * 4 * forced;
-    groups = std::max(1LL, std::min(groups, (long long)tile_count));
-    unsigned int* tickets = p->tickets + (p->next_ticket.fetch_add(1) % gr_program::TICKET_RING);
-    HIP_CHECK(hipSetDevice(p->device));
-    HIP_CHECK(hipMemsetAsync(tickets, 0, sizeof(unsigned int), (hipStream_t)stream));
-    void* args[] = {&rays, &ray_count, &cfg, &dfg, &attempt_counter, &tickets, &tile_count, &tile_order, &tile_cost};
-    return launch(p, K_DO_RAYS_SCHEDULED, stream, (unsigned)groups, 1, 64, 1, args);
-}
-
-int gr_sort_tiles_by_cost(gr_program* p, void* stream, const void* tile_cost, int tiles_x, int tiles_y, void* tile_order, void* work) {
-    if (!p || !tile_cost || !tile_order || !work) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_sort_tiles_by_cost: null argument");
-    const int tile_count = tiles_x * tiles_y;
-    if (tile_count < 1) return GR_OK;
-    HIP_CHECK(hipSetDevice(p->device));
-    HIP_CHECK(hipMemsetAsync(work, 0, 128 * sizeof(unsigned int), (hipStream_t)stream));
-    void* count_args[] = {&tile_cost, &tiles_x, &tiles_y, &work};
-    int rc = launch(p, K_SORT_TILES_COUNT, stream, blocks(tile_count, 256), 1, 256, 1, count_args);
-    if (rc != GR_OK) return rc;
-    int n = tile_count;
-    void* place_args[] = {&n, &work, &tile_order};
-    return launch(p, K_SORT_TILES_PLACE, stream, blocks(tile_count, 256), 1, 256, 1, place_args);
-}
-
-int gr_adaptive_refine(gr_program* p, void* stream, void* rdata, void* pending_count, int width, int height, const void* dfg,
-                       const void* lattice_rays, const void* cfg) {
-    return gr_adaptive_refine_strips(p, stream, rdata, pending_count, width, height, dfg, 0, 0, 1, lattice_rays, cfg);
-}
-
-int gr_trace_fused(gr_program* p, void* stream, const void* camera_generic, const void* camera_quat, void* rdata, int width,
-                   int height, int block_rows, int strip_rank, int strip_count, const void* term, int prepass_width,
-                   int prepass_height, const void* e0, const void* e1, const void* e2, const void* e3, const void* cfg,
-                   const void* dfg, void* attempt_counter) {
-    return trace_launch(p, 1, stream, camera_generic, camera_quat, rdata, width, height, block_rows, strip_rank, strip_count, term,
-                        prepass_width, prepass_height, e0, e1, e2, e3, cfg, dfg, attempt_counter);
-}
-
-int gr_trace_fused_launch(gr_program* p, void* stream, const gr_trace_fused_args* a) {
-    if (!a) return fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
-    return trace_launch(p, 1, stream, a->camera_generic, a->camera_quat, a->render_data, a->width, a->height, a->block_rows, a->strip_rank,
-                        a->strip_count, a->termination_buffer, a->prepass_width, a->prepass_height, a->e0, a->e1, a->e2, a->e3, a->cfg, a->dfg,
-                        a->attempt_counter, a->lattice == 2 ? 2 : 1, a->pending_only ? 1 : 0, a->tile_order, a->waves_per_simd, &a->shading,
-                        a->inline_prepass ? 1 : 0, a->tile_cost, a->tile_order_by_history ? 1 : 0, a->lattice == 2 ? a->lattice_rays : nullptr, &a->parking, a->speculative_classes, a->lattice == 2 ? a->guessed : nullptr);
-}
-
-int gr_trace_pair(gr_program* p, void* stream, const void* camera_generic, const void* camera_quat, void* rdata, int width,
-                  int height, int block_rows, int strip_rank, int strip_count, const void* term, int prepass_width,
-                  int prepass_height, const void* e0, const void* e1, const void* e2, const void* e3, const void* cfg,
-                  const void* dfg, void* attempt_counter) {
-    return trace_launch(p, 2, stream, camera_generic, camera_quat, rdata, width, height, block_rows, strip_rank, strip_count, term,
-                        prepass_width, prepass_height, e0, e1, e2, e3, cfg, dfg, attempt_counter);
-}
-
+// (the trace stage's launchers - prepass, tile order, gr_trace_fused and its kin, refine, pending, scheduled, compact - are in
+// trace_launch.cpp, their decisions in trace_plan.cpp)
 int gr_program_has_trace_pair(const gr_program* p) { return p && p->fn[K_TRACE_PAIR] ? 1 : 0; }
 int gr_program_has_tile_shading(const gr_program* p) { return p && p->tile_shading ? 1 : 0; }
 int gr_program_has_parking(const gr_program* p) { return p && p->fn[K_TRACE_FUSED_PARKING] ? 1 : 0; }
-
-int gr_trace_compact(gr_program* p, void* stream, const void* camera_generic, const void* camera_quat, void* rdata, int width,
-                     int height, int block_rows, int strip_rank, int strip_count, const void* term, int prepass_width,
-                     int prepass_height, const void* e0, const void* e1, const void* e2, const void* e3, const void* cfg,
-                     const void* dfg, void* attempt_counter, int keep_lanes) {
-    const int T = 8;
-    if (keep_lanes < 1 || keep_lanes > 64) return fail(GR_ERROR_INVALID_ARGUMENT, "keep_lanes must be 1..64");
-    if (strip_count <= 1) {
-        strip_count = 1;
-        strip_rank = 0;
-        block_rows = ((height + T - 1) / T) * T;
-    }
-    if (block_rows <= 0 || block_rows % T != 0 || strip_rank < 0 || strip_rank >= strip_count)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "block_rows must be a positive multiple of 8 and 0 <= strip_rank < strip_count");
-    if (strip_count > 1 && height > 1 && (height - 1) % block_rows == 0)
-        return fail(GR_ERROR_INVALID_ARGUMENT, "the last image row must not start a block (its filter reads the row above)");
-    int local_blocks = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count);
-    long long waves_per_block = (long long)((width + T - 1) / T) * (block_rows / T) + (strip_count > 1 ? (width + 63) / 64 : 0);
-    long long waves = waves_per_block * local_blocks;
-    if (waves <= 0) return GR_OK;
-    if (waves * 64 > 0x7fffffffLL) return fail(GR_ERROR_INVALID_ARGUMENT, "too many ray slots");
-    const int wg = 256;
-    unsigned int total_slots = (unsigned int)(waves * 64);
-    long long groups = std::min<long long>((waves * 64 + wg - 1) / wg, (long long)p->compute_units * 32 * 64 / wg);
-    unsigned int* tickets = p->tickets + (p->next_ticket.fetch_add(1) % gr_program::TICKET_RING);
-    HIP_CHECK(hipSetDevice(p->device));
-    HIP_CHECK(hipMemsetAsync(tickets, 0, sizeof(unsigned int), (hipStream_t)stream));
-    void* args[] = {&camera_generic, &camera_quat, &rdata, &width, &height, &block_rows, &strip_rank, &strip_count, &term,
-                    &prepass_width, &prepass_height, &e0, &e1, &e2, &e3, &cfg, &dfg, &attempt_counter, &tickets, &total_slots, &keep_lanes};
-    return launch(p, K_TRACE_COMPACT, stream, (unsigned)groups, 1, wg, 1, args);
-}
 
 // ---- camera on a timelike geodesic (cl.cl:2441-2481, 3117-3141, 4735-4940, 2569-2620, 2738-2872) --------------------
 

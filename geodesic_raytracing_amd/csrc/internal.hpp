@@ -57,6 +57,18 @@ int launch(gr_program* p, int k, void* stream, unsigned gx, unsigned gy, unsigne
 int device_of(const gr_program* p);
 const void* no_count_of(const gr_program* p);   // the device int INT_MAX that a range launch hands its kernel as the records' count
 inline unsigned blocks(long long n, int b) { return n <= 0 ? 0u : (unsigned)((n + b - 1) / b); }
+// capi.cpp, for the trace launchers (trace_launch.cpp, which decides by trace_plan.hpp): what a plan needs to know of a program ...
+struct program_facts {
+    int compute_units = 0;
+    bool cell_rows = false, tile_shading = false;    // built with -DGR_CELL_BLOCK=0, with -DGR_TILE_SHADING
+    bool has_pair = false, has_parking = false;      // gr_trace_pair, gr_trace_fused_parking
+};
+program_facts facts_of(const gr_program* p);
+// ... the workgroups of `wg` lanes of kernel k that one compute unit holds at once (asked of the runtime once per kernel; where it
+// does not say, 4 SIMDs x 8 waves: 4 * 8 * 64 / wg); GR_OK or the status, its text set ...
+int resident_groups_per_cu(gr_program* p, int k, int wg, int* per_cu);
+// ... and the counter of a launch by ticket: the next one of the program's ring, zeroed on `stream` (the device set)
+int draw_ticket(gr_program* p, void* stream, unsigned int** ticket);
 // A launcher refuses a NULL where its kernel dereferences unconditionally: the reference's clSetKernelArg returns CL_INVALID_MEM_OBJECT
 // for a null buffer, a HIP launch takes it and the device faults (and a device fault ends the process).  cfg / dfg are not checked:
 // a substituted program reads neither.

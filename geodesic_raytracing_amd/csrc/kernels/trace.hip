@@ -788,7 +788,7 @@ __device__ __forceinline__ void trace_tile(int wave, int lane, const float4* __r
     if (tile_cost && !(PARKING && from_lot)) atomicMax(tile_cost + __builtin_amdgcn_readfirstlane(wave), tries);   // (uniform by construction; said so for the reduction)
 }
 
-// workgroup size of the fused trace kernel: 4 tile-waves, one per SIMD of a CU (capi.cpp launches with the same number)
+// workgroup size of the fused trace kernel: 4 tile-waves, one per SIMD of a CU (trace_plan.cpp: the launch's is the same number)
 #ifndef GR_TRACE_BLOCK
 #define GR_TRACE_BLOCK 256
 #endif

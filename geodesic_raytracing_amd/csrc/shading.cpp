@@ -87,12 +87,6 @@ int gr_render(gr_program* p, void* stream, const void* rdata, const void* rdata_
                           whole_frame(num_pixels, rdata_count));
 }
 
-int gr_strip_local_blocks(int height, int block_rows, int strip_rank, int strip_count) {
-    if (block_rows <= 0 || strip_count <= 0) return 0;
-    int total = (height + block_rows - 1) / block_rows;
-    return strip_rank < total ? (total - strip_rank + strip_count - 1) / strip_count : 0;
-}
-
 int gr_render_strips(gr_program* p, void* stream, const void* rdata, void* out, const void* bg1, const void* bg2, int bg_width,
                      int bg_height, int bg_levels, int width, int height, int block_rows, int strip_rank, int strip_count,
                      int compact_out, int max_probes, const void* cfg, const void* dfg) {

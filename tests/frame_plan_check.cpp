@@ -7,7 +7,7 @@
 
 using namespace frame_plan;
 
-// gr_tile_order_bytes (csrc/capi.cpp) restated: 32 header words, one id and one class per tile of the device's row blocks
+// gr_tile_order_bytes (csrc/trace_launch.cpp) restated: 32 header words, one id and one class per tile of the device's row blocks
 static long long order_bytes(int width, int height, int block_rows, int strip_rank, int strip_count) {
     if (strip_count <= 1) { strip_count = 1; strip_rank = 0; block_rows = ((height + 7) / 8) * 8; }
     long long blocks = 0;

@@ -161,7 +161,7 @@ def cell_rows_needed(ph, H, block_rows, rank, count, margin):
 
 
 def split_is_refused(h, block_rows, count):
-    """the host's condition (trace_launch, capi.cpp): the last image row must not start a block of a split frame"""
+    """the host's condition (plan_trace, csrc/trace_plan.cpp): the last image row must not start a block of a split frame"""
     return count > 1 and h > 1 and (h - 1) % block_rows == 0
 
 
