@@ -30,12 +30,10 @@
 
 #include "builtin_metrics.hpp"
 #include "codeobject.hpp"
-#include "frame_format.hpp"
 #include "internal.hpp"
 #include "jsfront.hpp"
 #include "metric_codegen.hpp"
 #include "program_build.hpp"
-#include "trace_plan.hpp"
 
 namespace {
 
@@ -1089,209 +1087,8 @@ int gr_handle_adaptive_sampling(gr_program* p, void* stream, const void* rays, c
 
 // (the shading pass's launchers - gr_render and its kin, the analytic sky - are in shading.cpp; gr_strip_local_blocks is in trace_plan.cpp)
 
-// What the resolve, present and accumulate launchers below refuse alike, before any device call: a NULL buffer; a NULL program where the
-// launcher answers for it under its own name (launch() refuses it for the others); a factor outside 1 ... 4; a size below 1 or with more
-// than 2^31 - 1 source pixels; then grid_rows workgroup rows that the grid does not hold (0: no such check; a caller's blocks() of a bad size is 0 too).
-static int refuse_frame_launch(const char* who, const gr_program* p, bool needs_program, const void* src, const void* dst, int width, int height,
-                               int factor, unsigned grid_rows) {
-    GR_NEED(who, src, dst);
-    if (needs_program && !p) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": null program");
-    if (factor < 1 || factor > 4) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": factor " + std::to_string(factor) + " (1 to 4)");
-    if (width <= 0 || height <= 0 || (long long)width * factor * height * factor > 0x7fffffffll)
-        return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the frame's size");
-    if (grid_rows > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a frame of " + std::to_string(height) + " rows does not fit the grid");
-    return GR_OK;
-}
-
-// one work item per output pixel of this device's rows, a wave on 64 consecutive pixels of one row, four rows to a workgroup: the grid
-// and the row dealing of kernels/resolve.hip and of gr_present_rgba8
-static int launch_dealt_rows(int k, gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int block_rows,
-                             int strip_rank, int strip_count, int compact_out) {
-    const char* who = KERNEL_NAMES[k];
-    if (int rc = refuse_frame_launch(who, p, false, src, dst, width, height, factor, 0)) return rc;
-    const trace_plan::strip_share share = trace_plan::strips(height, block_rows, strip_rank, strip_count, trace_plan::THE_HEIGHT);
-    if (share.bad) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": bad strip parameters");
-    block_rows = share.block_rows; strip_rank = share.strip_rank; strip_count = share.strip_count;
-    int local_rows = gr_strip_local_blocks(height, block_rows, strip_rank, strip_count) * block_rows;
-    void* args[] = {&src, &dst, &width, &height, &factor, &block_rows, &strip_rank, &strip_count, &compact_out, &local_rows};
-    return launch(p, k, stream, blocks(width, 64), blocks(local_rows, 4), 64, 4, args);
-}
-
-// the box filter of a supersampled frame (kernels/resolve.hip)
-int gr_resolve_supersampled(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int block_rows,
-                            int strip_rank, int strip_count, int compact_out) {
-    return launch_dealt_rows(K_RESOLVE_SUPERSAMPLED, p, stream, src, dst, width, height, factor, block_rows, strip_rank, strip_count, compact_out);
-}
-
-// gr_resolve_supersampled fused with the 8-bit sRGB encode (kernels/present.hip): the same grid, the same row dealing, one uint32 a pixel
-int gr_present_rgba8(gr_program* p, void* stream, const void* src, void* dst_rgba8, int width, int height, int factor, int block_rows,
-                     int strip_rank, int strip_count, int compact_out) {
-    return launch_dealt_rows(K_PRESENT_RGBA8, p, stream, src, dst_rgba8, width, height, factor, block_rows, strip_rank, strip_count, compact_out);
-}
-
-// gr_present_rgba8's resolve and encode, then BT.709 Y'CbCr 4:2:0 (kernels/present.hip: gr_present_yuv420, and gr_present_yuv420p10 with ten
-// bits a sample in 16-bit words): a lane per 2 rows x 4 columns, a workgroup of 64 x 4 lanes on 256 columns x 8 rows.  Whole frames only.
-// The two differ in the kernel and in dst's alignment, which is the format's (frame_format.cpp).  Everything is refused before the first device call.
-static int launch_video(int k, int format, gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout) {
-    const char* who = KERNEL_NAMES[k];
-    const unsigned gx = blocks(((long long)width + 3) / 4, 64), gy = blocks(((long long)height + 1) / 2, 4);
-    if (int rc = refuse_frame_launch(who, p, true, src, dst, width, height, factor, gy)) return rc;
-    const std::string wrong = frame_format::refusal(format, false, layout, (uintptr_t)dst, &width, 1);
-    if (!wrong.empty()) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + wrong);
-    void* args[] = {&src, &dst, &width, &height, &factor, &layout};
-    return launch(p, k, stream, gx, gy, 64, 4, args);
-}
-int gr_present_yuv420(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout) {
-    return launch_video(K_PRESENT_YUV420, GR_FRAME_YUV420, p, stream, src, dst, width, height, factor, layout);
-}
-int gr_present_yuv420p10(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, int layout) {
-    return launch_video(K_PRESENT_YUV420P10, GR_FRAME_YUV420P10, p, stream, src, dst, width, height, factor, layout);
-}
-
-// one sub-frame of a shutter into the accumulation frame (kernels/shutter.hip): gr_resolve_supersampled's grid over the whole frame; with
-// `first` the accumulation frame is written without being read.  Everything is refused before the first device call.
-int gr_shutter_accumulate(gr_program* p, void* stream, const void* src, void* accum, int width, int height, int factor, float weight, int first) {
-    const char* who = "gr_shutter_accumulate";
-    const unsigned gy = blocks(height, 4);
-    if (int rc = refuse_frame_launch(who, p, true, src, accum, width, height, factor, gy)) return rc;
-    if (src == accum) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": the sub-frame and the accumulation frame are one buffer");
-    if (!std::isfinite(weight)) return fail(GR_ERROR_INVALID_ARGUMENT, std::string(who) + ": a weight that is not finite");
-    first = first ? 1 : 0;
-    void* args[] = {&src, &accum, &width, &height, &factor, &weight, &first};
-    return launch(p, K_SHUTTER_ACCUMULATE, stream, blocks(width, 64), gy, 64, 4, args);
-}
-
-// a filtered frame (kernels/filter.hip; geodesic_hip_internal.h, "Filtered frames"): one workgroup of 256 lanes per tile of 32 x 8 output
-// pixels (the kernel's GR_FILTER_TX x GR_FILTER_TY), the taps - host memory - copied into the argument block.  gr_filter_frame's refusals
-// (imageio.cpp) and the grid's, all before the first device call.
-int gr_resolve_filtered(gr_program* p, void* stream, const void* src, void* dst, int width, int height, int factor, const float* taps, int count) {
-    const std::string who = "gr_resolve_filtered: ";
-    if (!src || !dst || !taps) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a required buffer is NULL");
-    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
-    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
-    if (const char* wrong = gr_internal_filter_table_error(factor, taps, count)) return fail(GR_ERROR_INVALID_ARGUMENT, who + wrong);
-    if (src == dst) return fail(GR_ERROR_INVALID_ARGUMENT, who + "src and dst are one buffer");
-    if ((long long)width * factor * height * factor > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, who + "more than 2^31 - 1 source pixels");
-    const unsigned gy = blocks(height, 8);
-    if (gy > 65535u) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a frame of " + std::to_string(height) + " rows does not fit the grid");
-    struct { float tap[GR_FILTER_MAX_TAPS]; } table = {};
-    std::copy(taps, taps + count, table.tap);
-    void* args[] = {&src, &dst, &width, &height, &factor, &count, &table};
-    return launch(p, K_RESOLVE_FILTERED, stream, blocks(width, 32), gy, 256, 1, args);
-}
-
-// ---- glare (kernels/glare.hip; geodesic_hip_internal.h, "Glare") -----------------------------------------------------------------------
-
-int gr_glare_scratch_bytes(int width, int height, size_t* bytes) {
-    if (!bytes) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_glare_scratch_bytes: null argument");
-    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_glare_scratch_bytes: a size below 1");
-    if ((long long)width * height > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, "gr_glare_scratch_bytes: more than 2^31 - 1 pixels");
-    *bytes = (size_t)width * (size_t)height * 4 * sizeof(float);   // h_k of the one component in flight
-    return GR_OK;
-}
-
-// No component: one elementwise launch.  Otherwise, per component, gr_glare_rows (256 pixels of a row a workgroup) from src into scratch
-// and gr_glare_columns (16 x 64 pixels a workgroup) from scratch into dst, which adds the component to core * src (the first) or to what
-// dst holds (the others); the component's taps - host memory - are copied into the argument block.  The grids are one-dimensional and at
-// most 2^20 workgroups: a workgroup walks the tiles with the grid's stride.  gr_glare_frame's refusals (imageio.cpp) and the buffers', all
-// before the first device call.
-int gr_apply_glare(gr_program* p, void* stream, const void* src, void* dst, void* scratch, size_t scratch_bytes, int width, int height,
-                   const gr_glare* g) {
-    const std::string who = "gr_apply_glare: ";
-    if (!src || !dst || !scratch || !g) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null argument");
-    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
-    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
-    if ((long long)width * height > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, who + "more than 2^31 - 1 pixels");
-    if (src == dst) return fail(GR_ERROR_INVALID_ARGUMENT, who + "src and dst are one buffer");
-    if (int rc = gr_internal_check_glare("gr_apply_glare", g)) return rc;
-    const size_t frame_bytes = (size_t)width * (size_t)height * 4 * sizeof(float);
-    if (scratch_bytes < frame_bytes)
-        return fail(GR_ERROR_INVALID_ARGUMENT, who + "scratch of " + std::to_string(scratch_bytes) + " bytes is too short (gr_glare_scratch_bytes: " + std::to_string(frame_bytes) + ")");
-    if ((uintptr_t)scratch % 16) return fail(GR_ERROR_INVALID_ARGUMENT, who + "scratch is not aligned to 16 bytes");
-    const auto overlap = [](const void* a, size_t na, const void* b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; };
-    if (overlap(src, frame_bytes, dst, frame_bytes) || overlap(src, frame_bytes, scratch, scratch_bytes) || overlap(dst, frame_bytes, scratch, scratch_bytes))
-        return fail(GR_ERROR_INVALID_ARGUMENT, who + "src, dst and scratch overlap");
-    const unsigned long long pixels = (unsigned long long)width * (unsigned long long)height;
-    const auto grid = [](unsigned long long tiles) { return (unsigned)std::min<unsigned long long>(tiles, 1ull << 20); };
-    if (g->components == 0) {
-        float scale = g->core;
-        unsigned long long count = pixels;
-        void* args[] = {&src, &dst, &count, &scale};
-        return launch(p, K_GLARE_SCALE, stream, grid((pixels + 255) / 256), 1, 256, 1, args);
-    }
-    const unsigned long long row_tiles = (((unsigned long long)width + 255) / 256) * (unsigned long long)height;
-    const unsigned long long column_tiles = (((unsigned long long)width + 15) / 16) * (((unsigned long long)height + 63) / 64);
-    for (int k = 0; k < g->components; k++) {
-        struct { float tap[GR_GLARE_MAX_TAPS]; } table = {};
-        std::copy(g->tap[k], g->tap[k] + g->taps[k], table.tap);
-        int count = g->taps[k], first = k == 0 ? 1 : 0;
-        float scale = g->core, weight = g->weight[k];
-        const void* rows = scratch;
-        const void* previous = first ? src : dst;
-        void* row_args[] = {&src, &scratch, &width, &height, &count, &table};
-        if (int rc = launch(p, K_GLARE_ROWS, stream, grid(row_tiles), 1, 256, 1, row_args)) return rc;
-        void* column_args[] = {&rows, &previous, &dst, &width, &height, &count, &scale, &weight, &first, &table};
-        if (int rc = launch(p, K_GLARE_COLUMNS, stream, grid(column_tiles), 1, 256, 1, column_args)) return rc;
-    }
-    return GR_OK;
-}
-
-// ---- metering and tone curve (kernels/tone.hip; geodesic_hip_internal.h, "Metering and tone curve") ----------------------------------
-
-// The 385 counters are zeroed on the stream, then one launch: a one-dimensional grid of at most METER_MAX_WORKGROUPS workgroups of
-// METER_LANES lanes, each walking tiles of METER_TILE pixels with the grid's stride.  METER_TILE and METER_LANES are tone.hip's
-// GR_METER_TILE and GR_METER_LANES (tests/test_tone_abi.py holds the two files to one value).
-static const unsigned long long METER_TILE = 1024, METER_MAX_WORKGROUPS = 1024;
-static const unsigned METER_LANES = 256;
-int gr_meter_frame(gr_program* p, void* stream, const void* src, int width, int height, void* device_hist) {
-    const std::string who = "gr_meter_frame: ";
-    if (!src || !device_hist) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null argument");
-    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
-    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
-    if ((long long)width * height > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, who + "more than 2^31 - 1 pixels");
-    if ((uintptr_t)src % 16) return fail(GR_ERROR_INVALID_ARGUMENT, who + "src is not aligned to 16 bytes");
-    if ((uintptr_t)device_hist % 4) return fail(GR_ERROR_INVALID_ARGUMENT, who + "device_hist is not aligned to 4 bytes");
-    HIP_CHECK(hipMemsetAsync(device_hist, 0, GR_METER_COUNTERS * sizeof(unsigned), (hipStream_t)stream));
-    unsigned long long pixels = (unsigned long long)width * (unsigned long long)height;
-    const unsigned grid = (unsigned)std::min<unsigned long long>((pixels + METER_TILE - 1) / METER_TILE, METER_MAX_WORKGROUPS);
-    void* args[] = {&src, &pixels, &device_hist};
-    return launch(p, K_METER_HISTOGRAM, stream, grid, 1, METER_LANES, 1, args);
-}
-
-int gr_meter_solve_device(gr_program* p, void* stream, const void* device_hist, const gr_tone* tone, void* device_state) {
-    const std::string who = "gr_meter_solve_device: ";
-    if (!device_hist || !tone || !device_state) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null argument");
-    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
-    if (int rc = gr_internal_check_tone("gr_meter_solve_device", tone)) return rc;
-    if (tone->mode != GR_TONE_AUTO) return fail(GR_ERROR_INVALID_ARGUMENT, who + "mode is not GR_TONE_AUTO (a manual gain is gr_meter_solve_host's)");
-    if ((uintptr_t)device_hist % 4) return fail(GR_ERROR_INVALID_ARGUMENT, who + "device_hist is not aligned to 4 bytes");
-    if ((uintptr_t)device_state % 8) return fail(GR_ERROR_INVALID_ARGUMENT, who + "device_state is not aligned to 8 bytes");
-    float key = tone->key_stops, low = tone->low, high = tone->high, lowest = tone->min_stops, highest = tone->max_stops, rate = tone->rate;
-    void* args[] = {&device_hist, &device_state, &key, &low, &high, &lowest, &highest, &rate};
-    return launch(p, K_METER_SOLVE, stream, 1, 1, 64, 1, args);
-}
-
-int gr_apply_tone(gr_program* p, void* stream, const void* src, void* dst, int width, int height, const gr_tone* tone, const void* device_gain,
-                  float host_gain) {
-    const std::string who = "gr_apply_tone: ";
-    if (!src || !dst || !tone) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null argument");
-    if (!p) return fail(GR_ERROR_INVALID_ARGUMENT, who + "null program");
-    if (width < 1 || height < 1) return fail(GR_ERROR_INVALID_ARGUMENT, who + "a size below 1");
-    if ((long long)width * height > 0x7fffffffll) return fail(GR_ERROR_INVALID_ARGUMENT, who + "more than 2^31 - 1 pixels");
-    if (int rc = gr_internal_check_tone("gr_apply_tone", tone)) return rc;
-    if (!device_gain && (!std::isfinite(host_gain) || host_gain < 0.f)) return fail(GR_ERROR_INVALID_ARGUMENT, who + "host_gain is not finite or is negative");
-    if ((uintptr_t)src % 16 || (uintptr_t)dst % 16) return fail(GR_ERROR_INVALID_ARGUMENT, who + "src or dst is not aligned to 16 bytes");
-    if ((uintptr_t)device_gain % 4) return fail(GR_ERROR_INVALID_ARGUMENT, who + "device_gain is not aligned to 4 bytes");
-    const size_t frame_bytes = (size_t)width * (size_t)height * 4 * sizeof(float);
-    if (src != dst && (uintptr_t)src < (uintptr_t)dst + frame_bytes && (uintptr_t)dst < (uintptr_t)src + frame_bytes)
-        return fail(GR_ERROR_INVALID_ARGUMENT, who + "src and dst overlap and are not one buffer");
-    unsigned long long pixels = (unsigned long long)width * (unsigned long long)height;
-    int curve = tone->curve;
-    float iw2 = gr_internal_tone_inverse_white_squared(tone);
-    const unsigned grid = (unsigned)std::min<unsigned long long>((pixels + 255) / 256, 1ull << 20);
-    void* args[] = {&src, &dst, &pixels, &curve, &iw2, &device_gain, &host_gain};
-    return launch(p, K_TONE_APPLY, stream, grid, 1, 256, 1, args);
-}
+// (the launchers of the stages behind the trace - resolve, present, shutter, filter, glare, meter, solve, tone - are in frame_launch.cpp,
+// the order a delivery calls them in is delivery_plan.cpp's)
 
 // ---- the sky's mip slices on the device (kernels/background.hip) ------------------------------------
 

@@ -3,6 +3,8 @@
 // Reference counterparts: render_state.hpp:97-197 (buffers), main.cpp:2244-2526 (the sequence of
 // launches on one in-order queue), execute_kernel main.cpp:139-205.  Everything is asynchronous on
 // the caller's stream; the only host->device traffic per frame is camera (48 B), cfg and features.
+// What a frame decides is in frame_plan.cpp, what its delivery decides - the stages behind the trace, their order and their buffers -
+// in delivery_plan.cpp; both are host-tested, and this file gathers their inputs and carries their plans out.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -13,6 +15,7 @@
 #include <vector>
 #include <mutex>
 
+#include "delivery_plan.hpp"
 #include "frame_format.hpp"
 #include "frame_plan.hpp"
 #include "internal.hpp"
@@ -73,27 +76,20 @@ struct gr_render_state {
     // sub-frame; accumulated: sub-frames in it since the last one with `first` (0: nothing to add to, nothing to deliver)
     void* accumulation = nullptr;
     unsigned long long accumulated = 0;
-    // gr_render_state_set_filter: GR_FILTER_BOX is the box average of resolve.hip, launch for launch as before; any other filter goes
-    // through gr_resolve_filtered into filtered_frame (float4[out_width * out_height], allocated with the first frame that is not refused)
+    // What gr_render_state_set_filter, _set_glare and _set_tone set, and the buffers their stages work in (delivery_plan.hpp tells the
+    // chain and names the buffers: filtered_frame is its RESOLVED).  Each is float4[out_width * out_height] - but tone_words: a
+    // gr_tone_state, then the 385 counters - and is allocated with the first call whose plan needs it and that is not refused.
     int filter = GR_FILTER_BOX;
     void* filtered_frame = nullptr;
-    // gr_render_state_set_glare (geodesic_hip_internal.h, "Glare"): with a glare the frame is resolved into filtered_frame (by the filter,
-    // or by the box at a factor above 1; a factor-1 box state's traced frame serves as it is), gr_apply_glare writes glare_frame (or the
-    // caller's float4 memory) through glare_scratch, and the sink reads glare_frame at factor 1.  All float4[out_width * out_height],
-    // allocated with the first frame that is not refused.
     bool glare_set = false;
     gr_glare glare{};
     void* glare_frame = nullptr;
     void* glare_scratch = nullptr;
-    // gr_render_state_set_tone (geodesic_hip_internal.h, "Metering and tone curve"): with a tone the finished frame - resolved, and glared
-    // into glare_frame if a glare is set - is metered and solved (auto mode) into tone_words (a gr_tone_state, then the 385 counters) and
-    // gr_apply_tone writes tone_frame (or the caller's float4 memory), which the sink reads at factor 1.  tone_frame is allocated with
-    // the first delivery in an encoded format, tone_words with the first in auto mode.  tone_reset: the adaptation state is zeroed on the stream of the next delivery.
     bool tone_set = false;
     gr_tone tone{};
     void* tone_frame = nullptr;
     void* tone_words = nullptr;
-    bool tone_reset = false;
+    bool tone_reset = false;   // the adaptation state is zeroed on the stream of the next delivery
     // gr_render_state_set_sky: with a sky every frame of the state is shaded by gr_render_analytic and reads no background; without
     // one (the default) by gr_render / gr_render_strips, launch for launch as before.  Shading only: the records do not depend on it.
     bool sky_set = false;
@@ -1717,6 +1713,9 @@ static int render_traced_frame(gr_render_state* s, gr_program* p, const gr_metri
 // What the entry points below deliver: the frame as render_traced_frame renders it, at the traced size, into the state's own traced frame (at factor 1
 // too: the encoders read float4 and the caller has only bytes), and from there into a sink - the caller's memory in one of the formats of frame_format.cpp,
 // or the state's accumulation frame.  A device's share of a split frame is traced in blocks of factor x as many rows: the rows its output blocks average.
+// Which stages lie between the traced frame and the sink, and in which of the state's buffers, is delivery_plan.cpp's answer (the chain is
+// told there, once); this file gathers the facts, allocates what the plan needs and calls the stages' launchers (frame_launch.cpp).
+namespace dp = delivery_plan;
 
 // The one launch that makes `out` from a float4 frame of width*factor x height*factor: the format's existing launcher - the box average
 // as float4, or resolve and encode in one pass as 8-bit sRGB or as BT.709 Y'CbCr 4:2:0 planes of 8-bit or 10-bit samples (whole frames only).
@@ -1743,129 +1742,113 @@ static int refuse_output(const char* name, int format, int layout, const void* o
 // where a delivered frame goes: encoded as (format, layout) into out, or - accumulate - weight x the frame into the accumulation frame
 struct sink { int format, layout; void* out; bool accumulate; float weight; int first; };
 
-// the two frames a glare works in (gr_render_state: glare_frame, glare_scratch), on the state's device, which the caller has set
-static int allocate_glare_frames(gr_render_state* s) {
-    const size_t bytes = (size_t)s->out_width * s->out_height * 4 * sizeof(float);
-    if (!s->glare_frame) HIP_CHECK(hipMalloc(&s->glare_frame, bytes));
-    if (!s->glare_scratch) HIP_CHECK(hipMalloc(&s->glare_scratch, bytes));
-    return GR_OK;
+// the facts of a call on this state, and what delivery_plan.cpp makes of them (options NULL: a whole frame)
+static dp::plan plan_delivery(const gr_render_state* s, dp::call_kind call, int format, const void* out, const gr_frame_options* options) {
+    dp::facts f;
+    f.factor = s->supersample;
+    f.filtered = s->filter != GR_FILTER_BOX;
+    f.glare_set = s->glare_set;
+    f.tone = !s->tone_set ? dp::TONE_NONE : s->tone.mode == GR_TONE_AUTO ? dp::TONE_AUTO : dp::TONE_MANUAL;
+    f.tone_reset = s->tone_reset || !s->tone_words;   // (words allocated by this call start zeroed too)
+    f.format = format;
+    f.call = call;
+    f.out_is_null = !out;
+    if (options) {
+        f.strip_count = options->strip_count;
+        f.mode_is_fused = options->mode == GR_MODE_FUSED;   // (as the fused path reads strips; the reference-shaped sequence renders whole frames)
+        f.block_rows = options->block_rows;
+    }
+    return dp::plan_delivery(f);
 }
 
-// what a tone works in (gr_render_state: tone_frame; tone_words: a gr_tone_state at 0, the 385 counters at 32), on the state's device
+// the state's buffer of that name (dp::buffer's first seven)
+static void** state_buffer(gr_render_state* s, int name) {
+    void** const buffers[dp::STATE_BUFFERS] = {&s->traced_frame, &s->accumulation, &s->filtered_frame, &s->glare_frame, &s->glare_scratch, &s->tone_frame, &s->tone_words};
+    return buffers[name];
+}
+
+// tone_words: a gr_tone_state at 0, the 385 counters at 32
 static const size_t TONE_WORDS_BYTES = 32 + GR_METER_COUNTERS * sizeof(unsigned);
-static bool tone_memory_missing(const gr_render_state* s, int format) {
-    return (format != GR_FRAME_F32 && !s->tone_frame) || (s->tone.mode == GR_TONE_AUTO && !s->tone_words);
-}
-// (a float4 delivery is toned straight into the caller's memory and needs no frame; a manual tone needs no words)
-static int allocate_tone_memory(gr_render_state* s, int format) {
-    if (format != GR_FRAME_F32 && !s->tone_frame) HIP_CHECK(hipMalloc(&s->tone_frame, (size_t)s->out_width * s->out_height * 4 * sizeof(float)));
-    if (s->tone.mode == GR_TONE_AUTO && !s->tone_words) {
-        HIP_CHECK(hipMalloc(&s->tone_words, TONE_WORDS_BYTES));
-        s->tone_reset = true;
+
+// What the plan needs of the state's buffers and is not there yet, on the state's device - which is set here only if something is
+// missing (render_traced_frame sets it for everything else).  The traced frame of a factor-1 state comes with the resolve's events,
+// the tone's words with a reset.
+static int allocate_missing(gr_render_state* s, unsigned needs, bool device_is_set) {
+    for (int name = 0; name < dp::STATE_BUFFERS; name++) {
+        void** buffer = state_buffer(s, name);
+        if (!(needs >> name & 1) || *buffer) continue;
+        if (!device_is_set) HIP_CHECK(hipSetDevice(s->device));
+        device_is_set = true;
+        const size_t pixels = name == dp::TRACED ? (size_t)s->width * s->height : (size_t)s->out_width * s->out_height;
+        HIP_CHECK(hipMalloc(buffer, name == dp::TONE_WORDS ? TONE_WORDS_BYTES : pixels * 4 * sizeof(float)));
+        if (name == dp::TRACED)
+            for (auto& ev : s->ev_resolve)
+                if (!ev) HIP_CHECK(hipEventCreate(&ev));
+        if (name == dp::TONE_WORDS) s->tone_reset = true;
     }
     return GR_OK;
 }
 
-// The stages between the resolve and the sink of a state with a glare, a tone or both (their memory is allocated): the glare of
-// `resolved` if one is set, the meter and the solve in auto mode, the tone; the last of them writes the caller's memory where that is
-// float4, else a frame of the state, which the format's own kernel encodes at factor 1.  No call here waits for the device.
-static int finish_frame(gr_render_state* s, gr_program* p, void* stream, const void* resolved, int format, int layout, void* out) {
+// The plan's stages, one launcher each, in order.  strips: the call's options where a stage may take a share's description from them.
+// No call here waits for the device.
+static int run_stages(const dp::plan& plan, gr_render_state* s, gr_program* p, void* stream, const sink& to, const gr_frame_options* strips,
+                      const float* taps, int tap_count) {
     const int w = s->out_width, h = s->out_height;
-    const bool into_out = format == GR_FRAME_F32;
-    const void* finished = resolved;
-    if (s->glare_set) {
-        void* glared = into_out && !s->tone_set ? out : s->glare_frame;
-        GR_CHECK(gr_apply_glare(p, stream, resolved, glared, s->glare_scratch, (size_t)w * h * 4 * sizeof(float), w, h, &s->glare));
-        finished = glared;
-    }
-    if (s->tone_set) {
-        const void* device_gain = nullptr;   // auto: the word the solve writes; manual: the host's gain in the argument block
-        float host_gain = 1.f;
-        int q = 0;
-        if (s->tone.mode == GR_TONE_AUTO) {
-            gr_tone_state* words = (gr_tone_state*)s->tone_words;
-            void* counters = (char*)s->tone_words + 32;
-            device_gain = &words->gain;
-            if (s->tone_reset) HIP_CHECK(hipMemsetAsync(s->tone_words, 0, 32, (hipStream_t)stream));
+    const auto at = [&](dp::buffer name) -> void* { return name == dp::NONE ? nullptr : name == dp::OUT ? to.out : *state_buffer(s, name); };
+    for (int i = 0; i < plan.count; i++) {
+        const dp::stage& stage = plan.stages[i];
+        const void* src = at(stage.source);
+        void* dst = at(stage.destination);
+        switch (stage.kind) {
+        case dp::FILTER: GR_CHECK(gr_resolve_filtered(p, stream, src, dst, w, h, stage.factor, taps, tap_count)); break;
+        case dp::BOX: GR_CHECK(gr_resolve_supersampled(p, stream, src, dst, w, h, stage.factor, 0, 0, 1, 0)); break;
+        case dp::GLARE: GR_CHECK(gr_apply_glare(p, stream, src, dst, s->glare_scratch, (size_t)w * h * 4 * sizeof(float), w, h, &s->glare)); break;
+        case dp::ZERO_TONE_STATE:
+            HIP_CHECK(hipMemsetAsync(s->tone_words, 0, 32, (hipStream_t)stream));
             s->tone_reset = false;
-            GR_CHECK(gr_meter_frame(p, stream, finished, w, h, counters));
-            GR_CHECK(gr_meter_solve_device(p, stream, counters, &s->tone, words));
-        } else {
-            gr_internal_tone_gain((double)s->tone.stops, &host_gain, &q);
+            break;
+        case dp::METER: GR_CHECK(gr_meter_frame(p, stream, src, w, h, (char*)s->tone_words + 32)); break;
+        case dp::SOLVE: GR_CHECK(gr_meter_solve_device(p, stream, (char*)s->tone_words + 32, &s->tone, s->tone_words)); break;
+        case dp::TONE: {   // auto: the word the solve wrote; manual: the host's gain in the argument block
+            const void* device_gain = s->tone.mode == GR_TONE_AUTO ? &((gr_tone_state*)s->tone_words)->gain : nullptr;
+            float host_gain = 1.f;
+            int q = 0;
+            if (!device_gain) gr_internal_tone_gain((double)s->tone.stops, &host_gain, &q);
+            GR_CHECK(gr_apply_tone(p, stream, src, dst, w, h, &s->tone, device_gain, host_gain));
+            break;
         }
-        void* toned = into_out ? out : s->tone_frame;
-        GR_CHECK(gr_apply_tone(p, stream, finished, toned, w, h, &s->tone, device_gain, host_gain));
-        finished = toned;
+        case dp::ACCUMULATE: GR_CHECK(gr_shutter_accumulate(p, stream, src, dst, w, h, stage.factor, to.weight, to.first)); break;
+        case dp::ENCODE: GR_CHECK(encode_frame(p, stream, to.format, to.layout, src, w, h, stage.factor, stage.with_strips ? strips : nullptr, dst)); break;
+        }
     }
-    return into_out ? GR_OK : encode_frame(p, stream, format, layout, finished, w, h, 1, nullptr, out);
+    return GR_OK;
 }
 
-// The delivery core (`name`: the entry point's, for its refusals).  What needs no device is refused first; nothing is allocated for a call that is refused.
+// The delivery core of a frame and of a sub-frame (`name`: the entry point's, for its refusals): facts, plan, refuse, allocate, render,
+// stages.  What needs no device is refused first; nothing is allocated for a call that is refused.
 static int deliver_frame(const char* name, const sink& to, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream,
                          const gr_camera* camera, const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1,
                          const void* bg2, int bg_width, int bg_height, int bg_levels, const gr_frame_options* options) {
     gr_frame_options opt;
     gr_frame_options_default(&opt);
     if (options) opt = *options;
-    const int factor = s->supersample, w = s->out_width, h = s->out_height;
-    if (opt.block_rows > 0x7fffffff / factor) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": block_rows").c_str());
-    gr_frame_options traced = opt;   // the frame behind it: blocks of factor x as many rows
-    traced.block_rows *= factor;
-    const bool filtered = s->filter != GR_FILTER_BOX;
-    if (filtered && opt.strip_count > 1)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": a state with a filter renders whole frames only (strip_count > 1): a filter "
-                                                                                "wider than a pixel reads across strip borders").c_str());
-    // a glare is applied to a delivered frame; a sub-frame is accumulated without it and gr_deliver_accumulated applies it to the sum
-    const bool glared = s->glare_set && !to.accumulate;
-    if (s->glare_set && opt.strip_count > 1)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": a state with a glare renders whole frames only (strip_count > 1): the PSF "
-                                                                                "reads across strip borders").c_str());
-    // ... and so is a tone: the delivery meters and tones the frame, or the accumulation, once
-    const bool toned = s->tone_set && !to.accumulate;
-    if (s->tone_set && opt.strip_count > 1)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(name) + ": a state with a tone renders whole frames only (strip_count > 1): a histogram "
-                                                                                "of a strip is not the frame's").c_str());
+    const dp::plan plan = plan_delivery(s, to.accumulate ? dp::ACCUMULATE_SUBFRAME : dp::DELIVER, to.format, to.out, &opt);
+    if (plan.direct)
+        return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, to.out, options);
+    if (plan.refused) return gr_internal::refuse(name, plan.refused);
     GR_CHECK(check_frame_arguments(s, p, m, camera, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, to.accumulate ? s : to.out));   // (s: any non-NULL out)
-    const bool finished = glared || toned;   // stages between the resolve and the sink: finish_frame
-    const bool resolves = filtered || (finished && factor > 1);   // into filtered_frame: by the filter, or by the box in front of a glare or a tone
-    const bool allocates = !s->traced_frame || (to.accumulate && !s->accumulation) || (resolves && !s->filtered_frame) || (glared && (!s->glare_frame || !s->glare_scratch)) ||
-                           (toned && tone_memory_missing(s, to.format));
-    if (allocates) HIP_CHECK(hipSetDevice(s->device));   // (render_traced_frame sets it for everything else)
-    if (!s->traced_frame) {   // a factor-1 state's first frame that does not go straight to the caller
-        HIP_CHECK(hipMalloc(&s->traced_frame, (size_t)s->width * s->height * 4 * sizeof(float)));
-        for (auto& ev : s->ev_resolve)
-            if (!ev) HIP_CHECK(hipEventCreate(&ev));
-    }
-    if (to.accumulate && !s->accumulation) HIP_CHECK(hipMalloc(&s->accumulation, (size_t)w * h * 4 * sizeof(float)));
     float taps[GR_FILTER_MAX_TAPS];
     int tap_count = 0;
-    if (filtered) {   // the frame a state with a filter resolves into (geodesic_hip_internal.h, "Filtered frames"): allocated once, freed with the state
-        GR_CHECK(gr_filter_taps(s->filter, factor, taps, &tap_count));
-    }
-    if (resolves && !s->filtered_frame) HIP_CHECK(hipMalloc(&s->filtered_frame, (size_t)w * h * 4 * sizeof(float)));
-    if (glared) GR_CHECK(allocate_glare_frames(s));
-    if (toned) GR_CHECK(allocate_tone_memory(s, to.format));
+    if (s->filter != GR_FILTER_BOX) GR_CHECK(gr_filter_taps(s->filter, s->supersample, taps, &tap_count));   // (geodesic_hip_internal.h, "Filtered frames")
+    GR_CHECK(allocate_missing(s, plan.needs, false));
     if (to.accumulate && to.first) s->accumulated = 0;   // (a sub-frame that fails below leaves nothing to deliver)
+    gr_frame_options traced = opt;   // the frame behind it: blocks of factor x as many rows
+    traced.block_rows *= s->supersample;
     GR_CHECK(render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
                                  s->traced_frame, &traced));
-    const bool strips = opt.mode == GR_MODE_FUSED && opt.strip_count > 1;   // (as the fused path reads them; the reference-shaped sequence renders whole frames)
     const bool timed = opt.time_kernels == 1;
     if (timed) HIP_CHECK(hipEventRecord(s->ev_resolve[0], (hipStream_t)stream));
-    // a state with a filter: the filtered frame - straight into the caller's memory where that is float4 - and the sink from it at factor 1
-    if (finished) {
-        // a state with a glare or a tone: the resolved frame at the output size, then finish_frame - the last stage straight into the
-        // caller's memory where that is float4 - and the sink from the state's frame at factor 1
-        if (filtered) GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, s->filtered_frame, w, h, factor, taps, tap_count));
-        else if (factor > 1) GR_CHECK(gr_resolve_supersampled(p, stream, s->traced_frame, s->filtered_frame, w, h, factor, 0, 0, 1, 0));
-        const void* resolved = resolves ? s->filtered_frame : s->traced_frame;
-        GR_CHECK(finish_frame(s, p, stream, resolved, to.format, to.layout, to.out));
-    } else {
-    const bool direct = filtered && !to.accumulate && to.format == GR_FRAME_F32;
-    if (filtered) GR_CHECK(gr_resolve_filtered(p, stream, s->traced_frame, direct ? to.out : s->filtered_frame, w, h, factor, taps, tap_count));
-    const void* src = filtered ? s->filtered_frame : s->traced_frame;
-    if (to.accumulate) GR_CHECK(gr_shutter_accumulate(p, stream, src, s->accumulation, w, h, filtered ? 1 : factor, to.weight, to.first));
-    else if (!direct) GR_CHECK(encode_frame(p, stream, to.format, to.layout, src, w, h, filtered ? 1 : factor, strips ? &opt : nullptr, to.out));
-    }
+    GR_CHECK(run_stages(plan, s, p, stream, to, &opt, taps, tap_count));
     if (timed) {
         HIP_CHECK(hipEventRecord(s->ev_resolve[1], (hipStream_t)stream));
         s->resolve_timed = true;
@@ -1874,7 +1857,7 @@ static int deliver_frame(const char* name, const sink& to, gr_render_state* s, g
     return GR_OK;
 }
 
-// gr_render_frame and its three encoded kin by format.  All but float4 refuse a NULL and what their launch would of `out` before anything is rendered or allocated.
+// gr_render_frame and its three encoded kin by format. All but float4 refuse a NULL and what their launch would of `out` before anything is rendered or allocated.
 int gr_internal_render_frame_as(int format, int layout, gr_render_state* s, gr_program* p, const gr_metric* m, void* stream, const gr_camera* camera,
                                 const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
                                 int bg_width, int bg_height, int bg_levels, void* out, const gr_frame_options* options) {
@@ -1884,10 +1867,8 @@ int gr_internal_render_frame_as(int format, int layout, gr_render_state* s, gr_p
         if (!s || !p || !m || !camera || !out) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, (std::string(f.entry) + ": null argument").c_str());
         GR_CHECK(refuse_output(f.entry, format, layout, out, s, options ? options->strip_count : 1));
     }
-    if (s) s->resolve_timed = false;
-    // (a factor-1 box state's float4 frame goes straight to the caller unless a glare or a tone is set; out == NULL stops after the records: nothing was shaded, nothing to resolve)
-    if (format == GR_FRAME_F32 && (!s || (s->supersample == 1 && s->filter == GR_FILTER_BOX && !s->glare_set && !s->tone_set) || !out))
-        return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out, options);
+    if (!s) return render_traced_frame(s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels, out, options);   // (float4: refused there)
+    s->resolve_timed = false;
     return deliver_frame(f.entry, sink{format, layout, out, false, 0.f, 0}, s, p, m, stream, camera, features, cfg_values, num_cfg_values, bg1, bg2,
                          bg_width, bg_height, bg_levels, options);
 }
@@ -1948,13 +1929,11 @@ int gr_deliver_accumulated(gr_render_state* s, gr_program* p, void* stream, int 
     GR_CHECK(refuse_output("gr_deliver_accumulated", format, layout, out, s, 1));
     if (!s->accumulated || !s->accumulation)
         return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_deliver_accumulated: the state holds no accumulation (gr_render_subframe first)");
-    HIP_CHECK(hipSetDevice(s->device));
-    if (s->glare_set || s->tone_set) {   // the glare of the accumulation, then its meter and tone - into the state's own frames, or the caller's float4 memory -, then the encode of that
-        if (s->glare_set) GR_CHECK(allocate_glare_frames(s));
-        if (s->tone_set) GR_CHECK(allocate_tone_memory(s, format));
-        return finish_frame(s, p, stream, s->accumulation, format, layout, out);
-    }
-    return encode_frame(p, stream, format, layout, s->accumulation, s->out_width, s->out_height, 1, nullptr, out);
+    const dp::plan plan = plan_delivery(s, dp::DELIVER_ACCUMULATED, format, out, nullptr);
+    if (plan.refused) return gr_internal::refuse("gr_deliver_accumulated", plan.refused);
+    HIP_CHECK(hipSetDevice(s->device));   // (nothing is rendered here that would set it)
+    GR_CHECK(allocate_missing(s, plan.needs, true));
+    return run_stages(plan, s, p, stream, sink{format, layout, out, false, 0.f, 0}, nullptr, nullptr, 0);
 }
 
 }  // extern "C"

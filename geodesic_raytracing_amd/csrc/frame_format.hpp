@@ -1,5 +1,5 @@
 // frame_format.hpp — the formats a frame leaves the device in: one table, and what an output is refused for on account of its format.
-// Host only (no HIP): tests/frame_format_check.cpp compiles frame_format.cpp alone.  frame.cpp, capi.cpp, tiled.cpp and imageio.cpp read it.
+// Host only (no HIP): tests/frame_format_check.cpp compiles frame_format.cpp alone.  frame.cpp, frame_launch.cpp, tiled.cpp and imageio.cpp read it.
 #pragma once
 
 #include <cstdint>

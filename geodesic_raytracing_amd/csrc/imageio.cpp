@@ -572,7 +572,7 @@ int gr_filter_taps(int filter, int factor, float taps[GR_FILTER_MAX_TAPS], int* 
     return GR_OK;
 }
 
-// what gr_filter_frame and the launcher gr_resolve_filtered (capi.cpp) both refuse about a table; NULL: nothing wrong
+// what gr_filter_frame and the launcher gr_resolve_filtered (frame_launch.cpp) both refuse about a table; NULL: nothing wrong
 extern "C" const char* gr_internal_filter_table_error(int factor, const float* taps, int count) {
     if (factor < 1 || factor > 4) return "a factor outside 1 to 4";
     if (count < 1 || count > GR_FILTER_MAX_TAPS) return "a count of taps outside 1 to 16";
@@ -629,7 +629,7 @@ GR_NO_CONTRACTION int gr_filter_frame(const float* src, int width, int height, i
 
 // ---- glare: a PSF and an exposure on the resolved frame - the host statement (geodesic_hip_internal.h, "Glare"; kernels/glare.hip's launches
 // behind gr_apply_glare are held to gr_glare_frame bit for bit).
-// what gr_glare_frame, gr_apply_glare (capi.cpp) and gr_render_state_set_glare (frame.cpp) refuse about a glare, under the caller's name and by the field's
+// what gr_glare_frame, gr_apply_glare (frame_launch.cpp) and gr_render_state_set_glare (frame.cpp) refuse about a glare, under the caller's name and by the field's
 int gr_internal_check_glare(const char* who, const gr_glare* g) {
     std::string wrong;
     if (!std::isfinite(g->core)) wrong = "core is not finite";

@@ -289,18 +289,20 @@ int next_slot(gr_tiled* t, hipStream_t stream, frame_slot** out) {
     return GR_OK;
 }
 
-// whether the state's frames go through a PSF (gr_render_state_set_glare): such a state renders whole frames only
-bool state_has_glare(const gr_render_state* s) {
+// What a split frame refuses of a state under the entry point's `name`: a filter wider than a pixel, a PSF and a histogram all read beyond
+// a strip's rows (halo rows and their exchange are a change of their own), so a state with one renders whole frames only.
+int refuse_whole_frame_state(const char* name, const gr_render_state* s) {
+    const auto refuse = [name](const char* which) { return gr_internal::refuse(name, std::string("a render state with a ") + which); };
+    int filter = GR_FILTER_BOX, glare_set = 0, tone_set = 0;
+    gr_render_state_filter(s, &filter);
+    if (filter != GR_FILTER_BOX) return refuse("filter (gr_render_state_set_filter) renders whole frames only; a split frame takes GR_FILTER_BOX");
     auto glare = std::make_unique<gr_glare>();
-    int is_set = 0;
-    return gr_render_state_glare(s, glare.get(), &is_set) == GR_OK && is_set;
-}
-
-// ... or are metered and toned (gr_render_state_set_tone): whole frames only too
-bool state_has_tone(const gr_render_state* s) {
+    if (gr_render_state_glare(s, glare.get(), &glare_set) == GR_OK && glare_set)
+        return refuse("glare (gr_render_state_set_glare) renders whole frames only: the PSF reads across strip borders");
     gr_tone tone;
-    int is_set = 0;
-    return gr_render_state_tone(s, &tone, &is_set) == GR_OK && is_set;
+    if (gr_render_state_tone(s, &tone, &tone_set) == GR_OK && tone_set)
+        return refuse("tone (gr_render_state_set_tone) renders whole frames only: a histogram of a strip is not the frame's");
+    return GR_OK;
 }
 
 }  // namespace
@@ -577,16 +579,7 @@ int gr_render_frame_tiled_as(gr_tiled* t, gr_render_state* s, gr_program* p, con
     if (t->transport == GR_TRANSPORT_PEER && !frame_on_root) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "peer transport: every participant is given the root's frame buffer");
     if (!s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
     if (t->device < 0) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "this participant was created without a device (schedule tests): nothing to render with");
-    {   // (a filter wider than a pixel reads across strip borders: halo rows and their exchange are a change of their own)
-        int filter = GR_FILTER_BOX;
-        gr_render_state_filter(s, &filter);
-        if (filter != GR_FILTER_BOX)
-            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled_as: a render state with a filter (gr_render_state_set_filter) renders whole frames only; a split frame takes GR_FILTER_BOX");
-        if (state_has_glare(s))
-            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled_as: a render state with a glare (gr_render_state_set_glare) renders whole frames only: the PSF reads across strip borders");
-        if (state_has_tone(s))
-            return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled_as: a render state with a tone (gr_render_state_set_tone) renders whole frames only: a histogram of a strip is not the frame's");
-    }
+    GR_CHECK(refuse_whole_frame_state("gr_render_frame_tiled_as", s));
     {   // (the staging buffers and the blocks' places in the root's frame are those of the participant's frame size: the size of the
         // state's frames, which a supersampled state traces at factor x that)
         int factor = 1, tw = 0, th = 0;
@@ -645,15 +638,9 @@ int gr_render_frame_tiled(gr_tiled* t, gr_render_state* s, gr_program* p, const 
                           const gr_features* features, const float* cfg_values, int num_cfg_values, const void* bg1, const void* bg2,
                           int bg_width, int bg_height, int bg_levels, void* frame_on_root, const gr_frame_options* options, int rotation) {
     if (!t || !s || !p || !m || !camera) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "null argument");
-    int factor = 1, filter = GR_FILTER_BOX;
+    int factor = 1;
     gr_render_state_supersample(s, &factor, nullptr, nullptr);
-    gr_render_state_filter(s, &filter);
-    if (filter != GR_FILTER_BOX)
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a render state with a filter (gr_render_state_set_filter) renders whole frames only; a split frame takes GR_FILTER_BOX");
-    if (state_has_glare(s))
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a render state with a glare (gr_render_state_set_glare) renders whole frames only: the PSF reads across strip borders");
-    if (state_has_tone(s))
-        return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a render state with a tone (gr_render_state_set_tone) renders whole frames only: a histogram of a strip is not the frame's");
+    GR_CHECK(refuse_whole_frame_state("gr_render_frame_tiled", s));
     if (factor != 1) return gr_internal_fail(GR_ERROR_INVALID_ARGUMENT, "gr_render_frame_tiled: a supersampled render state (gr_render_state_create_supersampled) renders its split frames through gr_render_frame_tiled_as; this entry point takes a state of factor 1");
     return gr_render_frame_tiled_as(t, s, p, m, stream_v, camera, features, cfg_values, num_cfg_values, bg1, bg2, bg_width, bg_height, bg_levels,
                                     frame_on_root, options, rotation, GR_FRAME_F32);

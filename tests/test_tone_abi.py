@@ -317,9 +317,10 @@ def test_the_kernels_are_in_the_setup_module_only_and_the_frame_paths_sources_ar
     assert (waves, counters) == (4, 385) and waves * counters * 4 <= 64 * 1024   # static LDS a workgroup
     assert lanes == 64 * waves and tile == lanes * per_lane
     # the launcher's tile and workgroup are the kernel's: a grid sized by another tile would leave pixels uncounted
-    launcher = re.search(r"static const unsigned long long METER_TILE = (\d+), METER_MAX_WORKGROUPS = (\d+);\s*static const unsigned METER_LANES = (\d+);", capi)
+    launchers = open(os.path.join(CSRC, "frame_launch.cpp")).read()   # (gr_meter_frame's file)
+    launcher = re.search(r"static const unsigned long long METER_TILE = (\d+), METER_MAX_WORKGROUPS = (\d+);\s*static const unsigned METER_LANES = (\d+);", launchers)
     assert launcher and (int(launcher.group(1)), int(launcher.group(3))) == (tile, lanes) and int(launcher.group(2)) >= 1
-    assert "(pixels + METER_TILE - 1) / METER_TILE" in capi and "K_METER_HISTOGRAM, stream, grid, 1, METER_LANES, 1" in capi
+    assert "(pixels + METER_TILE - 1) / METER_TILE" in launchers and "K_METER_HISTOGRAM, stream, grid, 1, METER_LANES, 1" in launchers
 
 
 def test_the_setup_module_cross_compiles_with_the_three_kernels(tmp_path, monkeypatch):
